@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- FP8 quantize+dequantize throughput on MI355X (driver contract).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line: `value`, `ms_per_step` (wall milliseconds
+of one timed step) and the event-timed `roofline` of those steps.  Everything else the line can carry (live PMC
+traffic, `cpu_baseline`, `north_star_path`, `extras`, and at N > 1 the fp32-wire run) is measured only with --full.
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs).
 
 Headline workload (BASELINE.json config 2, scaled as north_star allows: "synthetic NxCxKxK tensors"):
     a conv1-shaped weight tensor [2^21, 3, 7, 7] fp32 per GPU (308 M elements, 1.23 GB in +
@@ -36,6 +41,7 @@ compute stub and scaled-down tensors, and prints every collective with its byte 
 
 The JSON line also carries:
   roofline      the dominant kernel's algorithmic bytes (8 B/element) / its HIP-event launch time
+With --full, also:
   cpu_baseline  value: the reference's eager ATen op chain on the host cores (kind "reference-equivalent"); port_value: the
                 fused C port of the oracle (oracle/fp8q_oracle.c, OpenMP); bounded samples, rank 0, N=1
   extras        other kernels of the path on their own shapes (not part of `value`)
@@ -102,8 +108,7 @@ def measure_traffic(timeout_s=60):
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         out = tempfile.mkdtemp(prefix="fp8q_pmc_", dir="/tmp")
         cmd = [prof, "--pmc", ctr, "--output-format", "csv", "-d", out, "-o", "b", "--", sys.executable,
-               os.path.abspath(__file__), "--steps", "3", "--warmup", "1", "--no-extras", "--no-cpu-baseline",
-               "--no-north-star-path", "--no-traffic"]
+               os.path.abspath(__file__), "--steps", "3", "--warmup", "1"]          # a plain run: the headline alone
         try:
             subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=timeout_s)
             got = []
@@ -970,11 +975,37 @@ def dry_run(args, world, rank):
         sys.exit(f"bench.py: dry run spanned {int(one.item())} ranks, expected {R}")
 
 
+DUMP_CHANNELS = 1 << 16        # whole output channels sampled by --dump-outputs: 38.5 MB of float32
+DUMP_GROUPS = 1 << 20          # float64 sums over contiguous channel groups: 8.4 MB, every element of the output counted
+
+
+def dump_outputs(out_dir, y):
+    """--dump-outputs: the tensor a caller of the timed path receives from its last step (the quantized [C,3,7,7]
+    weights), kept under 64 MB:
+      y_sample.npy      float32 [<= 2^16, 3, 7, 7]  the channels np.random.default_rng(0) picks, in ascending order
+      y_group_sums.npy  float64 [<= 2^20]           sums of y over contiguous groups of channels (the last group padded)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    C = y.shape[0]
+    idx = np.sort(np.random.default_rng(0).choice(C, size=min(C, DUMP_CHANNELS), replace=False))
+    np.save(os.path.join(out_dir, "y_sample.npy"), y[torch.from_numpy(idx).to(y.device)].cpu().numpy())
+    rows = y.reshape(C, -1).sum(1, dtype=torch.float64)
+    G = min(C, DUMP_GROUPS)
+    rows = torch.cat([rows, rows.new_zeros((-C) % G)])
+    np.save(os.path.join(out_dir, "y_group_sums.npy"), rows.view(G, -1).sum(1).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)      # 0.2 s timed region by default
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the line can carry: live PMC traffic, "
+                         "cpu_baseline, north_star_path, extras (incl. BASELINE configs 3 and 4), the fp32 wire at N > 1; "
+                         "the --no-* options below leave out parts of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step to DIR/*.npy (a seeded sample; see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--no-traffic", action="store_true",
@@ -997,6 +1028,8 @@ def main():
                     help="process-group backend for --gpus N > 1 (nccl = RCCL; gloo only for smoke-testing the "
                          "multi-process path on a box with fewer GPUs than ranks)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1098,6 +1131,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, y if world == 1 else full[0])
     collective_s = 0.0
     if world > 1:
         t = torch.tensor([elapsed], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
@@ -1106,19 +1141,20 @@ def main():
         e = timing["events"]       # per step: before | encode done | all-gather done | decode done
         step_s = sorted((e[4 * i].elapsed_time(e[4 * i + 1]) + e[4 * i + 2].elapsed_time(e[4 * i + 3])) * 1e-3 for i in range(args.steps))
         collective_s = sum(e[4 * i + 1].elapsed_time(e[4 * i + 2]) * 1e-3 for i in range(args.steps)) / max(args.steps, 1)
-        # the fp32 wire form of the same flow (round 5's headline), same steps, outside the judged region
-        for _ in range(min(args.warmup, 2)):
-            step_fp32()
-        torch.cuda.synchronize()
-        dist.barrier()
-        t32 = time.perf_counter()
-        for _ in range(args.steps):
-            step_fp32()
-        torch.cuda.synchronize()
-        dist.barrier()
-        t32 = torch.tensor([time.perf_counter() - t32], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
-        dist.all_reduce(t32, op=dist.ReduceOp.MAX)
-        elapsed_fp32 = float(t32.item())
+        if args.full:
+            # the fp32 wire form of the same flow (round 5's headline), same steps, outside the judged region
+            for _ in range(min(args.warmup, 2)):
+                step_fp32()
+            torch.cuda.synchronize()
+            dist.barrier()
+            t32 = time.perf_counter()
+            for _ in range(args.steps):
+                step_fp32()
+            torch.cuda.synchronize()
+            dist.barrier()
+            t32 = torch.tensor([time.perf_counter() - t32], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
+            dist.all_reduce(t32, op=dist.ReduceOp.MAX)
+            elapsed_fp32 = float(t32.item())
     else:
         step_s = sorted(a.elapsed_time(b) * 1e-3 for a, b in evs)
     kern_s = sum(step_s) / max(len(step_s), 1)
@@ -1135,7 +1171,7 @@ def main():
     if rank == 0:
         traffic, traffic_source = None, None
         tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if world == 1 and not args.no_traffic:
+        if world == 1 and args.full and not args.no_traffic:
             traffic, detail = measure_traffic()
             if traffic is not None:
                 traffic_source = ("measured in this run: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) over "
@@ -1180,11 +1216,12 @@ def main():
             line.update(kernel_us=round(kern_s * 1e6, 1), collective_us=round(collective_s * 1e6, 1),
                         wire="codes_u8 (1 byte per element; ranges fixed, not shipped)",
                         xgmi_bytes_received_per_rank=int(rx_bytes),
-                        xgmi_gb_s=round(rx_bytes / max(collective_s, 1e-9) / 1e9, 2) if args.backend == "nccl" else None,
-                        value_fp32_wire=round(total_elem * args.steps / elapsed_fp32 / 1e9, 2),
-                        fp32_wire_ms_per_step=round(elapsed_fp32 / args.steps * 1e3, 4),
-                        fp32_wire_xgmi_bytes_received_per_rank=int(rx_bytes_fp32))
-        if world == 1 and not args.no_cpu_baseline:
+                        xgmi_gb_s=round(rx_bytes / max(collective_s, 1e-9) / 1e9, 2) if args.backend == "nccl" else None)
+            if args.full:
+                line.update(value_fp32_wire=round(total_elem * args.steps / elapsed_fp32 / 1e9, 2),
+                            fp32_wire_ms_per_step=round(elapsed_fp32 / args.steps * 1e3, 4),
+                            fp32_wire_xgmi_bytes_received_per_rank=int(rx_bytes_fp32))
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # bounded sample: generate only what the CPU leg needs
             sample_ch = 1 << 18
             xc = x[:sample_ch].cpu()
@@ -1206,7 +1243,7 @@ def main():
     if world > 1:
         del full
     torch.cuda.empty_cache()
-    if not args.no_north_star_path:
+    if args.full and not args.no_north_star_path:
         nsp = north_star_path(args, ops, dev, rank, world, args.backend)     # every rank takes part
         if rank == 0:
             line["north_star_path"] = nsp
@@ -1222,7 +1259,7 @@ def main():
         seen = int(one.item())
     if rank == 0:
         line["ranks_seen"] = seen
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             line["extras"] = extras(ops, dev)
             if not args.no_model_configs:
                 line["extras"].update(model_configs(ops, dev))

@@ -100,7 +100,7 @@ def test_bare_two_rank_gloo_bench_on_one_gpu():
     """The multi-process path end to end on the one-GPU box: bare `python bench.py --gpus 2 --backend gloo` re-executes
     itself through torch.distributed.run, both ranks share cuda:0, every section of the line is produced and the
     collectives saw 2 ranks.  (gloo carries device tensors through the host: its times say nothing about xGMI.)"""
-    r = _run(["--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--channels-per-gpu", "65536"], 1500)
+    r = _run(["--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--channels-per-gpu", "65536", "--full"], 1500)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     line = _line(r.stdout)
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2 and line["scaling"] == "weak"
@@ -128,7 +128,7 @@ def test_bare_two_rank_gloo_bench_on_one_gpu():
 def test_single_gpu_line_carries_roofline_cpu_baseline_and_model_configs():
     """N = 1 as the driver runs it (fewer steps): the contract's keys, `roofline`, `cpu_baseline` (the C port + the
     reference-equivalent eager chain), and BASELINE configs 3 / 4 under `extras`."""
-    r = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--no-north-star-path"], 1500)
+    r = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-north-star-path"], 1500)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     line = _line(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -172,3 +172,24 @@ def test_single_gpu_line_carries_roofline_cpu_baseline_and_model_configs():
         assert c["logits_bit_identical_with_oracle_quantizers"] is True and c["quantized_weights_bit_identical_with_oracle"] is True
         assert c["top1_delta_attributable_to_kernels"] == 0
         assert 0.0 <= c["argmax_agreement_with_fp32"] <= 1.0 and c["weights_checked"] >= 21
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and reports the headline alone; --dump-outputs writes the
+    last step's output: a seeded float32 sample of whole channels and float64 sums over channel groups, under 64 MB."""
+    import numpy as np
+    r = _run(["--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path)], 600)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+    line = _line(r.stdout)
+    assert line["steps"] == 7 and line["ms_per_step"] > 0 and line["unit"] == "Gelem/s" and line["dtype"] == "f32"
+    assert abs(line["value"] - (1 << 21) * 147 / (line["ms_per_step"] * 1e-3) / 1e9) <= 0.01 * line["value"]
+    for k in ("cpu_baseline", "extras", "north_star_path"):
+        assert k not in line, k
+    assert "NOT measured in this run" in line["roofline"]["traffic_source"]
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["y_group_sums.npy", "y_sample.npy"], files
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
+    ys, sums = np.load(tmp_path / "y_sample.npy"), np.load(tmp_path / "y_group_sums.npy")
+    assert ys.dtype == np.float32 and ys.shape == (1 << 16, 3, 7, 7) and np.isfinite(ys).all() and ys.any()
+    assert sums.dtype == np.float64 and sums.shape == (1 << 20,) and np.isfinite(sums).all()
