@@ -1,0 +1,387 @@
+// fp8q_int.hip -- uniform (INT) fake-quantization on gfx950: the reference's SymmetricUniformQuantizer /
+// AsymmetricUniformQuantizer (uniform_quantizers.py) with linear scale domain, and their range setting.
+//
+// Arithmetic contract (bit for bit the reference's fp32 op chain, every op rounded on its own; -ffp-contract=off):
+//   range       xmin' = min(xmin, 0),  xmax' = max(xmax, eps)                      (_tensorize_min_max)
+//               asymmetric: delta = (xmax' - xmin') / int_max,  zero_float = -xmin' / delta
+//               symmetric:  signed = (min over ALL channels of xmin') < 0     -- one flag per quantizer; a NaN
+//                           anywhere makes it false (torch.min propagates NaN, NaN < 0 is false)
+//                           delta = max(|xmin'|, xmax') / int_max(signed)
+//   quantize    scale = max(delta, eps)
+//               zp = clamp(rint(zero_float), int_min, int_max)  (asymmetric),  0 (symmetric)
+//               y  = scale * (clamp(rint(x / scale) + zp, int_min, int_max) - zp)
+//               [int_min, int_max] = [-2^(n-1), 2^(n-1) - 1] when signed, [0, 2^n - 1] otherwise (asymmetric:
+//               unsigned); the symmetric sign is read from device memory -- no host round trip.
+//   min / max / clamp propagate NaN as torch's do (a bare fminf / fmaxf would not); +-inf saturates to the clamp
+//   ends.  min(xmin, 0) keeps an xmin of -0 (torch's scalar loop: per-tensor ranges; torch's vectorised CPU loop
+//   returns the +0 operand -- the one case where the two torch paths themselves differ).  rint rounds half to even.
+//
+// x / scale without a division per element: r = fl32(1 / scale) once per channel (IEEE division), q0 = fl32(x * r).
+// |q0 - x/scale| <= |x/scale| (2^-24 + 2^-24 + 2^-48) and |fl32(x/scale) - x/scale| <= 2^-24 |x/scale|, so q0 and
+// fl32(x / scale) differ by less than 2^-22 |q0| (1 + 2^-22).  rint(q0) == rint(fl32(x / scale)) unless q0 lies
+// within that distance of a rounding tie: lanes with |q0 - rint(q0)| >= 0.5 - 2^-20 |q0| redo the IEEE division
+// (4x margin; a tie itself is always redone).  Subnormal quotients have |q| < 0.5 and round to a zero of x's sign on
+// both paths; an overflow to inf on one path only happens at |q| > 2^127, where both clamp to int_max / int_min; NaN
+// fails the comparison and stays NaN.
+//
+// Kernels:
+//   k_int_quant<RANGE, PC, VEC, NT>  one aligned 4096-element chunk per block (K1's streaming: 16 B per lane per
+//                 access, 4 accesses in flight, neighbouring blocks on neighbouring chunks).  The channel constants
+//                 {scale, 1/scale, zp} of the rows overlapping the chunk are built once per block in LDS, from
+//                 (delta, zero_float) -- or, RANGE, from (xmin, xmax), with the block in which a row starts writing
+//                 that row's delta / zero_float (and block 0 the sign): range-set and quantize in one launch.
+//   k_int_sign    the global sign of a symmetric per-channel range with more than kSignInline channels (fewer: every
+//                 block of k_int_quant / k_int_range folds it itself from the xmin vector).
+//   k_int_range   range-set alone: (xmin, xmax) -> delta, zero_float, signed.
+#include "fp8q_common.h"
+
+namespace {
+
+constexpr int kIntChunk = 4096;       // elements per block: 16 KiB of fp32
+constexpr int kSignInline = 2048;     // symmetric per-channel: up to here every block reduces the xmin vector itself
+
+struct IntArgs {
+    const float *a;          // delta  | RANGE: x_min
+    const float *b;          // zero_float (asymmetric) | RANGE: x_max
+    float *delta_out;        // RANGE: delta written here
+    float *zf_out;           // RANGE, asymmetric: zero_float written here
+    unsigned char *sflag;    // symmetric: the sign (read; RANGE with an inline fold: written by block 0)
+    int64_t n;               // elements
+    int64_t C;               // rows of the range vectors (1: per tensor)
+    int inner;               // row length (PC)
+    uint32_t magic;          // l / inner for l < inner + 4096 (inner < 4096)
+    int nc_max;              // LDS entries per block
+    int symmetric;
+    int sign_inline;         // RANGE + symmetric: fold the sign from the xmin vector in every block
+    float eps;
+    float n_hi_u;            // 2^n - 1
+    float n_hi_s;            // 2^(n-1) - 1
+    float n_lo_s;            // -2^(n-1)
+};
+
+__device__ __forceinline__ float t_min(float a, float b)   // torch.min(a, b) of the scalar loop: a unless b < a
+{
+    return (a != a) ? a : ((b != b) ? b : (b < a ? b : a));
+}
+__device__ __forceinline__ float t_max(float a, float b)
+{
+    return (a != a) ? a : ((b != b) ? b : (b > a ? b : a));
+}
+__device__ __forceinline__ float t_clamp(float v, float lo, float hi)   // torch.clamp: NaN passes, v when equal
+{
+    return (v != v) ? v : (v < lo ? lo : (v > hi ? hi : v));
+}
+
+// the sign of a symmetric range: no NaN in x_min and some x_min < 0 (x_min' = min(x_min, 0) has the same predicates)
+__device__ __forceinline__ bool block_sign(const float *__restrict__ xmin, int64_t C)
+{
+    int neg = 0, nan = 0;
+    for (int64_t i = threadIdx.x; i < C; i += kBlock) {
+        const float v = xmin[i];
+        neg |= v < 0.0f;
+        nan |= v != v;
+    }
+    neg = __syncthreads_or(neg);
+    nan = __syncthreads_or(nan);
+    return neg && !nan;
+}
+
+struct Range {
+    float delta, zf;
+};
+
+__device__ __forceinline__ Range range_of(float xmin, float xmax, bool symmetric, float int_max, float eps)
+{
+    const float mn = t_min(xmin, 0.0f);
+    const float mx = t_max(xmax, eps);
+    Range r;
+    if (symmetric) {
+        r.delta = t_max(fabsf(mn), mx) / int_max;
+        r.zf = 0.0f;
+    } else {
+        r.delta = (mx - mn) / int_max;
+        r.zf = -mn / r.delta;
+    }
+    return r;
+}
+
+// {scale, 1/scale, zp, -}
+__device__ __forceinline__ float4 consts_of(float delta, float zf, bool symmetric, float lo, float hi, float eps)
+{
+    const float s = t_max(delta, eps);
+    const float zp = symmetric ? 0.0f : t_clamp(rintf(zf), lo, hi);
+    return make_float4(s, 1.0f / s, zp, 0.0f);
+}
+
+__device__ __forceinline__ float int_one(float v, const float4 k, float lo, float hi)
+{
+    const float q0 = v * k.y;
+    float rq = rintf(q0);
+    if (fabsf(q0 - rq) >= 0.5f - fabsf(q0) * 0x1p-20f) rq = rintf(v / k.x);
+    const float t = t_clamp(rq + k.z, lo, hi);
+    return k.x * (t - k.z);
+}
+
+template <bool RANGE, bool PC, bool VEC, bool NT>
+__global__ void __launch_bounds__(kBlock)
+k_int_quant(const float *__restrict__ x, float *__restrict__ y, IntArgs a)
+{
+    extern __shared__ float4 kc[];    // nc_max channel constants
+    __shared__ int s_sign;
+    const int tid = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * kIntChunk;
+    const int64_t e1 = e0 + kIntChunk < a.n ? e0 + kIntChunk : a.n;
+
+    bool sgn = false;
+    if (a.symmetric) {
+        if (RANGE && a.sign_inline) {
+            sgn = PC ? block_sign(a.a, a.C) : (a.a[0] < 0.0f);
+            if (blockIdx.x == 0 && tid == 0) a.sflag[0] = (unsigned char)sgn;
+        } else {
+            if (tid == 0) s_sign = a.sflag[0] != 0;
+            __syncthreads();
+            sgn = s_sign != 0;
+        }
+    }
+    const float lo = sgn ? a.n_lo_s : 0.0f;
+    const float hi = (a.symmetric && sgn) ? a.n_hi_s : a.n_hi_u;
+
+    const int64_t c_lo = PC ? e0 / a.inner : 0;
+    const int phase = PC ? (int)(e0 - c_lo * a.inner) : 0;
+    const int nc = PC ? (int)((e1 - 1) / a.inner - c_lo) + 1 : 1;
+    for (int i = tid; i < nc; i += kBlock) {
+        const int64_t c = c_lo + i;
+        float delta, zf;
+        if (RANGE) {
+            const Range r = range_of(a.a[c], a.b[c], a.symmetric, hi, a.eps);
+            delta = r.delta;
+            zf = r.zf;
+            if (PC ? c * a.inner >= e0 : blockIdx.x == 0) {   // the row starts in this chunk: this block reports it
+                a.delta_out[c] = delta;
+                if (!a.symmetric) a.zf_out[c] = zf;
+            }
+        } else {
+            delta = a.a[c];
+            zf = a.symmetric ? 0.0f : a.b[c];
+        }
+        kc[i] = consts_of(delta, zf, a.symmetric, lo, hi, a.eps);
+    }
+    __syncthreads();
+    float4 k0 = kc[0];
+
+    auto chan = [&](int64_t e) -> float4 {
+        if (!PC) return k0;
+        const uint32_t l = (uint32_t)(phase + (int)(e - e0));
+        const int ch = a.inner >= kIntChunk ? (int)(l >= (uint32_t)a.inner) : div_small(l, a.magic);
+        return kc[ch];
+    };
+
+    if (VEC) {
+        // x and y 16-byte aligned, e0 a multiple of 4096: groups of 4 are aligned
+        const int ngroups = (int)((e1 - e0) >> 2);
+        const vf4 *xv = reinterpret_cast<const vf4 *>(x + e0);
+        vf4 *yv = reinterpret_cast<vf4 *>(y + e0);
+        if (ngroups == kIntChunk / 4) {
+            vf4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = ld16<NT>(xv + u * kBlock + tid);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int64_t e = e0 + 4 * (u * kBlock + tid);
+                vf4 o;
+                o.x = int_one(v[u].x, chan(e), lo, hi);
+                o.y = int_one(v[u].y, chan(e + 1), lo, hi);
+                o.z = int_one(v[u].z, chan(e + 2), lo, hi);
+                o.w = int_one(v[u].w, chan(e + 3), lo, hi);
+                st16<NT>(yv + u * kBlock + tid, o);
+            }
+        } else {
+            for (int g = tid; g < ngroups; g += kBlock) {
+                const vf4 w = ld16<NT>(xv + g);
+                const int64_t e = e0 + 4 * (int64_t)g;
+                vf4 o;
+                o.x = int_one(w.x, chan(e), lo, hi);
+                o.y = int_one(w.y, chan(e + 1), lo, hi);
+                o.z = int_one(w.z, chan(e + 2), lo, hi);
+                o.w = int_one(w.w, chan(e + 3), lo, hi);
+                st16<NT>(yv + g, o);
+            }
+            for (int64_t e = e0 + 4 * (int64_t)ngroups + tid; e < e1; e += kBlock)
+                y[e] = int_one(x[e], chan(e), lo, hi);
+        }
+    } else {
+        for (int64_t e = e0 + tid; e < e1; e += kBlock) y[e] = int_one(x[e], chan(e), lo, hi);
+    }
+}
+
+__global__ void __launch_bounds__(1024) k_int_sign(const float *__restrict__ xmin, int64_t C, unsigned char *sflag)
+{
+    int neg = 0, nan = 0;
+    for (int64_t i = threadIdx.x; i < C; i += 1024) {
+        const float v = xmin[i];
+        neg |= v < 0.0f;
+        nan |= v != v;
+    }
+    neg = __syncthreads_or(neg);
+    nan = __syncthreads_or(nan);
+    if (threadIdx.x == 0) sflag[0] = (unsigned char)(neg && !nan);
+}
+
+__global__ void __launch_bounds__(kBlock) k_int_range(IntArgs a)
+{
+    __shared__ int s_sign;
+    bool sgn = false;
+    if (a.symmetric) {
+        if (a.sign_inline) {
+            sgn = a.C > 1 ? block_sign(a.a, a.C) : (a.a[0] < 0.0f);
+            if (blockIdx.x == 0 && threadIdx.x == 0) a.sflag[0] = (unsigned char)sgn;
+        } else {
+            if (threadIdx.x == 0) s_sign = a.sflag[0] != 0;
+            __syncthreads();
+            sgn = s_sign != 0;
+        }
+    }
+    const float hi = (a.symmetric && sgn) ? a.n_hi_s : a.n_hi_u;
+    for (int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x; c < a.C; c += (int64_t)gridDim.x * kBlock) {
+        const Range r = range_of(a.a[c], a.b[c], a.symmetric, hi, a.eps);
+        a.delta_out[c] = r.delta;
+        if (!a.symmetric) a.zf_out[c] = r.zf;
+    }
+}
+
+int int_bits(int n_bits, IntArgs &a)
+{
+    if (n_bits < 2 || n_bits > 16) return FP8Q_EUNSUPPORTED;
+    a.n_hi_u = ldexpf(1.0f, n_bits) - 1.0f;
+    a.n_hi_s = ldexpf(1.0f, n_bits - 1) - 1.0f;
+    a.n_lo_s = -ldexpf(1.0f, n_bits - 1);
+    return FP8Q_OK;
+}
+
+// the quantize launch; `range`: a / b are (x_min, x_max) and the launch also writes delta (zero_float, sign)
+int int_quant_launch(bool range, const float *x, float *y, int64_t C, int64_t inner, bool pc, IntArgs a,
+                     hipStream_t st)
+{
+    a.n = C * inner;
+    a.inner = pc ? (int)inner : 1;
+    a.magic = pc ? magic_of((int)inner) : 0u;
+    a.nc_max = pc ? (int)(kIntChunk / inner + 2 < (int64_t)C ? kIntChunk / inner + 2 : C) : 1;
+    const int64_t nblocks = cdiv(a.n, kIntChunk);
+    const size_t shmem = (size_t)a.nc_max * sizeof(float4);
+    const bool vec = (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+    const bool nt = a.n * 4 >= kNtBytes;
+    const dim3 g((unsigned)nblocks), b(kBlock);
+#define FP8Q_INT_LAUNCH(R, P)                                                                                         \
+    do {                                                                                                              \
+        if (vec && nt) hipLaunchKernelGGL((k_int_quant<R, P, true, true>), g, b, shmem, st, x, y, a);               \
+        else if (vec) hipLaunchKernelGGL((k_int_quant<R, P, true, false>), g, b, shmem, st, x, y, a);               \
+        else hipLaunchKernelGGL((k_int_quant<R, P, false, false>), g, b, shmem, st, x, y, a);                       \
+    } while (0)
+    if (range && pc) FP8Q_INT_LAUNCH(true, true);
+    else if (range) FP8Q_INT_LAUNCH(true, false);
+    else if (pc) FP8Q_INT_LAUNCH(false, true);
+    else FP8Q_INT_LAUNCH(false, false);
+#undef FP8Q_INT_LAUNCH
+    return launch_rc();
+}
+
+// shared argument checks of the quantize entry points
+int int_check_x(const float *x, const float *y, int64_t C, int64_t inner, int64_t n_range)
+{
+    if (!x || !y || C <= 0 || inner <= 0 || (n_range != 1 && n_range != C)) return FP8Q_EINVAL;
+    if ((n_range > 1 && inner > INT32_MAX) || C > INT64_MAX / inner || cdiv(C * inner, kIntChunk) > (int64_t)UINT32_MAX)
+        return FP8Q_EINVAL;
+    return FP8Q_OK;
+}
+
+// RANGE launches of the symmetric per-channel case: the sign first when the blocks cannot fold it themselves
+int int_sign_prepass(IntArgs &a, hipStream_t st)
+{
+    a.sign_inline = !(a.symmetric && a.C > kSignInline);
+    if (a.sign_inline) return FP8Q_OK;
+    hipLaunchKernelGGL(k_int_sign, dim3(1), dim3(1024), 0, st, a.a, a.C, a.sflag);
+    return launch_rc();
+}
+
+}  // namespace
+
+extern "C" {
+
+int fp8q_int_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, const float *delta,
+                          const float *zero_float, int64_t n_delta, const unsigned char *signed_flag, int n_bits,
+                          int symmetric, float eps, fp8q_stream_t stream)
+{
+    if (int rc = int_check_x(x, y, C, inner, n_delta)) return rc;
+    if (!delta || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
+    IntArgs a = {};
+    if (int rc = int_bits(n_bits, a)) return rc;
+    a.a = delta;
+    a.b = zero_float;
+    a.sflag = const_cast<unsigned char *>(signed_flag);   // read only (RANGE == false)
+    a.C = n_delta;
+    a.symmetric = symmetric != 0;
+    a.eps = eps;
+    const bool pc = n_delta > 1;
+    return int_quant_launch(false, x, y, pc ? C : 1, pc ? inner : C * inner, pc, a, (hipStream_t)stream);
+}
+
+int fp8q_int_set_range_f32(const float *x_min, const float *x_max, int64_t n, float *delta, float *zero_float,
+                           unsigned char *signed_flag, int n_bits, int symmetric, float eps, fp8q_stream_t stream)
+{
+    if (!x_min || !x_max || !delta || n <= 0 || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
+    IntArgs a = {};
+    if (int rc = int_bits(n_bits, a)) return rc;
+    a.a = x_min;
+    a.b = x_max;
+    a.delta_out = delta;
+    a.zf_out = zero_float;
+    a.sflag = signed_flag;
+    a.C = n;
+    a.symmetric = symmetric != 0;
+    a.eps = eps;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = int_sign_prepass(a, st)) return rc;
+    const int64_t nb = cdiv(n, kBlock);
+    hipLaunchKernelGGL(k_int_range, dim3((unsigned)(nb < kTargetBlocks ? nb : kTargetBlocks)), dim3(kBlock), 0, st, a);
+    return launch_rc();
+}
+
+int fp8q_int_range_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, const float *x_min,
+                                const float *x_max, int64_t n_range, float *delta, float *zero_float,
+                                unsigned char *signed_flag, int n_bits, int symmetric, float eps,
+                                fp8q_stream_t stream)
+{
+    if (int rc = int_check_x(x, y, C, inner, n_range)) return rc;
+    if (!x_min || !x_max || !delta || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
+    IntArgs a = {};
+    if (int rc = int_bits(n_bits, a)) return rc;
+    a.a = x_min;
+    a.b = x_max;
+    a.delta_out = delta;
+    a.zf_out = zero_float;
+    a.sflag = signed_flag;
+    a.C = n_range;
+    a.symmetric = symmetric != 0;
+    a.eps = eps;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = int_sign_prepass(a, st)) return rc;
+    const bool pc = n_range > 1;
+    return int_quant_launch(true, x, y, pc ? C : 1, pc ? inner : C * inner, pc, a, st);
+}
+
+int fp8q_int_minmax_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, float *row_min, float *row_max,
+                                 float *delta, float *zero_float, unsigned char *signed_flag, int n_bits, int symmetric,
+                                 float eps, void *ws, size_t ws_bytes, fp8q_stream_t stream)
+{
+    if (int rc = int_check_x(x, y, C, inner, C)) return rc;
+    if (!row_min || !row_max || !delta || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
+    IntArgs probe = {};
+    if (int rc = int_bits(n_bits, probe)) return rc;
+    if (int rc = fp8q_minmax_f32(x, C, inner, row_min, row_max, nullptr, FP8Q_FOLD_CURRENT, 0.0, 1, ws, ws_bytes,
+                                 stream))
+        return rc;
+    return fp8q_int_range_quantize_f32(x, y, C, inner, row_min, row_max, C, delta, zero_float, signed_flag, n_bits,
+                                       symmetric, eps, stream);
+}
+
+}  // extern "C"

@@ -92,6 +92,11 @@ SIGNATURES = {
     "fp8q_multi_plan_launches": (_i, [_vp]),
     "fp8q_multi_plan_destroy": (None, [_vp]),
     "fp8q_copy_f32": (_i, [_vp, _vp, _i64, _vp]),
+    "fp8q_int_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i, _i, _f, _vp]),
+    "fp8q_int_set_range_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "fp8q_int_range_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "fp8q_int_minmax_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp,
+                                          ctypes.c_size_t, _vp]),
 }
 
 

@@ -506,6 +506,138 @@ def minmax_quantize(x, mbits, n_bits=8, sign_bits=1, out=None):
     return y, mn, mx, mv
 
 
+def _int_ptrs(x, delta, zero_float, signed_flag, symmetric, n):
+    """Checks of the INT entry points' range buffers: fp32 [n] delta (and zero_float, asymmetric), a 1-byte sign
+    (symmetric: uint8 or bool), all contiguous on x's device.  Returns the three raw pointers (None where unused)."""
+    bufs = [("delta", delta, torch.float32)]
+    if symmetric:
+        bufs.append(("signed_flag", signed_flag, (torch.uint8, torch.bool)))
+    else:
+        bufs.append(("zero_float", zero_float, torch.float32))
+    for name, t, dt in bufs:
+        _require(t, name, dt, like=x)
+        if not t.is_contiguous() or t.numel() != (1 if name == "signed_flag" else n):
+            raise Fp8qError(f"{name} must be a contiguous tensor of {1 if name == 'signed_flag' else n} elements")
+    return (delta.data_ptr(), None if symmetric else zero_float.data_ptr(),
+            signed_flag.data_ptr() if symmetric else None)
+
+
+def _int_x(x, out, n_range):
+    """(x as the kernel reads it, y, C, inner, result): per tensor on a dense non-contiguous layout the storage as it
+    lies (the result keeps x's strides, as the elementwise ATen chain does); otherwise a contiguous [C, inner] view."""
+    flat = _dense_flat(x) if (n_range == 1 and out is None) else None
+    if flat is not None:
+        res = torch.empty_like(x)
+        flat_out = _dense_flat(res) if res.stride() == x.stride() else None
+        if flat_out is not None:
+            return flat, flat_out, 1, flat.numel(), res
+    x = x.contiguous()
+    C, inner = _rows(x, n_range != 1)
+    if n_range != 1 and n_range != C:
+        raise Fp8qError(f"the range has {n_range} elements, expected 1 or {C}")
+    y = _out(out, x)
+    return x, y, C, inner, y
+
+
+def int_quantize(x, delta, zero_float=None, signed_flag=None, n_bits=8, symmetric=False, eps=1e-8, out=None):
+    """Uniform (INT) quantize+dequantize with fixed ranges (uniform_quantizers.py forward, linear scale domain):
+    y = scale * (clamp(rint(x / scale) + zp, int_min, int_max) - zp).  delta (and zero_float, asymmetric) [1] or [C]
+    CUDA fp32; symmetric: signed_flag is the quantizer's 1-byte device sign, read by the kernel.  One launch."""
+    _require(x, "x")
+    delta = delta.detach().reshape(-1)
+    n = delta.numel()
+    zero_float = zero_float.detach().reshape(-1) if zero_float is not None else None
+    signed_flag = signed_flag.detach().reshape(-1) if signed_flag is not None else None
+    pd, pz, ps = _int_ptrs(x, delta, zero_float, signed_flag, symmetric, n)
+    xk, y, C, inner, res = _int_x(x, out, n)
+    if xk.numel() == 0:
+        return res
+    with _on_device(xk):
+        rc = lib().fp8q_int_quantize_f32(xk.data_ptr(), y.data_ptr(), C, inner, pd, pz, n, ps, int(n_bits),
+                                         int(bool(symmetric)), float(eps), _stream(xk))
+    check(rc, "fp8q_int_quantize_f32")
+    return res
+
+
+def _int_range_out(x_min, delta, zero_float, signed_flag, symmetric):
+    n = x_min.numel()
+    dev = x_min.device
+    if delta is None:
+        delta = torch.empty(x_min.shape, dtype=torch.float32, device=dev)
+    if zero_float is None and not symmetric:
+        zero_float = torch.empty(x_min.shape, dtype=torch.float32, device=dev)
+    if signed_flag is None and symmetric:
+        signed_flag = torch.empty((), dtype=torch.bool, device=dev)
+    return n, delta, zero_float, signed_flag
+
+
+def int_set_range(x_min, x_max, n_bits=8, symmetric=False, eps=1e-8, delta=None, zero_float=None, signed_flag=None):
+    """set_quant_range of the uniform quantizers on the device: (x_min, x_max) [n] -> (delta, zero_float, signed_flag)
+    (zero_float None when symmetric, signed_flag None when not).  Buffers passed in are written in place; missing
+    ones are allocated with x_min's shape (signed_flag: a 0-dim bool).  One launch, no host round trip."""
+    _require(x_min, "x_min")
+    _require(x_max, "x_max", like=x_min)
+    x_min, x_max = x_min.detach().contiguous(), x_max.detach().contiguous()
+    if x_max.numel() != x_min.numel() or x_min.numel() == 0:
+        raise Fp8qError("x_min and x_max must have the same, non-zero number of elements")
+    n, delta, zero_float, signed_flag = _int_range_out(x_min, delta, zero_float, signed_flag, symmetric)
+    pd, pz, ps = _int_ptrs(x_min, delta, zero_float, signed_flag, symmetric, n)
+    with _on_device(x_min):
+        rc = lib().fp8q_int_set_range_f32(x_min.data_ptr(), x_max.data_ptr(), n, pd, pz, ps, int(n_bits),
+                                          int(bool(symmetric)), float(eps), _stream(x_min))
+    check(rc, "fp8q_int_set_range_f32")
+    return delta, zero_float, signed_flag
+
+
+def int_range_quantize(x, x_min, x_max, n_bits=8, symmetric=False, eps=1e-8, delta=None, zero_float=None,
+                       signed_flag=None, out=None):
+    """int_set_range and int_quantize in ONE launch (the range-estimating forward).  Returns
+    (y, delta, zero_float, signed_flag) like int_set_range."""
+    _require(x, "x")
+    _require(x_min, "x_min", like=x)
+    _require(x_max, "x_max", like=x)
+    x_min, x_max = x_min.detach().contiguous(), x_max.detach().contiguous()
+    if x_max.numel() != x_min.numel() or x_min.numel() == 0:
+        raise Fp8qError("x_min and x_max must have the same, non-zero number of elements")
+    n, delta, zero_float, signed_flag = _int_range_out(x_min, delta, zero_float, signed_flag, symmetric)
+    pd, pz, ps = _int_ptrs(x, delta, zero_float, signed_flag, symmetric, n)
+    xk, y, C, inner, res = _int_x(x, out, n)
+    if xk.numel() == 0:
+        return (res,) + int_set_range(x_min, x_max, n_bits, symmetric, eps, delta, zero_float, signed_flag)
+    with _on_device(xk):
+        rc = lib().fp8q_int_range_quantize_f32(xk.data_ptr(), y.data_ptr(), C, inner, x_min.data_ptr(),
+                                               x_max.data_ptr(), n, pd, pz, ps, int(n_bits), int(bool(symmetric)),
+                                               float(eps), _stream(xk))
+    check(rc, "fp8q_int_range_quantize_f32")
+    return res, delta, zero_float, signed_flag
+
+
+def int_minmax_quantize(x, n_bits=8, symmetric=False, eps=1e-8, delta=None, zero_float=None, signed_flag=None,
+                        out=None):
+    """Per-channel current_minmax + set_quant_range + quantize of a uniform quantizer (weights): row min / max, then
+    range and quantize in one more launch.  Returns (y, row_min, row_max, delta, zero_float, signed_flag)."""
+    _require(x, "x")
+    x = x.contiguous()
+    C, inner = _rows(x, True)
+    if C == 0 or inner == 0:
+        raise Fp8qError("min/max of an empty tensor")
+    y = _out(out, x)
+    mn, mx = torch.empty((2, C), dtype=torch.float32, device=x.device).unbind(0)
+    n, delta, zero_float, signed_flag = _int_range_out(mn, delta, zero_float, signed_flag, symmetric)
+    pd, pz, ps = _int_ptrs(x, delta, zero_float, signed_flag, symmetric, n)
+    L = lib()
+    nbytes = _mm_ws_bytes.get((C, inner))
+    if nbytes is None:
+        nbytes = _mm_ws_bytes[(C, inner)] = L.fp8q_minmax_workspace_bytes(C, inner)
+    ws = _workspace(x.device, nbytes, zeroed=True)
+    with _on_device(x):
+        rc = L.fp8q_int_minmax_quantize_f32(x.data_ptr(), y.data_ptr(), C, inner, mn.data_ptr(), mx.data_ptr(), pd,
+                                            pz, ps, int(n_bits), int(bool(symmetric)), float(eps), ws.data_ptr(),
+                                            ws.numel(), _stream(x))
+    check(rc, "fp8q_int_minmax_quantize_f32")
+    return y, mn, mx, delta, zero_float, signed_flag
+
+
 def copy(x, out=None):
     """float4 copy kernel with K1's launch shape (HBM ceiling yardstick)."""
     _require(x, "x")

@@ -235,7 +235,8 @@ class QuantizationHijacker(QuantizedModule):
         mgr = self.weight_quantizer
         q = getattr(mgr, "quantizer", None)
         if (os.environ.get("FP8Q_CACHE_WEIGHTS", "1") == "0" or getattr(mgr, "state", None) != Qstates.fix_ranges
-                or not hasattr(q, "maxval") or weight.requires_grad and torch.is_grad_enabled()):
+                or not (hasattr(q, "maxval") or isinstance(q, AsymmetricUniformQuantizer))
+                or weight.requires_grad and torch.is_grad_enabled()):
             return self.quantize_weights(weight)
         key = self._weight_cache_key(weight, q)
         if getattr(self, "_wq_key", None) != key:
@@ -250,6 +251,11 @@ class QuantizationHijacker(QuantizedModule):
         range tensor's in-place version -- never a raw address alone, which a freed-and-reallocated tensor can
         repeat.  Weights: address + autograd version, which in-place ops (optimizer steps, mul_) bump; edits
         through `.data` do NOT -- call invalidate_weight_cache() after those (or run with FP8Q_CACHE_WEIGHTS=0)."""
+        if isinstance(q, AsymmetricUniformQuantizer):   # INT: delta / zero_float / signed, each by address and version
+            rng = tuple((t.data_ptr(), t._version) if isinstance(t, torch.Tensor) else None
+                        for t in (q._delta, q._zero_float, getattr(q, "_signed", None)))
+            return (weight.data_ptr(), weight._version, tuple(weight.shape), getattr(q, "_range_epoch", None), rng,
+                    q.n_bits, q.scale_domain, q.eps)
         mv = q.maxval
         return (weight.data_ptr(), weight._version, tuple(weight.shape), getattr(q, "_range_epoch", None),
                 mv.data_ptr(), mv._version, float(q.mantissa_bits), q.sign_bits, q.n_bits)

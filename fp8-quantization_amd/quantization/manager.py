@@ -8,6 +8,9 @@ it (:114-122) -- but picks the cheapest kernel sequence for it:
   estimate, per-channel current_minmax, set_maxval  -> 1 launch  (fp8q_minmax_quantize_f32)
   estimate, any min/max estimator                    -> 2-3 launches (minmax [+final], quantize)
   fixed ranges                                       -> 1 launch  (fp8q_quantize_f32)
+  INT (uniform) quantizer, min/max estimator         -> the estimator's launch + 1 (fp8q_int_range_quantize_f32);
+                           per-channel current_minmax -> 2 launches (fp8q_int_minmax_quantize_f32)
+  INT, fixed ranges                                  -> 1 launch  (fp8q_int_quantize_f32)
   anything else (custom estimator / quantizer)       -> the generic protocol calls
 """
 from enum import auto
@@ -37,6 +40,7 @@ class Qstates(BaseEnumOptions):
 
 
 _MINMAX = (CurrentMinMaxEstimator, AllMinMaxEstimator, RunningMinMaxEstimator)
+_UNIFORM = (SymmetricUniformQuantizer, AsymmetricUniformQuantizer)
 
 
 class QuantizationManager(nn.Module):
@@ -99,6 +103,15 @@ class QuantizationManager(nn.Module):
         q, est = self.quantizer, self.range_estimator
         if not self._estimating():
             return q(x)
+        if type(q) in _UNIFORM and type(est) in _MINMAX and not getattr(est, "percentile", None):
+            if type(est) is CurrentMinMaxEstimator and self.per_channel:
+                r = q._minmax_forward(x)                 # current_minmax + range + quantize: two launches
+                if r is not None:
+                    y, mn, mx = r
+                    est.current_xmin, est.current_xmax, est.last_maxval = mn, mx, None
+                    return y
+            xmin, xmax = est(x)                          # the estimator as ever (folds, data-parallel exchange) ...
+            return q._range_forward(x, xmin, xmax)       # ... then range + quantize in one launch
         fast = (type(q) is FPQuantizer and type(est) in _MINMAX and not q.allow_unsigned
                 and not getattr(est, "percentile", None) and x.is_cuda
                 and not (x.requires_grad and torch.is_grad_enabled()))   # weights are Parameters: fine under no_grad

@@ -1,16 +1,121 @@
-"""Uniform (INT) fake-quantizers -- the comparison baseline of compute_quant_error.py (config 1).
+"""Uniform (INT) fake-quantizers -- the INT baseline of the FP8 study (compute_quant_error.py config 1, --qmethod-act).
 
-Reference: quantization/quantizers/uniform_quantizers.py:13-331.  These are NOT part of the FP8 hot
-path: they are a handful of elementwise torch ops on whatever device the
-tensor lives on, kept so that the `symmetric_uniform` / `asymmetric_uniform` registry entries and
-the INT8 row of the SQNR study work.
+Reference: quantization/quantizers/uniform_quantizers.py:13-331.  On CUDA fp32 tensors in the linear scale domain,
+without autograd, `forward` and `set_quant_range` run the HIP kernels of csrc/fp8q_int.hip (one launch each, the
+symmetric sign read from device memory: no host round trip); everything else -- CPU, other dtypes, the log domain,
+range learning, a custom discretizer -- is the reference's torch op chain.  FP8Q_INT_KERNELS=0 forces that chain.
 """
+import os
+
 import torch
 
+from fp8q import ops as _ops
 from .fp8 import QuantizerBase, QuantizerNotInitializedError, round_ste_func
 
 
+def _int_kernels_enabled():
+    return os.environ.get("FP8Q_INT_KERNELS", "1") != "0"
+
+
 class AsymmetricUniformQuantizer(QuantizerBase):
+    _RANGE_BUFFERS = ("_delta", "_zero_float", "_signed")
+
+    def __setattr__(self, name, value):
+        # every assignment of a range buffer starts a new range epoch (the layers' quantized-weight cache keys on it,
+        # as on FPQuantizer's); the kernels' in-place range writes bump it themselves
+        if name in AsymmetricUniformQuantizer._RANGE_BUFFERS:
+            object.__setattr__(self, "_range_epoch", getattr(self, "_range_epoch", 0) + 1)
+        super().__setattr__(name, value)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        object.__setattr__(self, "_range_epoch", getattr(self, "_range_epoch", 0) + 1)   # copies in place
+        super()._load_from_state_dict(*args, **kwargs)
+
+    def _bump_range_epoch(self):
+        object.__setattr__(self, "_range_epoch", getattr(self, "_range_epoch", 0) + 1)
+
+    def _kernel_common(self, dev):
+        """The quantizer side of the kernel path's conditions (see the module docstring)."""
+        n = self.n_bits
+        return (self.scale_domain == "linear" and self.discretizer is round_ste_func and dev.type == "cuda"
+                and isinstance(n, int) and 2 <= n <= 16 and _int_kernels_enabled())
+
+    def _kernel_buffers_ok(self, dev):
+        """Fixed ranges on the kernel path: plain fp32 buffers (not range Parameters) on `dev`."""
+        d = self._delta
+        if not (isinstance(d, torch.Tensor) and not isinstance(d, torch.nn.Parameter) and d.dtype == torch.float32
+                and d.device == dev and not d.requires_grad):
+            return False
+        if self.symmetric:
+            sg = self._signed
+            return isinstance(sg, torch.Tensor) and sg.dtype == torch.bool and sg.device == dev and sg.numel() == 1
+        z = self._zero_float
+        return (isinstance(z, torch.Tensor) and not isinstance(z, torch.nn.Parameter) and z.dtype == torch.float32
+                and z.device == dev and z.numel() == d.numel() and not z.requires_grad)
+
+    def _kernel_x_ok(self, x, n):
+        if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_cuda
+                and not (x.requires_grad and torch.is_grad_enabled())):
+            return False
+        return n == 1 or (self.per_channel and x.dim() > 0 and x.shape[0] == n)
+
+    def _range_out(self, x_min):
+        """The range buffers the kernels write: the current ones in place when they fit, fresh ones otherwise."""
+        def fits(t, shape, dtype):
+            return (isinstance(t, torch.Tensor) and not isinstance(t, torch.nn.Parameter) and t.shape == shape
+                    and t.dtype == dtype and t.device == x_min.device and t.is_contiguous())
+        d = self._delta if fits(self._delta, x_min.shape, torch.float32) else None
+        if self.symmetric:
+            return d, None, self._signed if fits(self._signed, torch.Size(()), torch.bool) else None
+        return d, self._zero_float if fits(self._zero_float, x_min.shape, torch.float32) else None, None
+
+    def _range_kernel_ok(self, x_min, x_max):
+        if not (isinstance(x_min, torch.Tensor) and isinstance(x_max, torch.Tensor)):
+            return False
+        if not self._kernel_common(x_min.device):
+            return False
+        if (x_min.dtype != torch.float32 or x_max.dtype != torch.float32 or x_max.device != x_min.device
+                or x_min.shape != x_max.shape or x_min.numel() == 0):
+            return False
+        if torch.is_grad_enabled() and (x_min.requires_grad or x_max.requires_grad):
+            return False
+        if isinstance(self._delta, torch.nn.Parameter) or isinstance(self._zero_float, torch.nn.Parameter):
+            return False
+        return self.per_channel or x_min.numel() == 1      # per tensor with a vector: the eager path raises
+
+    def _store_range(self, delta, zero_float, signed_flag):
+        self._delta = delta
+        if self.symmetric:
+            self._signed = signed_flag
+        else:
+            self._zero_float = zero_float
+        self._bump_range_epoch()
+
+    def _range_forward(self, x, x_min, x_max):
+        """set_quant_range(x_min, x_max) then forward(x); ONE launch on the kernel path."""
+        if self._range_kernel_ok(x_min, x_max) and self._kernel_x_ok(x, x_min.numel()) and x.device == x_min.device:
+            self.x_min_fp32, self.x_max_fp32 = x_min, x_max
+            y, d, z, sg = _ops.int_range_quantize(x, x_min, x_max, self.n_bits, self.symmetric, self.eps,
+                                                  *self._range_out(x_min))
+            self._store_range(d, z, sg)
+            return y
+        self.set_quant_range(x_min, x_max)
+        return self(x)
+
+    def _minmax_forward(self, x):
+        """Per-channel current_minmax + set_quant_range + forward (weights), or None off the kernel path.
+        Returns (y, row_min, row_max)."""
+        if not (self.per_channel and x.dim() > 0 and x.numel() > 0 and self._kernel_common(x.device)
+                and self._kernel_x_ok(x, x.shape[0]) and not isinstance(self._delta, torch.nn.Parameter)
+                and not isinstance(self._zero_float, torch.nn.Parameter)):
+            return None
+        like = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        y, mn, mx, d, z, sg = _ops.int_minmax_quantize(x, self.n_bits, self.symmetric, self.eps,
+                                                       *self._range_out(like))
+        self.x_min_fp32, self.x_max_fp32 = mn, mx
+        self._store_range(d, z, sg)
+        return y, mn, mx
+
     def __init__(self, n_bits, scale_domain="linear", discretizer=round_ste_func, discretizer_args=tuple(),
                  grad_scaling=False, eps=1e-8, **kwargs):
         super().__init__(n_bits=n_bits, **kwargs)
@@ -83,6 +188,11 @@ class AsymmetricUniformQuantizer(QuantizerBase):
         return torch.clamp(self.discretizer(x_float / scale) + zp, self.int_min, self.int_max)
 
     def forward(self, x_float, *args, **kwargs):
+        d = self._delta
+        if (d is not None and self._kernel_common(x_float.device) and self._kernel_buffers_ok(x_float.device)
+                and self._kernel_x_ok(x_float, d.numel())):
+            return _ops.int_quantize(x_float, d, None if self.symmetric else self._zero_float,
+                                     self._signed if self.symmetric else None, self.n_bits, self.symmetric, self.eps)
         scale, zp = self._params_like(x_float)
         return scale * (self.to_integer_forward(x_float) - zp)
 
@@ -97,6 +207,10 @@ class AsymmetricUniformQuantizer(QuantizerBase):
 
     def set_quant_range(self, x_min, x_max):
         self.x_min_fp32, self.x_max_fp32 = x_min, x_max
+        if self._range_kernel_ok(x_min, x_max):
+            d, z, sg = _ops.int_set_range(x_min, x_max, self.n_bits, self.symmetric, self.eps, *self._range_out(x_min))
+            self._store_range(d, z, sg)
+            return
         x_min, x_max = self._tensorize_min_max(x_min, x_max)
         delta = (x_max - x_min) / self.int_max
         self._zero_float = (-x_min / delta).detach()
@@ -148,6 +262,10 @@ class SymmetricUniformQuantizer(AsymmetricUniformQuantizer):
 
     def set_quant_range(self, x_min, x_max):
         self.x_min_fp32, self.x_max_fp32 = x_min, x_max
+        if self._range_kernel_ok(x_min, x_max):
+            d, _, sg = _ops.int_set_range(x_min, x_max, self.n_bits, True, self.eps, *self._range_out(x_min))
+            self._store_range(d, None, sg)
+            return
         x_min, x_max = self._tensorize_min_max(x_min, x_max)
         self._signed = x_min.min() < 0
         delta = torch.max(x_min.abs(), x_max) / self.int_max

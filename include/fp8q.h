@@ -450,6 +450,40 @@ void fp8q_multi_plan_destroy(fp8q_multi_plan *plan);
  * bench.py reports next to the 8 TB/s spec figure. */
 int fp8q_copy_f32(const float *x, float *y, int64_t n, fp8q_stream_t stream);
 
+/*
+ * Uniform (INT) fake-quantization (csrc/fp8q_int.hip): the reference's AsymmetricUniformQuantizer /
+ * SymmetricUniformQuantizer (uniform_quantizers.py) in the linear scale domain, bit for bit its fp32 op chain:
+ *   y = scale * (clamp(rint(x / scale) + zp, int_min, int_max) - zp),  scale = max(delta, eps),
+ *   zp = clamp(rint(zero_float), int_min, int_max) (asymmetric) or 0 (symmetric).
+ * Asymmetric: [int_min, int_max] = [0, 2^n - 1].  Symmetric: [-2^(n-1), 2^(n-1) - 1] when the device byte
+ * signed_flag[0] is non-zero, [0, 2^n - 1] otherwise -- read by the kernels, never by the host.
+ * x, y [C, inner] fp32; delta / zero_float / x_min / x_max have n_delta (n_range) elements, 1 (per tensor) or C (per
+ * channel, dim 0).  zero_float is unused (may be NULL) when symmetric; signed_flag is unused (may be NULL) when not.
+ * n_bits in [2, 16] (FP8Q_EUNSUPPORTED otherwise); FP8Q_EINVAL for null pointers, empty shapes, n_delta not in {1, C}.
+ * HBM traffic: 8 B / element.  Enqueue-only.
+ *
+ *   int_quantize       fixed ranges: one launch.
+ *   int_set_range      (x_min, x_max) [n] -> delta, zero_float (asymmetric), signed_flag (symmetric: the sign of the
+ *                      whole vector, NaN -> unsigned): x_min' = min(x_min, 0), x_max' = max(x_max, eps),
+ *                      delta = (x_max' - x_min') / int_max, zero_float = -x_min' / delta, or, symmetric,
+ *                      delta = max(|x_min'|, x_max') / int_max.  One launch (two for more than 2048 symmetric channels).
+ *   int_range_quantize int_set_range and int_quantize in ONE launch (two for more than 2048 symmetric channels).
+ *   int_minmax_quantize per-channel current_minmax: row_min / row_max [C] (fp8q_minmax_f32, FOLD_CURRENT; ws / ws_bytes
+ *                      as there), then int_range_quantize on them.  Two launches (three beyond 2048 symmetric channels).
+ */
+int fp8q_int_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, const float *delta,
+                          const float *zero_float, int64_t n_delta, const unsigned char *signed_flag, int n_bits,
+                          int symmetric, float eps, fp8q_stream_t stream);
+int fp8q_int_set_range_f32(const float *x_min, const float *x_max, int64_t n, float *delta, float *zero_float,
+                           unsigned char *signed_flag, int n_bits, int symmetric, float eps, fp8q_stream_t stream);
+int fp8q_int_range_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, const float *x_min,
+                                const float *x_max, int64_t n_range, float *delta, float *zero_float,
+                                unsigned char *signed_flag, int n_bits, int symmetric, float eps,
+                                fp8q_stream_t stream);
+int fp8q_int_minmax_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, float *row_min, float *row_max,
+                                 float *delta, float *zero_float, unsigned char *signed_flag, int n_bits, int symmetric,
+                                 float eps, void *ws, size_t ws_bytes, fp8q_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
