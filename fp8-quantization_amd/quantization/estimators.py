@@ -214,6 +214,14 @@ class FP_MSE_Estimator(RangeEstimatorBase):
         self._mbit_list = None
         self.__dict__["_cal"] = None
 
+    def __getstate__(self):
+        # the native calibration state holds ctypes pointers into this estimator's device block: it is neither pickled nor
+        # deep-copied (copy.deepcopy / torch.save of a calibrated model); a copy binds its own on its next batch, adopting
+        # the copied `search_grid` / `mses`
+        state = super().__getstate__()
+        state["_cal"] = None
+        return state
+
     # ---- the one-call calibration step (fp8q_mse_calibrate_f32) ---------------------------------------------------------
     def one_call_ok(self, x):
         """True when estimate + set_quant_range + quantize of this batch can run as ONE library call with the same

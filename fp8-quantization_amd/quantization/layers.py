@@ -185,6 +185,14 @@ class QuantizationHijacker(QuantizedModule):
         out = self.run_forward(x, weight, bias, offsets=offsets)
         return self._finish(out)
 
+    def __getstate__(self):
+        # what calibrate_weights_ahead() leaves on a layer for the forward in progress (a stream, an event, the result of a
+        # launch still running on the side stream) belongs to that forward: a deep copy or a pickle does not take it along
+        state = super().__getstate__()
+        state.pop("_ahead_ctl", None)
+        state.pop("_wq_ahead", None)
+        return state
+
     def _act_code(self):
         """0 none / 1 ReLU / 2 ReLU6 for the fused epilogue kernel, None for any other activation."""
         a = self.activation_function

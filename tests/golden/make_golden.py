@@ -30,6 +30,10 @@ Fixture files:
   g12_allow_unsigned.npz allow_unsigned over three batches through QuantizationManager (min/max estimators, MSE with a fixed width):
                      outputs, maxval and sign_bits after every batch (fp8_quantizer.py:216-225 is sticky)
   g1c_quantize_f64.npz quantize_to_fp8_ste_MM on FLOAT64 inputs (ATen type promotion: bias float32, the rest float64)
+  g13_r18.npz, g13_mbv2.npz, g13_mbv2m.npz (+ *_sub.npz: the raw run_forward outputs)
+                     every QuantizationManager call of one calibration batch (2x3x32x32) of QuantizedResNet (config 3) and
+                     QuantizedMobileNetV2 (config 4, without / with mse_include_mantissa_bits): inputs, outputs, estimator
+                     state, MSE grids and tables, and the tensors the teacher-forced tests substitute (make_g13)
   (g5 also holds LineSearchEstimator.loss_array -- 1001 float64 sums per distribution and format -- and the chosen index)
 """
 import os
@@ -646,9 +650,8 @@ def _qparams(M, w_est, a_est, incl=False):
                                 learn_mantissa_bits=False, mse_include_mantissa_bits=incl, allow_unsigned=False))
 
 
-def make_g8():
-    """BASELINE config 3 (reduced): reference QuantizedResNet on a seeded ResNet-18, 64x64 inputs,
-    E5M2, per-channel current_minmax weights, per-tensor allminmax activations."""
+def _install_torchvision_stub():
+    """torchvision (absent here) -> this repo's fp32 ResNet definitions, for the reference's models/resnet_quantized.py"""
     own = _load_own("amd_resnet", "models/resnet.py")
     tv = types.ModuleType("torchvision")
     tvm = types.ModuleType("torchvision.models")
@@ -659,6 +662,13 @@ def make_g8():
     tvm.resnet = tvr
     tv.models = tvm
     sys.modules.update({"torchvision": tv, "torchvision.models": tvm, "torchvision.models.resnet": tvr})
+    return own
+
+
+def make_g8():
+    """BASELINE config 3 (reduced): reference QuantizedResNet on a seeded ResNet-18, 64x64 inputs,
+    E5M2, per-channel current_minmax weights, per-tensor allminmax activations."""
+    own = _install_torchvision_stub()
     from models.resnet_quantized import QuantizedResNet      # the REFERENCE's class
     torch.manual_seed(0)
     fp = warm_bn(own.resnet18())
@@ -817,6 +827,237 @@ def make_g3b():
         out["q"] = q(x).numpy()                       # all-zero rows: maxval 0 -> NaN rows (a reproduced quirk)
     np.savez_compressed(os.path.join(OUT, "g3b_signed_zero.npz"), **out)
     print("g3b ok")
+
+
+# ---- G13: teacher-forced per-quantizer record of a whole-model calibration ---------------------------------------
+G13_CONFIGS = (("g13_r18", "r18", 2, "current_minmax", "allminmax", False),
+               ("g13_mbv2", "mbv2", 3, "MSE", "MSE", False),
+               ("g13_mbv2m", "mbv2", 3, "MSE", "MSE", True))
+G13_NEAR_TIE = 1e-5
+
+
+def _sha(a):
+    import hashlib
+    return np.frombuffer(hashlib.sha256(np.ascontiguousarray(a).tobytes()).digest(), np.uint8)
+
+
+def _g13_diff(out, key, y_ref, base):
+    """g1b's scheme: y_ref as the SHA-256 of its bytes plus the sparse ULP difference to `base` (a recomputation by the C
+    oracle); differences of more than 100 ULP (grid-step flips) are stored as values.  Returns the number of differences."""
+    y_ref = np.ascontiguousarray(y_ref, np.float32).reshape(-1)
+    base = np.ascontiguousarray(base, np.float32).reshape(-1)
+    assert y_ref.shape == base.shape and not np.isnan(y_ref).any() and not np.isnan(base).any(), key
+    d = ulp_key(y_ref) - ulp_key(base)
+    idx = np.flatnonzero(y_ref.view(np.int32) != base.view(np.int32))
+    small = (np.abs(d[idx]) <= 100) & (d[idx] != 0)         # (-0.0 vs +0.0: no ULP apart, stored as a value)
+    out[f"{key}_sha256"] = _sha(y_ref)
+    out[f"{key}_idx_delta"] = np.diff(idx[small], prepend=0).astype(np.uint32)
+    out[f"{key}_ulp_delta"] = d[idx[small]].astype(np.int8)
+    out[f"{key}_big_idx"] = idx[~small].astype(np.int64)
+    out[f"{key}_big_val"] = y_ref[idx[~small]]
+    return int(idx.size)
+
+
+def _g13_pack(out):
+    """the per-call arrays c<k>_<what> concatenated per <what> (a zip entry per small array would double the file):
+    pack_<what> holds the flat data, pack_<what>_index the (call, offset, shape) of every piece as JSON"""
+    import json
+    import re
+    groups, rest = {}, {}
+    for key, a in out.items():
+        m = re.fullmatch(r"c(\d+)_(.+)", key)
+        if m is None:
+            rest[key] = a
+        else:
+            groups.setdefault(m.group(2), []).append((int(m.group(1)), np.asarray(a)))
+    for what, items in groups.items():
+        index, off = [], 0
+        for k, a in items:
+            index.append([k, off, list(a.shape)])
+            off += a.size
+        rest[f"pack_{what}"] = np.concatenate([a.reshape(-1) for _, a in items])
+        rest[f"pack_{what}_index"] = np.array(json.dumps(index))
+    return rest
+
+
+def _g13_net(model, size):
+    """the fp32 networks of g8 / g9 (seed 0, warm_bn at 64x64), MobileNetV2 rebuilt for `size` (its AvgPool2d is sized
+    at construction) from the warmed state dict"""
+    if model == "r18":
+        torch.manual_seed(0)
+        return warm_bn(sys.modules["torchvision.models"].resnet18())     # the classes the reference's model maps
+    own = _load_own("amd_mbv2", "models/mobilenet_v2.py")
+    from models.mobilenet_v2 import MobileNetV2 as RefMobileNetV2
+    torch.manual_seed(0)
+    warm = warm_bn(own.MobileNetV2(input_size=64))
+    ref_fp = RefMobileNetV2(input_size=size).eval()
+    ref_fp.load_state_dict(warm.state_dict())
+    return ref_fp
+
+
+def make_g13():
+    """Every quantizer call of one reference calibration batch (2x3x32x32, seed 13) of ResNet-18 (config 3) and
+    MobileNetV2 (config 4, without and with the mantissa-width search), in calibration order, so that the tests can feed
+    each of this repo's quantizers the reference's own input (tests/test_teacher_forced.py).  Raw fp32: only the tensors
+    the tests substitute -- every hijacked layer's run_forward output (before BN / activation) and both addends of every
+    residual add.  Everything else is a SHA-256 plus a sparse ULP diff against the C oracle: a quantizer input against
+    oracle.c_affine_act(pre, bn, residual, act), an output against oracle.c_quantize(input, maxval, mbits).  MSE calls:
+    per-tensor the full grid and table; per-channel the argmin and best-width index per channel, the grid's SHA-256 and
+    the table rows of near-tie channels (best and second-best entries within 1e-5 relative).  The BN running
+    statistics and the 1 / sqrt(var + eps) the oracle recomputation used are stored too: warm_bn's CPU reductions (and
+    torch's vectorised CPU arithmetic) need not agree bit for bit on another machine.  The run_forward outputs go to
+    a companion file <name>_sub.npz, so that no file reaches 1 MiB."""
+    import json
+    sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+    import oracle
+    _install_torchvision_stub()
+    from quantization.hijacker import QuantizationHijacker
+    from quantization.quantized_folded_bn import BNFusedHijacker
+    from models.resnet_quantized import QuantizedResNet, QuantizedBlock
+    from models.mobilenet_v2_quantized import QuantizedMobileNetV2, QuantizedInvertedResidual
+    from quantization.range_estimators import FP_MSE_Estimator
+    size = 32
+    for fname, model, M, w_est, a_est, incl in G13_CONFIGS:
+        fp = _g13_net(model, size)
+        cls = QuantizedResNet if model == "r18" else QuantizedMobileNetV2
+        q = cls(fp, input_size=(1, 3, size, size), **_qparams(M, w_est, a_est, incl)).eval()
+        torch.manual_seed(13)
+        calib = torch.randn(2, 3, size, size)
+        names, seen = {}, set()
+        for n, m in q.named_modules():
+            if isinstance(m, QuantizationManager) and id(m) not in seen:
+                seen.add(id(m))
+                names[id(m)] = n
+        owners = {}                        # activation manager -> (owner name, owner module)
+        for n, m in q.named_modules():
+            aq = getattr(m, "activation_quantizer", None)
+            if isinstance(aq, QuantizationManager) and id(aq) not in owners and isinstance(
+                    m, (QuantizationHijacker, QuantizedBlock, QuantizedInvertedResidual)):
+                owners[id(aq)] = (n, m)
+        pre = {}                           # owner name -> run_forward output or (branch, skip) addends
+        out, sub, calls = {}, {}, []
+        n_raw = [0]
+        stats = dict(in_diff=0, out_diff=0, w_diff=0, near_tie_ch=0, elems=0)
+
+        def raw(key, t, dst=sub):
+            dst[key] = t.detach().numpy().astype(np.float32).copy()
+            n_raw[0] += dst[key].size
+
+        hooks = []
+        for n, m in q.named_modules():
+            if isinstance(m, QuantizationHijacker):
+                def rf(x, weight, bias, offsets=None, _orig=m.run_forward, _n=n):
+                    y = _orig(x, weight, bias, offsets=offsets)
+                    pre[_n] = y.detach().clone()
+                    raw(f"run_{_n}", y)
+                    return y
+                m.run_forward = rf
+            if isinstance(m, (QuantizedBlock, QuantizedInvertedResidual)) and getattr(m, "use_res_connect", True):
+                def blk_in(mod, args, _n=n):
+                    pre[_n + ".in"] = args[0].detach().clone()
+                hooks.append(m.register_forward_pre_hook(blk_in))
+                main = m.features if isinstance(m, QuantizedBlock) else m.conv
+
+                def main_out(mod, args, y, _n=n):
+                    pre[_n + ".branch"] = y.detach().clone()          # (ResNet adds the skip into it in place)
+                hooks.append(main.register_forward_hook(main_out))
+                if getattr(m, "downsample", None) is not None:
+                    def ds_out(mod, args, y, _n=n):
+                        pre[_n + ".skip"] = y.detach().clone()
+                    hooks.append(m.downsample.register_forward_hook(ds_out))
+
+        def mgr_hook(mgr, args, y):
+            n = names[id(mgr)]
+            k = len(calls)
+            x = args[0].detach()
+            est, qz = mgr.range_estimator, mgr.quantizer
+            weight = n.endswith("weight_quantizer")
+            mv = qz.maxval.detach().numpy().astype(np.float32).reshape(-1).copy()
+            mb = float(qz.mantissa_bits)
+            info = dict(k=k, name=n, kind="weight" if weight else "act", est=type(est).__name__,
+                        per_channel=bool(mgr.per_channel), shape=list(x.shape), mbits=mb, sign_bits=int(qz.sign_bits))
+            stats["elems"] += x.numel()
+            if weight:
+                out[f"c{k}_x_sha256"] = _sha(x.numpy())
+            else:
+                on, om = owners[id(mgr)]
+                info["owner"] = on
+                if isinstance(om, QuantizationHijacker):
+                    a = om.activation_function
+                    act = 0 if a is None else {nn.ReLU: 1, nn.ReLU6: 2}.get(type(a), -1)
+                    bn = None
+                    if isinstance(om, BNFusedHijacker):
+                        bn = tuple(t.detach().numpy() for t in (om.running_mean, 1 / torch.sqrt(om.running_var + om.epsilon),
+                                                               om.gamma, om.beta))
+                    src, res = pre.pop(on), None
+                    info.update(bn=bn is not None, act=act, residual=False)
+                else:
+                    branch = pre.pop(on + ".branch")
+                    skip = pre.pop(on + ".in")
+                    skip = pre.pop(on + ".skip", skip)          # the downsample's output when there is one
+                    raw(f"res_{on}_branch", branch, out)
+                    raw(f"res_{on}_skip", skip, out)
+                    src, res, bn = branch, skip, None
+                    act = 1 if isinstance(om, QuantizedBlock) else 0
+                    info.update(bn=False, act=act, residual=True)
+                assert act >= 0, n
+                base = oracle.c_affine_act(src.numpy(), bn, None if res is None else res.numpy(), act)
+                stats["in_diff"] += _g13_diff(out, f"c{k}_x", x.numpy(), base)
+            yb = oracle.c_quantize(x.numpy(), mv, mb, 8, int(qz.sign_bits))
+            nd = _g13_diff(out, f"c{k}_y", y.detach().numpy(), yb)
+            stats["w_diff" if weight else "out_diff"] += nd
+            out[f"c{k}_maxval"] = mv
+            if isinstance(est, FP_MSE_Estimator):
+                grid = est.search_grid.detach().numpy().astype(np.float32)
+                mses = est.mses.detach().numpy().astype(np.float32)
+                info["n_m"] = int(mses.shape[0])
+                if not mgr.per_channel:
+                    out[f"c{k}_grid"], out[f"c{k}_mses"] = grid.copy(), mses.copy()
+                else:
+                    out[f"c{k}_grid_sha256"] = _sha(grid)
+                    best_m = mses.min(1).argmin(0)
+                    vote = int(torch.mode(torch.from_numpy(best_m)).values)
+                    out[f"c{k}_best_m"] = best_m.astype(np.uint8)
+                    out[f"c{k}_argmin"] = mses[vote].argmin(0).astype(np.uint8)
+                    flat = np.sort(mses.reshape(-1, mses.shape[2]), axis=0)
+                    tie = np.flatnonzero(flat[1] <= flat[0] * (1 + G13_NEAR_TIE))
+                    out[f"c{k}_tie_ch"] = tie.astype(np.int32)
+                    out[f"c{k}_tie_rows"] = np.ascontiguousarray(mses[:, :, tie].transpose(2, 0, 1))
+                    stats["near_tie_ch"] += tie.size
+            else:
+                out[f"c{k}_xmin"] = est.current_xmin.detach().numpy().astype(np.float32).reshape(-1).copy()
+                out[f"c{k}_xmax"] = est.current_xmax.detach().numpy().astype(np.float32).reshape(-1).copy()
+            calls.append(info)
+
+        for m in q.modules():
+            if isinstance(m, QuantizationManager):
+                hooks.append(m.register_forward_hook(mgr_hook))
+        with torch.no_grad():
+            q.set_quant_state(True, True)
+            q(calib)
+        for h in hooks:
+            h.remove()
+        assert not pre, sorted(pre)                  # every substitution tensor belongs to a recorded call
+        for n, m in q.named_modules():     # warm_bn's statistics: a CPU reduction, not reproducible bit for bit elsewhere
+            if isinstance(m, BNFusedHijacker):
+                out[f"bn_{n}"] = np.stack([m.running_mean.numpy(), m.running_var.numpy(),
+                                           (1 / torch.sqrt(m.running_var + m.epsilon)).numpy()]).astype(np.float32)
+        out = _g13_pack(out)
+        out["calls"] = np.array(json.dumps(calls))
+        out["managers"] = np.array(list(names.values()))
+        out["calib"] = calib.numpy()
+        path, spath = os.path.join(OUT, f"{fname}.npz"), os.path.join(OUT, f"{fname}_sub.npz")
+        np.savez_compressed(path, **out)
+        np.savez_compressed(spath, **sub)
+        sizes = [os.path.getsize(path), os.path.getsize(spath)]
+        assert max(sizes) < 1 << 20, sizes           # (no committed file reaches 1 MiB)
+        print(f"{fname}: {len(calls)} calls of {len(names)} managers; {n_raw[0]} raw floats; quantizer inputs differ from "
+              f"c_affine_act in {stats['in_diff']}, outputs from c_quantize in {stats['out_diff']} (weights "
+              f"{stats['w_diff']}) of {stats['elems']} elements; {stats['near_tie_ch']} near-tie channels; "
+              f"{sizes[0] / 1e6:.3f} + {sizes[1] / 1e6:.3f} MB")
+    total = sum(os.path.getsize(os.path.join(OUT, f"{c[0]}{s}.npz")) for c in G13_CONFIGS for s in ("", "_sub"))
+    assert total <= 4e6, total
+    print(f"g13 total {total / 1e6:.3f} MB")
 
 
 if __name__ == "__main__":
