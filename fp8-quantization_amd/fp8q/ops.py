@@ -115,10 +115,67 @@ def _workspace(dev, nbytes, zeroed=False, kind=None, stream=None):
     return ws
 
 
-def quantize(x, maxval, mbits, n_bits=8, sign_bits=1, out=None):
+_HALF = (torch.float16, torch.bfloat16)
+_DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}      # FP8Q_DT_* (include/fp8q.h)
+
+
+def _half_out_dtype(x, out, out_dtype):
+    """result dtype of a half-lane call: out.dtype when `out` is given, else out_dtype, else float32 (the reference's
+    type promotion); only float32 and x.dtype exist"""
+    dt = out.dtype if isinstance(out, torch.Tensor) else (torch.float32 if out_dtype is None else out_dtype)
+    if dt != torch.float32 and dt != x.dtype:
+        raise Fp8qError(f"the output of a {x.dtype} input is float32 or {x.dtype}, not {dt}")
+    if out is not None and out_dtype is not None and out_dtype != dt:
+        raise Fp8qError(f"out is {dt} but out_dtype is {out_dtype}")
+    return dt
+
+
+def _check_out_dtype(x, out_dtype):
+    if out_dtype is not None and out_dtype != x.dtype:
+        raise Fp8qError(f"out_dtype: a {x.dtype} input gives a {x.dtype} result (float16 / bfloat16 inputs: float32 or their own)")
+
+
+def _quantize_h16(x, maxval, mbits, n_bits, sign_bits, out, out_dtype):
+    """K1 on float16 / bfloat16 (fp8q_quantize_h16): x widened exactly, the fp32 contract, the result stored as float32
+    or rounded once to x.dtype"""
+    if isinstance(mbits, torch.Tensor) or isinstance(sign_bits, torch.Tensor):
+        raise Fp8qError("a device-resident mantissa width / sign flag is float32-only: the half-precision lane takes "
+                        f"mbits and sign_bits as numbers (x is {x.dtype}; widen it with .float() for that route)")
+    dt = _half_out_dtype(x, out, out_dtype)      # (argument errors before the device check: they need no GPU to be told)
+    _require(x, "x", _HALF)
+    _require(maxval, "maxval", like=x)
+    maxval = maxval.contiguous().view(-1)
+    n_mv = maxval.numel()
+    flat = _dense_flat(x) if (n_mv == 1 and out is None) else None
+    if flat is not None:            # per tensor on a dense non-contiguous layout: the storage as it lies, x's strides kept
+        res = torch.empty_like(x, dtype=dt)
+        flat_out = _dense_flat(res) if res.stride() == x.stride() else None
+        if flat_out is not None:
+            _quantize_h16(flat, maxval, mbits, n_bits, sign_bits, flat_out, None)
+            return res
+    x = x.contiguous()
+    C, inner = _rows(x, n_mv != 1)
+    if n_mv != 1 and n_mv != C:
+        raise Fp8qError(f"maxval has {n_mv} elements, expected 1 or {C}")
+    y = _out(out, x, dtype=dt)
+    if x.numel() == 0:
+        return y
+    with _on_device(x):
+        rc = lib().fp8q_quantize_h16(x.data_ptr(), y.data_ptr(), _DT[x.dtype], _DT[dt], C, inner, maxval.data_ptr(), n_mv,
+                                     float(mbits), int(n_bits), int(sign_bits), _stream(x))
+    check(rc, "fp8q_quantize_h16")
+    return y
+
+
+def quantize(x, maxval, mbits, n_bits=8, sign_bits=1, out=None, out_dtype=None):
     """K1: FP8 quantize+dequantize (fp8_quantizer.py:91-133).  maxval: CUDA fp32 tensor [1] or [C]; x float32 or
-    float64; mbits: a number, or a 1-element CUDA float32 tensor (read by the kernel: no host round trip)."""
+    float64; mbits: a number, or a 1-element CUDA float32 tensor (read by the kernel: no host round trip).
+    x float16 / bfloat16: the result is float32 (what the reference's type promotion returns) unless `out` or
+    out_dtype=x.dtype asks for x's own dtype; mbits and sign_bits are numbers there."""
+    if isinstance(x, torch.Tensor) and x.dtype in _HALF:
+        return _quantize_h16(x, maxval, mbits, n_bits, sign_bits, out, out_dtype)
     _require(x, "x", (torch.float32, torch.float64))
+    _check_out_dtype(x, out_dtype)
     _require(maxval, "maxval", like=x)
     maxval = maxval.contiguous().view(-1)
     n_mv = maxval.numel()
@@ -440,9 +497,13 @@ def minmax(x, per_channel, cur_min=None, cur_max=None, mode=FOLD_CURRENT, moment
     cur_min/cur_max: running estimate tensors [C] (updated in place) or None on the first call.
     packed: optional [C, 4] buffer (new_packed) that receives {-min, max, nan flags} of the folded estimate for the
     range all-reduce of batch-sharded calibration (see ranges_unpack).
+    x float16 / bfloat16: fp8q_minmax_h16 (estimates float32); no packed= buffer there.
     Returns (cur_min, cur_max[, maxval]) as [C] tensors.
     """
-    _require(x, "x")
+    half = isinstance(x, torch.Tensor) and x.dtype in _HALF
+    if half and packed is not None:
+        raise Fp8qError(f"packed ranges (data-parallel calibration) are float32-only, x is {x.dtype}")
+    _require(x, "x", (torch.float32,) + _HALF)
     flat = None if per_channel else _dense_flat(x)      # per tensor: any dense layout, no copy
     x = flat if flat is not None else x.contiguous()
     C, inner = _rows(x, per_channel)
@@ -470,6 +531,13 @@ def minmax(x, per_channel, cur_min=None, cur_max=None, mode=FOLD_CURRENT, moment
     if nbytes is None:     # a pure function of the shape: one ctypes call per shape, not per launch
         nbytes = _mm_ws_bytes[(C, inner)] = L.fp8q_minmax_workspace_bytes(C, inner)
     ws = _workspace(x.device, nbytes, zeroed=True)
+    if half:
+        with _on_device(x):
+            rc = L.fp8q_minmax_h16(x.data_ptr(), _DT[x.dtype], C, inner, cur_min.data_ptr(), cur_max.data_ptr(),
+                                   mv.data_ptr() if mv is not None else None, int(mode), float(momentum),
+                                   int(first), ws.data_ptr(), ws.numel(), _stream(x))
+        check(rc, "fp8q_minmax_h16")
+        return (cur_min, cur_max, mv) if want_maxval else (cur_min, cur_max)
     with _on_device(x):
         if packed is None:
             rc = L.fp8q_minmax_f32(x.data_ptr(), C, inner, cur_min.data_ptr(), cur_max.data_ptr(),
@@ -489,11 +557,26 @@ def fused_max_inner():
     return int(lib().fp8q_fused_max_inner())
 
 
-def minmax_quantize(x, mbits, n_bits=8, sign_bits=1, out=None):
+def minmax_quantize(x, mbits, n_bits=8, sign_bits=1, out=None, out_dtype=None):
     """K2+K5+K1 fused per-channel weight quantization (current_minmax, set_maxval=True).
+    x float16 / bfloat16 (fp8q_minmax_quantize_h16): y is float32 unless `out` / out_dtype=x.dtype ask for x's dtype.
 
     Returns (y, row_min, row_max, maxval)."""
+    if isinstance(x, torch.Tensor) and x.dtype in _HALF:
+        dt = _half_out_dtype(x, out, out_dtype)
+        _require(x, "x", _HALF)
+        x = x.contiguous()
+        C, inner = _rows(x, True)
+        y = _out(out, x, dtype=dt)
+        mn, mx, mv = torch.empty((3, C), dtype=torch.float32, device=x.device).unbind(0)
+        with _on_device(x):
+            rc = lib().fp8q_minmax_quantize_h16(x.data_ptr(), y.data_ptr(), _DT[x.dtype], _DT[dt], C, inner, mn.data_ptr(),
+                                                mx.data_ptr(), mv.data_ptr(), float(mbits), int(n_bits), int(sign_bits),
+                                                _stream(x))
+        check(rc, "fp8q_minmax_quantize_h16")
+        return y, mn, mx, mv
     _require(x, "x")
+    _check_out_dtype(x, out_dtype)
     x = x.contiguous()
     C, inner = _rows(x, True)
     y = _out(out, x)

@@ -83,7 +83,9 @@ class RangeEstimatorBase(nn.Module):
             if self._fold_mode == _ops.FOLD_CURRENT:
                 cur_min = cur_max = None   # overwritten anyway; keeps buffers of old shapes out
         packed = self._packed(x.device)
-        if packed is None:
+        if packed is not None and x.dtype in (torch.float16, torch.bfloat16):
+            x = x.float()                            # the packed data-parallel min/max is float32-only
+        if packed is None:                           # (float16 / bfloat16 x: fp8q_minmax_h16, estimates float32)
             mn, mx, mv = _ops.minmax(x, self.per_channel, cur_min, cur_max, mode=self._fold_mode,
                                      momentum=self.momentum, want_maxval=True)
         else:

@@ -102,11 +102,32 @@ def _host_float(t):
     return float(t)
 
 
-def quantize_to_fp8_ste_MM(x_float, n_bits, maxval, num_mantissa_bits, sign_bits):
+_HALF = (torch.float16, torch.bfloat16)
+
+
+def quantize_to_fp8_ste_MM(x_float, n_bits, maxval, num_mantissa_bits, sign_bits, out_dtype=None):
     """Same call signature as fp8_quantizer.py:91-97.  maxval: tensor [1] or [C] on x's device.  num_mantissa_bits: a
     number / host tensor (passed to the kernel by value) or a 1-element tensor on x's GPU (read by the kernel).
-    sign_bits: 0 / 1, or a 1-element uint8 tensor on x's GPU (FPQuantizer's pending flag: read by the kernel)."""
+    sign_bits: 0 / 1, or a 1-element uint8 tensor on x's GPU (FPQuantizer's pending flag: read by the kernel).
+    x_float float16 / bfloat16: the result is float32, as the reference's type promotion gives (maxval and the width are
+    float32 tensors), from the half-precision kernels (fp8q_quantize_h16); out_dtype=x_float.dtype (not in the reference)
+    rounds it once to x's own dtype.  Under autograd, or with a width / sign still pending on the device, the input is
+    widened with .float() and takes the float32 route."""
     mb_grad = isinstance(num_mantissa_bits, torch.Tensor) and num_mantissa_bits.requires_grad and torch.is_grad_enabled()
+    if x_float.dtype in _HALF:
+        if out_dtype not in (None, torch.float32, x_float.dtype):
+            raise ValueError(f"out_dtype must be float32 or {x_float.dtype}, got {out_dtype}")
+        grad = torch.is_grad_enabled() and (x_float.requires_grad or mb_grad
+                                            or (isinstance(maxval, torch.Tensor) and maxval.requires_grad))
+        pending = (isinstance(num_mantissa_bits, torch.Tensor) and num_mantissa_bits.is_cuda) or isinstance(sign_bits, torch.Tensor)
+        if grad or pending or not x_float.is_cuda:
+            y = quantize_to_fp8_ste_MM(x_float.float(), n_bits, maxval, num_mantissa_bits, sign_bits)
+            return y if out_dtype in (None, torch.float32) else y.to(out_dtype)
+        if not isinstance(maxval, torch.Tensor):
+            maxval = torch.tensor([float(maxval)], dtype=torch.float32)
+        maxval = maxval.to(device=x_float.device, dtype=torch.float32).reshape(-1)
+        return _ops.quantize(x_float, maxval.detach(), _host_float(num_mantissa_bits), int(n_bits), int(sign_bits),
+                             out_dtype=out_dtype)
     on_device = (isinstance(num_mantissa_bits, torch.Tensor) and num_mantissa_bits.is_cuda and num_mantissa_bits.numel() == 1
                  and x_float.dtype == torch.float32 and not mb_grad
                  and not (torch.is_grad_enabled() and x_float.requires_grad))
@@ -188,7 +209,7 @@ class FPQuantizer(QuantizerBase):
 
     def __init__(self, *args, scale_domain=None, mantissa_bits=4, maxval=3, set_maxval=False,
                  learn_maxval=False, learn_mantissa_bits=False, mse_include_mantissa_bits=True,
-                 allow_unsigned=False, **kwargs):
+                 allow_unsigned=False, keep_dtype=False, **kwargs):
         super().__init__(*args, **kwargs)
         m = mantissa_bits
         self.ebits = self.n_bits - m - 1
@@ -202,6 +223,10 @@ class FPQuantizer(QuantizerBase):
         self.learning_mantissa_bits = learn_mantissa_bits
         self.mse_include_mantissa_bits = mse_include_mantissa_bits
         self.allow_unsigned = allow_unsigned
+        # float16 / bfloat16 inputs: False returns float32 (the reference's type promotion), True rounds the result once to
+        # the input's dtype so that a model held in half precision type-checks.  Not in the reference, not in the state dict;
+        # ignored for float32 / float64 inputs.
+        self.keep_dtype = keep_dtype
         self.sign_bits = 1
 
     _RANGE_ATTRS = ("maxval", "mantissa_bits", "sign_bits")
@@ -306,8 +331,15 @@ class FPQuantizer(QuantizerBase):
     def forward(self, x_float):
         if self.maxval.device != x_float.device:
             self.maxval = self.maxval.to(x_float.device)
+        if x_float.dtype in _HALF:
+            return quantize_to_fp8_ste_MM(x_float, self.n_bits, self.maxval, self._mantissa_bits_arg(),
+                                          self._sign_bits_arg(), out_dtype=self._half_out_dtype(x_float))
         return quantize_to_fp8_ste_MM(x_float, self.n_bits, self.maxval, self._mantissa_bits_arg(),
                                       self._sign_bits_arg())
+
+    def _half_out_dtype(self, x):
+        """dtype of the result for a float16 / bfloat16 input: its own with keep_dtype, else float32 (None)"""
+        return x.dtype if getattr(self, "keep_dtype", False) else None
 
     # NB: plain methods, as in the reference (:207-211): truthy when used without a call
     def is_initialized(self):

@@ -12,6 +12,11 @@ it (:114-122) -- but picks the cheapest kernel sequence for it:
                            per-channel current_minmax -> 2 launches (fp8q_int_minmax_quantize_f32)
   INT, fixed ranges                                  -> 1 launch  (fp8q_int_quantize_f32)
   anything else (custom estimator / quantizer)       -> the generic protocol calls
+
+float16 / bfloat16 inputs take the same FP8 min/max routes on the half-precision kernels (fp8q_minmax_h16,
+fp8q_minmax_quantize_h16, fp8q_quantize_h16); everything else (MSE / line search, allow_unsigned, percentile, INT
+quantizers) is float32-only: the input is widened with .float() and the existing path runs (the output is cast back
+when the quantizer was built with keep_dtype).
 """
 from enum import auto
 
@@ -101,6 +106,9 @@ class QuantizationManager(nn.Module):
 
     def forward(self, x):
         q, est = self.quantizer, self.range_estimator
+        half = isinstance(x, torch.Tensor) and x.dtype in (torch.float16, torch.bfloat16) and x.is_cuda
+        if half and type(q) is not FPQuantizer:
+            x, half = x.float(), False               # INT / custom quantizers: float32-only
         if not self._estimating():
             return q(x)
         if type(q) in _UNIFORM and type(est) in _MINMAX and not getattr(est, "percentile", None):
@@ -119,6 +127,10 @@ class QuantizationManager(nn.Module):
             y = est.calibrate_quantize(x)            # estimate + set_quant_range + quantize: one library call
             if y is not None:
                 return y
+        if half and not fast:
+            # MSE search, allow_unsigned, percentile, custom estimators: float32-only -- widen, take the existing route
+            y = self.forward(x.float())
+            return y.to(x.dtype) if getattr(q, "keep_dtype", False) else y
         if not fast:
             xmin, xmax = est(x)                      # generic protocol, reference order
             if (type(q) is FPQuantizer and type(est) is FP_MSE_Estimator and q.set_maxval
@@ -136,7 +148,11 @@ class QuantizationManager(nn.Module):
         inner = x.numel() // max(x.shape[0], 1) if x.dim() > 0 else 1
         if (type(est) is CurrentMinMaxEstimator and self.per_channel and x.dim() > 0
                 and 0 < inner <= _ops.fused_max_inner()):
-            y, mn, mx, mv = _ops.minmax_quantize(x, float(q.mantissa_bits), q.n_bits, q.sign_bits)
+            if half:
+                y, mn, mx, mv = _ops.minmax_quantize(x, float(q.mantissa_bits), q.n_bits, q.sign_bits,
+                                                     out_dtype=q._half_out_dtype(x))
+            else:
+                y, mn, mx, mv = _ops.minmax_quantize(x, float(q.mantissa_bits), q.n_bits, q.sign_bits)
             est.current_xmin, est.current_xmax, est.last_maxval = mn, mx, mv
             q._set_maxval_tensor(mv)
             return y

@@ -484,6 +484,44 @@ int fp8q_int_minmax_quantize_f32(const float *x, float *y, int64_t C, int64_t in
                                  float *delta, float *zero_float, unsigned char *signed_flag, int n_bits, int symmetric,
                                  float eps, void *ws, size_t ws_bytes, fp8q_stream_t stream);
 
+/*
+ * The half-precision lane (csrc/fp8q_h16.hip): K1, min/max and min/max + quantize on IEEE fp16 and bfloat16 tensors.
+ * The reference holds maxval and the mantissa width as fp32 tensors, so ATen's type promotion widens a half x exactly,
+ * runs quantize_to_fp8_ste_MM (fp8_quantizer.py:105-133) in fp32 and returns fp32.  Contract of the lane:
+ *   - every input element is widened to fp32 exactly (fp16 subnormals become normal fp32 numbers, bf16 subnormals fp32
+ *     subnormals; nothing is flushed; NaN stays NaN, infinities clamp like any value beyond maxval);
+ *   - from there the fp32 contract applies unchanged: the fp32 result is bit-identical to fp8q_quantize_f32 -- and to
+ *     oracle/fp8q_oracle.c -- on the widened input;
+ *   - y_type is FP8Q_DT_F32 (the reference's promotion) or equal to x_type; in the second case the fp32 result is rounded
+ *     ONCE to the storage type (round to nearest even, overflow to infinity: torch.Tensor.to(dtype)).  y may alias x then;
+ *   - min/max: the fp32 minimum / maximum of the widened row with the NaN and signed-zero rules of fp8q_minmax_f32; the
+ *     running estimate, the fold and maxval_out are fp32.
+ * x_type / y_type: FP8Q_DT_*.  x (and a half y) need only their natural 2-byte alignment, an fp32 y 4 bytes; rows of any
+ * length, views at any element offset (per channel: rows of at most 2^30 elements, C * inner below 2^42; FP8Q_EINVAL
+ * beyond).  maxval fp32 [1] or [C] as in fp8q_quantize_f32.
+ * Errors, all reported before any launch: FP8Q_EINVAL for null pointers, n_maxval not in {1, C}, EMPTY tensors (C or inner
+ * <= 0), an x_type that is not a half type, a y_type that is neither FP8Q_DT_F32 nor x_type; FP8Q_EUNSUPPORTED for more
+ * than 7 exponent bits; FP8Q_EWORKSPACE / FP8Q_ETOOLONG as in the fp32 twins.
+ *   fp8q_quantize_h16         K1.  HBM traffic: 6 B / element (fp32 out), 4 B / element (half out).
+ *   fp8q_minmax_h16           fp8q_minmax_f32 on half x: same arguments, same fold modes, same workspace
+ *                             (fp8q_minmax_workspace_bytes(C, inner), zero on first use, left zero).  2 B / element.
+ *   fp8q_minmax_quantize_h16  per-channel current_minmax + K1 (fp8q_minmax_quantize_f32 on half x): a 2 B / element scan
+ *                             that writes row_min / row_max (each may be NULL) and maxval_out (REQUIRED here: it carries
+ *                             the ranges to the second launch), then K1 reading maxval_out.  inner <= fp8q_fused_max_inner().
+ * Enqueue-only, no allocation.  FP8Q_VERSION is unchanged: the entries are additive.
+ */
+#define FP8Q_DT_F32 0
+#define FP8Q_DT_F16 1
+#define FP8Q_DT_BF16 2
+int fp8q_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t C, int64_t inner, const float *maxval,
+                      int64_t n_maxval, float mbits, int n_bits, int sign_bits, fp8q_stream_t stream);
+int fp8q_minmax_h16(const void *x, int x_type, int64_t C, int64_t inner, float *cur_min, float *cur_max,
+                    float *maxval_out, int fold_mode, double momentum, int first, void *ws, size_t ws_bytes,
+                    fp8q_stream_t stream);
+int fp8q_minmax_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t C, int64_t inner, float *row_min,
+                             float *row_max, float *maxval_out, float mbits, int n_bits, int sign_bits,
+                             fp8q_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
