@@ -97,7 +97,8 @@ def _workspace(dev, nbytes, zeroed=False, kind=None, stream=None):
     counters must be zero on first use and are left zero by every call (include/fp8q.h) -- allocated zero-filled and
     never shared with the kernels that scribble over their scratch (MSE partial sums).  kind="select": the winner
     selection's buffer -- allocated zero-filled too (its header holds a ticket that every call leaves zero), but the rest
-    of it is ordinary scratch, so it is neither shared with the min/max workspace nor inspected by check_workspaces()."""
+    of it is ordinary scratch, so it is neither shared with the min/max workspace nor inspected by check_workspaces().
+    kind="grad": the partial sums of quantize_backward -- zero-filled, left zero by every call, a buffer of its own."""
     if stream is None:       # (callers that make several requests per launch pass the raw stream they already looked up)
         stream = _raw_stream(dev.index) if _raw_stream is not None else torch.cuda.current_stream(dev).cuda_stream
     key = (dev.index, stream, zeroed, kind)
@@ -109,7 +110,7 @@ def _workspace(dev, nbytes, zeroed=False, kind=None, stream=None):
             # synchronise inside an unrelated enqueue-only op (and raise another call's failure from it).  The list stays
             # short: a workspace only ever grows, and these buffers are tens of kilobytes.
             _ws_retired.append((key, ws))
-        alloc = torch.zeros if (zeroed or kind == "select") else torch.empty
+        alloc = torch.zeros if (zeroed or kind in ("select", "grad")) else torch.empty
         ws = alloc(max(int(nbytes), 1 << 16), dtype=torch.uint8, device=dev)
         _ws_cache[key] = ws
     return ws
@@ -228,6 +229,76 @@ def quantize(x, maxval, mbits, n_bits=8, sign_bits=1, out=None, out_dtype=None):
                 int(sign_bits), _stream(x))
     check(rc, "fp8q_quantize_f64" if x.dtype == torch.float64 else "fp8q_quantize_f32")
     return y
+
+
+_bwd_ws_bytes = {}
+
+
+def quantize_backward(x, g, maxval, mbits, n_bits=8, sign_bits=1, need_gx=True, need_gmaxval=True, need_gmbits=False,
+                      out=None):
+    """Backward of K1 (fp8q_quantize_bwd_f32): d/dx, d/dmaxval and d/dmbits of quantize(x; maxval, mbits) for the upstream
+    gradient g, in one pass over x and g -- the forward's result is recomputed in the kernel, nothing but x and maxval has to
+    be kept.  x, g: CUDA float32 of the same shape, contiguous (per tensor: any dense layout they share, as quantize());
+    maxval: CUDA float32 [1] or [C]; mbits: a number, or a 1-element CUDA float32 tensor (read by the kernel, which then also
+    evaluates the clamp test and the factor of d/dmbits: no host round trip).
+    out (with need_gx): a contiguous CUDA float32 tensor of x's shape that receives gx, as quantize()'s out; gx is then
+    written in x's logical order whatever x's layout.
+    Returns (gx | None, gmaxval | None, gmbits | None): gx like x (or out), gmaxval float32 [n_maxval], gmbits float32 [1]."""
+    _require(x, "x")
+    _require(g, "g", like=x)
+    _require(maxval, "maxval", like=x)
+    if out is not None:
+        _require(out, "out", like=x)
+        if not need_gx or out.shape != x.shape or not out.is_contiguous():
+            raise Fp8qError("out must be a contiguous tensor of x's shape, and only with need_gx")
+    if g.shape != x.shape:
+        raise Fp8qError(f"g has shape {tuple(g.shape)}, x {tuple(x.shape)}")
+    if not (need_gx or need_gmaxval or need_gmbits):
+        raise Fp8qError("quantize_backward: nothing requested")
+    maxval = maxval.detach().contiguous().view(-1)
+    n_mv = maxval.numel()
+    x, g = x.detach(), g.detach()
+    flat = _dense_flat(x) if (n_mv == 1 and out is None and g.stride() == x.stride()) else None
+    if flat is not None:
+        # per tensor on a dense non-contiguous layout shared by x and g: the storage as it lies, gx keeps the strides
+        res = torch.empty_like(x) if need_gx else None
+        flat_out = _dense_flat(res) if (need_gx and res.stride() == x.stride()) else None
+        if not need_gx or flat_out is not None:
+            _, gmv, gmb = quantize_backward(flat, _dense_flat(g), maxval, mbits, n_bits, sign_bits, need_gx, need_gmaxval,
+                                            need_gmbits, out=flat_out)
+            return res, gmv, gmb
+    x, g = x.contiguous(), g.contiguous()
+    C, inner = _rows(x, n_mv != 1)
+    if n_mv != 1 and n_mv != C:
+        raise Fp8qError(f"maxval has {n_mv} elements, expected 1 or {C}")
+    if x.numel() == 0:
+        raise Fp8qError("quantize_backward of an empty tensor")
+    mb_dev = None
+    if isinstance(mbits, torch.Tensor) and mbits.is_cuda:
+        _require(mbits, "mbits", like=x)
+        if mbits.numel() != 1:
+            raise Fp8qError("a device-resident mantissa width must be a 1-element float32 tensor")
+        mb_dev = mbits.detach()
+    gx = (out if out is not None else torch.empty_like(x)) if need_gx else None
+    gmv = torch.empty(n_mv, dtype=torch.float32, device=x.device) if need_gmaxval else None
+    gmb = torch.empty(1, dtype=torch.float32, device=x.device) if need_gmbits else None
+    L = lib()
+    ws_ptr, ws_len = None, 0
+    stream = _stream(x)
+    if need_gmaxval or need_gmbits:
+        nbytes = _bwd_ws_bytes.get((C, inner, n_mv))
+        if nbytes is None:
+            nbytes = _bwd_ws_bytes[(C, inner, n_mv)] = L.fp8q_quantize_bwd_workspace_bytes(C, inner, n_mv)
+        ws = _workspace(x.device, nbytes, kind="grad", stream=stream)
+        ws_ptr, ws_len = ws.data_ptr(), ws.numel()
+    with _on_device(x):
+        rc = L.fp8q_quantize_bwd_f32(x.data_ptr(), g.data_ptr(), gx.data_ptr() if need_gx else None, C, inner,
+                                     maxval.data_ptr(), n_mv, 0.0 if mb_dev is not None else float(mbits),
+                                     mb_dev.data_ptr() if mb_dev is not None else None, int(n_bits), int(sign_bits),
+                                     gmv.data_ptr() if need_gmaxval else None, gmb.data_ptr() if need_gmbits else None,
+                                     ws_ptr, ws_len, stream)
+    check(rc, "fp8q_quantize_bwd_f32")
+    return gx, gmv, gmb
 
 
 def sign_fold(x_min, signed_flag=None):

@@ -5,6 +5,8 @@
 one HIP kernel launch (fp8q.ops.quantize -> fp8q_quantize_f32) instead of 13 eager ATen ops.
 There is no CPU path: tensors must live on the GPU (fp8q raises otherwise).
 """
+import os
+
 import numpy as np
 import torch
 from torch import nn
@@ -50,29 +52,55 @@ class _FakeQuantSTE(torch.autograd.Function):
                  s = 2^(p - M - bias(M)), bias'(M) = -ln2 2^E + 2^-M / (2 - 2^-M), so dy/dM = (y - xc) ln2 (-1 - bias'(M))
                  per element, summed; round_ste passes the gradient, the clamp cuts it off outside [1, n_bits - sign_bits].
 
-    The backward runs as a handful of torch ops (PTQ, the path this engine accelerates, never calls it).  The kernel takes
-    the mantissa width by value (float(mbits): a host round trip per forward when the Parameter lives on the GPU -- QAT
-    territory, outside the accelerated path)."""
+    On CUDA float32 tensors the backward is ONE streaming kernel (fp8q.ops.quantize_backward -> fp8q_quantize_bwd_f32): it
+    reads x and the upstream gradient, recomputes y per element with the forward's own code and writes d/dx and the
+    deterministic fp64-accumulated sums of d/dmaxval and d/dmbits -- so the forward saves x and maxval only, not y.  A width
+    that lives on the GPU (learn_mantissa_bits: a CUDA Parameter) is never read by the host: the forward hands it to the
+    kernel as a device scalar (fp8q_quantize_dm_f32), the backward likewise, and d/dmbits comes back on the Parameter's device.
+    Everything else -- CPU tensors under the test-only oracle backend, float64, FP8Q_GRAD_KERNELS=0 -- runs the same
+    arithmetic as a chain of torch ops on the saved y (a host-resident width is passed by value on either route)."""
 
     @staticmethod
     def forward(ctx, x, maxval, mbits, n_bits, sign_bits):
-        mb_val = _host_float(mbits)
+        kernel_route = x.is_cuda and x.dtype == torch.float32 and _grad_kernels()
+        dev_width = kernel_route and isinstance(mbits, torch.Tensor) and mbits.is_cuda and mbits.numel() == 1
+        mb_val = mbits.detach().reshape(1).float() if dev_width else _host_float(mbits)
         y = _ops.quantize(x.detach(), maxval.detach(), mb_val, n_bits, sign_bits)
-        ctx.save_for_backward(x, maxval, y)
-        ctx.sign_bits, ctx.n_bits, ctx.mb_val = sign_bits, n_bits, mb_val
+        if kernel_route:
+            ctx.save_for_backward(*((x, maxval, mb_val) if dev_width else (x, maxval)))
+        else:
+            ctx.save_for_backward(x, maxval, y)
+        ctx.kernel_route, ctx.dev_width = kernel_route, dev_width
+        ctx.sign_bits, ctx.n_bits, ctx.mb_val = sign_bits, n_bits, (None if dev_width else mb_val)
         ctx.mbits_like = mbits if isinstance(mbits, torch.Tensor) else None
         return y
 
     @staticmethod
     def backward(ctx, grad):
+        need_x, need_mv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_mb = ctx.mbits_like is not None and ctx.needs_input_grad[2]
+        if ctx.kernel_route:
+            x, maxval = ctx.saved_tensors[:2]
+            mb = ctx.saved_tensors[2] if ctx.dev_width else ctx.mb_val
+            if not (grad.is_cuda and grad.dtype == torch.float32):      # y is CUDA float32, so its gradient is too
+                raise _ops.Fp8qError(f"_FakeQuantSTE.backward: expected a CUDA float32 gradient, got {grad.dtype} on {grad.device}")
+            if not (need_x or need_mv or need_mb):
+                return None, None, None, None, None
+            gx, gmv, gmb = _ops.quantize_backward(x, grad, maxval, mb, ctx.n_bits, ctx.sign_bits, need_x, need_mv, need_mb)
+            if need_mv:
+                gmv = gmv.reshape(maxval.shape)
+            if need_mb:
+                gmb = gmb.reshape(ctx.mbits_like.shape).to(device=ctx.mbits_like.device, dtype=ctx.mbits_like.dtype)
+            return gx, gmv, gmb, None, None
         x, maxval, y = ctx.saved_tensors
+        mb_val = ctx.mb_val
         mv = maxval.view([-1] + [1] * (x.dim() - 1)) if maxval.numel() != 1 else maxval
         lo = -mv if ctx.sign_bits == 1 else torch.zeros_like(mv)
         at_hi, at_lo = (x == mv), (x == lo)
         w_x = ((x > lo) & (x < mv)).to(grad.dtype) + 0.5 * (at_hi | at_lo).to(grad.dtype)
-        grad_x = grad * w_x if ctx.needs_input_grad[0] else None
+        grad_x = grad * w_x if need_x else None
         grad_mv = None
-        if ctx.needs_input_grad[1]:
+        if need_mv:
             xc = torch.min(torch.max(x, lo), mv)
             w = (y - xc) / mv + (x > mv).to(grad.dtype) + 0.5 * at_hi.to(grad.dtype)
             if ctx.sign_bits == 1:
@@ -81,9 +109,9 @@ class _FakeQuantSTE(torch.autograd.Function):
             grad_mv = g.sum().reshape(maxval.shape) if maxval.numel() == 1 else \
                 g.reshape(maxval.numel(), -1).sum(1).reshape(maxval.shape)
         grad_mb = None
-        if ctx.mbits_like is not None and ctx.needs_input_grad[2]:
+        if need_mb:
             hi = ctx.n_bits - ctx.sign_bits
-            r = float(np.float32(ctx.mb_val).round())          # torch.round: half to even, as np.round
+            r = float(np.float32(mb_val).round())          # torch.round: half to even, as np.round
             if 1.0 <= r <= hi:
                 M = r
                 E = hi - M
@@ -93,6 +121,12 @@ class _FakeQuantSTE(torch.autograd.Function):
             else:
                 grad_mb = torch.zeros_like(ctx.mbits_like)
         return grad_x, grad_mv, grad_mb, None, None
+
+
+def _grad_kernels():
+    """FP8Q_GRAD_KERNELS=0: the backward as a chain of torch ops even on the GPU (the comparison route of the tests and of
+    tools/mb_grad.py); read at every forward"""
+    return os.environ.get("FP8Q_GRAD_KERNELS", "1") != "0"
 
 
 def _host_float(t):
@@ -112,7 +146,9 @@ def quantize_to_fp8_ste_MM(x_float, n_bits, maxval, num_mantissa_bits, sign_bits
     x_float float16 / bfloat16: the result is float32, as the reference's type promotion gives (maxval and the width are
     float32 tensors), from the half-precision kernels (fp8q_quantize_h16); out_dtype=x_float.dtype (not in the reference)
     rounds it once to x's own dtype.  Under autograd, or with a width / sign still pending on the device, the input is
-    widened with .float() and takes the float32 route."""
+    widened with .float() and takes the float32 route.
+    Under autograd (x, maxval or the width requires a gradient) the call goes through _FakeQuantSTE: on CUDA float32 the
+    backward is one HIP kernel too, and a width on the GPU is read by neither pass on the host."""
     mb_grad = isinstance(num_mantissa_bits, torch.Tensor) and num_mantissa_bits.requires_grad and torch.is_grad_enabled()
     if x_float.dtype in _HALF:
         if out_dtype not in (None, torch.float32, x_float.dtype):
@@ -128,14 +164,16 @@ def quantize_to_fp8_ste_MM(x_float, n_bits, maxval, num_mantissa_bits, sign_bits
         maxval = maxval.to(device=x_float.device, dtype=torch.float32).reshape(-1)
         return _ops.quantize(x_float, maxval.detach(), _host_float(num_mantissa_bits), int(n_bits), int(sign_bits),
                              out_dtype=out_dtype)
-    on_device = (isinstance(num_mantissa_bits, torch.Tensor) and num_mantissa_bits.is_cuda and num_mantissa_bits.numel() == 1
-                 and x_float.dtype == torch.float32 and not mb_grad
-                 and not (torch.is_grad_enabled() and x_float.requires_grad))
-    mbits = num_mantissa_bits.detach().reshape(1).float() if on_device else _host_float(num_mantissa_bits)
     if not isinstance(maxval, torch.Tensor):
         maxval = torch.tensor([float(maxval)], dtype=torch.float32)
     maxval = maxval.to(device=x_float.device, dtype=torch.float32).reshape(-1)
-    if torch.is_grad_enabled() and (x_float.requires_grad or maxval.requires_grad or mb_grad):
+    autograd = torch.is_grad_enabled() and (x_float.requires_grad or maxval.requires_grad or mb_grad)
+    # a width on the GPU stays there (fp8q_quantize_dm_f32 reads it) -- under autograd too, where the backward kernel reads
+    # it as well; only the torch-chain backward (FP8Q_GRAD_KERNELS=0) needs it on the host
+    on_device = (isinstance(num_mantissa_bits, torch.Tensor) and num_mantissa_bits.is_cuda and num_mantissa_bits.numel() == 1
+                 and x_float.dtype == torch.float32 and x_float.is_cuda and not (autograd and not _grad_kernels()))
+    mbits = num_mantissa_bits.detach().reshape(1).float() if on_device else _host_float(num_mantissa_bits)
+    if autograd:
         return _FakeQuantSTE.apply(x_float, maxval, num_mantissa_bits if mb_grad else mbits, int(n_bits), int(sign_bits))
     if isinstance(sign_bits, torch.Tensor):
         # FPQuantizer's pending device flag (allow_unsigned, not yet read by the host): the kernel reads it
@@ -203,8 +241,11 @@ class FPQuantizer(QuantizerBase):
 
     Constructor kwargs, attributes (`maxval`, `mantissa_bits`, `sign_bits`, `set_maxval`,
     `allow_unsigned`, `mse_include_mantissa_bits`) and methods follow the reference class
-    (fp8_quantizer.py:151-272).  `maxval` lives on the GPU ([1] or [C]); `mantissa_bits` stays a
-    host tensor because the kernel takes it by value.
+    (fp8_quantizer.py:151-272).  `maxval` lives on the GPU ([1] or [C]); `mantissa_bits` is a host
+    tensor passed to the kernels by value -- unless it is pending on the device (the MSE vote) or being
+    learned (learn_mantissa_bits: a Parameter on the quantizer's device), in which case forward AND
+    backward kernels read it from device memory and no step synchronises.  With learn_maxval /
+    learn_mantissa_bits the gradients come from one HIP kernel per backward (see _FakeQuantSTE).
     """
 
     def __init__(self, *args, scale_domain=None, mantissa_bits=4, maxval=3, set_maxval=False,
@@ -417,7 +458,8 @@ class FPQuantizer(QuantizerBase):
 
     def learn_mantissa_bits(self):
         """:253-255: the mantissa width becomes an nn.Parameter; quantize_to_fp8_ste_MM's backward then yields
-        d/dmbits (see _FakeQuantSTE).  The forward still hands the kernel the width by value."""
+        d/dmbits (see _FakeQuantSTE).  The Parameter lives on the quantizer's device; on the GPU the forward and the
+        backward kernel read it there (fp8q_quantize_dm_f32 / fp8q_quantize_bwd_f32's mbits_dev): no host round trip."""
         self.learning_mantissa_bits = True
         # on the quantizer's device (maxval's): a host Parameter inside a CUDA model would stay behind until the next .to()
         self.mantissa_bits = nn.Parameter(self.mantissa_bits.detach().clone().float().to(self.maxval.device))

@@ -522,6 +522,35 @@ int fp8q_minmax_quantize_h16(const void *x, void *y, int x_type, int y_type, int
                              float *row_max, float *maxval_out, float mbits, int n_bits, int sign_bits,
                              fp8q_stream_t stream);
 
+/* ---- backward of the FP quantizer (csrc/fp8q_grad.hip) --------------------------------------------------------------------
+ * The gradient of quantize_to_fp8_ste_MM (fp8_quantizer.py:105-133) with respect to x, maxval and the mantissa width, in
+ * ONE streaming pass over x and the upstream gradient g (contiguous fp32 viewed as [C, inner], the layout rules of
+ * fp8q_quantize_f32: n_maxval == 1 treats the tensor as one row).  With lo = -maxval (signed) or 0 (unsigned):
+ *   gx[i]      = g[i] * m,  m = 1 strictly inside (lo, maxval), 0.5 exactly on a bound, 0 outside (a NaN x gives 0).  Exact.
+ *   gmaxval[c] = sum over the row of g * w,  w = (y - xc) / maxval + [x > maxval] + 0.5 [x == maxval]
+ *                                                - [x < lo] - 0.5 [x == lo]     (the last two terms: signed formats only)
+ *   gmbits[0]  = ln2 (-1 - bias'(M)) * sum over everything of g * (y - xc),  bias'(M) = -ln2 2^E + 2^-M / (2 - 2^-M),
+ *                M = clamp(rint(mbits), 1, n_bits - sign_bits); zero when rint(mbits) lies outside the clamp.
+ * y is the forward's result, recomputed per element with the forward's own code (bit-identical to fp8q_quantize_f32), so
+ * the caller keeps no y between forward and backward; xc = min(max(x, lo), maxval).  Each term is formed in fp32 in the order
+ * written above, the sums are accumulated in fp64 in a fixed order (no floating-point atomics): two calls on the same buffers
+ * give the same bits.  Any of gx, gmaxval [n_maxval], gmbits [1] may be NULL (not all three).
+ * mbits_dev != NULL: the width is read from that device scalar (as fp8q_quantize_dm_f32), `mbits` is ignored, and the
+ * rounding, the clamp test and the factor of gmbits are evaluated on the device: no host read of the width.
+ * ws: 8-byte aligned, at least fp8q_quantize_bwd_workspace_bytes(C, inner, n_maxval) bytes, needed when gmaxval or gmbits is
+ * requested (per-block partial sums; a second small launch adds them up).  The workspace rule of this library holds: zero
+ * before the first use, left zero by every call.
+ * HBM traffic: 12 B / element (x, g, gx), 8 B / element without gx.  Pointers need 4-byte alignment only.
+ * Errors, all reported before any launch: FP8Q_EINVAL for null x / g / maxval, empty shapes (C or inner <= 0), n_maxval not
+ * in {1, C}, sign_bits not in {0, 1}, misaligned fp32 pointers, gx == gmaxval == gmbits == NULL; FP8Q_EUNSUPPORTED for the
+ * formats the forward refuses (more than 7 exponent bits); FP8Q_EWORKSPACE for a missing, misaligned or too small workspace.
+ * Enqueue-only, no allocation.  FP8Q_VERSION is unchanged: the entries are additive.
+ */
+int fp8q_quantize_bwd_f32(const float *x, const float *g, float *gx, int64_t C, int64_t inner, const float *maxval,
+                          int64_t n_maxval, float mbits, const float *mbits_dev, int n_bits, int sign_bits, float *gmaxval,
+                          float *gmbits, void *ws, size_t ws_bytes, fp8q_stream_t stream);
+size_t fp8q_quantize_bwd_workspace_bytes(int64_t C, int64_t inner, int64_t n_maxval);
+
 #ifdef __cplusplus
 }
 #endif
