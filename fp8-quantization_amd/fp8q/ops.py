@@ -792,6 +792,37 @@ def int_minmax_quantize(x, n_bits=8, symmetric=False, eps=1e-8, delta=None, zero
     return y, mn, mx, delta, zero_float, signed_flag
 
 
+def int_sse_grid(x, per_channel, thr, n_bits=8, symmetric=True, one_sided=False, eps=1e-8, out=None):
+    """LineSearchEstimator's candidates for a uniform quantizer in one pass: out[n_cand, C] (float64, updated in place;
+    a zero-filled one when None) += row-sum of (x - q_k(x))^2, q_k the quantizer after
+    set_quant_range(0 if one_sided else -thr[k, c], thr[k, c]).  x CUDA float32 or float64 (the float64 lane follows
+    ATen's type promotion); thr CUDA fp32 [n_cand, C].  Two launches, no host round trip."""
+    _require(x, "x", (torch.float32, torch.float64))
+    _require(thr, "thr", like=x)
+    x = x.contiguous()
+    C, inner = _rows(x, per_channel)
+    if C == 0 or inner == 0:
+        raise Fp8qError("candidate search on an empty tensor")
+    if thr.dim() != 2 or thr.shape[1] != C or thr.shape[0] == 0 or not thr.is_contiguous():
+        raise Fp8qError(f"thr must be contiguous [n_cand, {C}]")
+    n_cand = thr.shape[0]
+    if out is None:
+        out = torch.zeros((n_cand, C), dtype=torch.float64, device=x.device)
+    else:
+        _require(out, "out", torch.float64, like=x)
+        if tuple(out.shape) != (n_cand, C) or not out.is_contiguous():
+            raise Fp8qError(f"out must be contiguous [{n_cand}, {C}]")
+    L = lib()
+    ws = _workspace(x.device, L.fp8q_int_sse_grid_workspace_bytes(C, inner, n_cand))
+    fn, name = ((L.fp8q_int_sse_grid_f64, "fp8q_int_sse_grid_f64") if x.dtype == torch.float64
+                else (L.fp8q_int_sse_grid_f32, "fp8q_int_sse_grid_f32"))
+    with _on_device(x):
+        rc = fn(x.data_ptr(), C, inner, thr.data_ptr(), n_cand, int(n_bits), int(bool(symmetric)), int(bool(one_sided)),
+                float(eps), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(x))
+    check(rc, name)
+    return out
+
+
 def copy(x, out=None):
     """float4 copy kernel with K1's launch shape (HBM ceiling yardstick)."""
     _require(x, "x")

@@ -434,8 +434,9 @@ class LineSearchEstimator(RangeEstimatorBase):
     k * (max|x| + range_margin) * expand_range / num_candidates; losses accumulate over calls.
 
     FP8 quantizers evaluate ALL candidates in one pass over x with the MSE-grid kernel
-    (fp8q_mse_grid_f32 with n_cand = num_candidates); INT quantizers, the comparison baseline,
-    loop over candidates with elementwise torch ops.  Only the symmetric 1-D search exists: the
+    (fp8q_mse_grid_f32 with n_cand = num_candidates); so do INT quantizers, the comparison baseline, on CUDA float32 /
+    float64 data in the linear scale domain (fp8q_int_sse_grid_f32 / _f64: one call per batch) -- elsewhere (CPU, log
+    domain, a custom discretizer, FP8Q_INT_KERNELS=0, a zero step) they loop over candidates with elementwise torch ops.  Only the symmetric 1-D search exists: the
     reference takes it for every quantizer that can reach this estimator (`quantizer.symmetric`
     is used without being called there, so it is truthy for FPQuantizer too -- SURVEY.md 3.4).
     Precision follows the data, as in the reference: a float64 sample (compute_quant_error.py:19-20) is searched in
@@ -505,6 +506,14 @@ class LineSearchEstimator(RangeEstimatorBase):
             mses = torch.zeros(1, n, C, device=data.device)
             _ops.mse_grid(data, self.per_channel, grid, [float(q.mantissa_bits)], q.n_bits, sign_bits, mses)
             return (mses[0].double() * inner).transpose(0, 1).cpu().numpy()
+        from .uniform import AsymmetricUniformQuantizer
+        if (isinstance(q, AsymmetricUniformQuantizer) and q._kernel_common(data.device)
+                and data.dtype in (torch.float32, torch.float64) and self.step_size > 0):
+            # every candidate in one pass over the batch (fp8q_int_sse_grid_f32 / _f64): the arithmetic of the loop below,
+            # element for element; float32 squares are summed in float64
+            grid = torch.from_numpy(thr).to(data.device).view(n, 1).expand(n, C).contiguous()
+            sse = _ops.int_sse_grid(data, self.per_channel, grid, q.n_bits, q.symmetric, bool(self.one_sided_dist), q.eps)
+            return sse.transpose(0, 1).cpu().numpy()
         import copy
         out = np.zeros((C, n))
         flat = data.view(C, -1)

@@ -485,6 +485,33 @@ int fp8q_int_minmax_quantize_f32(const float *x, float *y, int64_t C, int64_t in
                                  float eps, void *ws, size_t ws_bytes, fp8q_stream_t stream);
 
 /*
+ * The line search of the uniform quantizers (csrc/fp8q_int.hip): LineSearchEstimator's candidates
+ * (range_estimators.py:161-169, 236-256) in ONE pass over the data instead of one quantizer pass per candidate.
+ *   out[k, c] += sum over row c of (x - q_k(x))^2,   k < n_cand, c < C
+ * with q_k the uniform quantizer after set_quant_range(one_sided ? 0 : -thr[k, c], thr[k, c]): the range chain above in
+ * fp32 on that one-element range (symmetric: signed iff its x_min < 0), then the quantize chain.
+ *   x    [C, inner] contiguous float32 (_f32) or float64 (_f64), natural alignment: views at any element offset.
+ *   thr  [n_cand, C] fp32 (what torch.tensor(pos_thr).float() holds);  out [n_cand, C] float64, ACCUMULATED.
+ * Per element, _f32: the fp32 chain bit for bit, d = x - y and d * d in fp32, summed in float64.  _f64: ATen's type
+ * promotion -- scale and zero point are fp32 values widened exactly; the IEEE double division x / scale, rint, + zp, the
+ * clamp, scale * (r - zp), x - y and the square in float64.  No contraction.  A NaN in a row makes the row's sums NaN.
+ * The sums have a fixed order and use no atomics: two calls on the same buffers give the same bits; against the exact sum
+ * of the squares the relative error is below (inner + 2) 2^-53.
+ * ws: at least fp8q_int_sse_grid_workspace_bytes() bytes, 8-byte aligned, need not be initialised.  Two launches,
+ * enqueue-only, no allocation.  n_cand <= 2^20.
+ * Errors, all reported before any launch: FP8Q_EINVAL for null pointers, empty shapes (C or inner <= 0), n_cand <= 0,
+ * misaligned x / thr / out; FP8Q_EUNSUPPORTED for n_bits outside [2, 16]; FP8Q_ETOOMANY for C > 65535; FP8Q_EWORKSPACE
+ * for a missing, misaligned or too small workspace.  FP8Q_VERSION is unchanged: the entries are additive.
+ */
+size_t fp8q_int_sse_grid_workspace_bytes(int64_t C, int64_t inner, int64_t n_cand);
+int fp8q_int_sse_grid_f32(const float *x, int64_t C, int64_t inner, const float *thr, int64_t n_cand, int n_bits,
+                          int symmetric, int one_sided, float eps, double *out, void *ws, size_t ws_bytes,
+                          fp8q_stream_t stream);
+int fp8q_int_sse_grid_f64(const double *x, int64_t C, int64_t inner, const float *thr, int64_t n_cand, int n_bits,
+                          int symmetric, int one_sided, float eps, double *out, void *ws, size_t ws_bytes,
+                          fp8q_stream_t stream);
+
+/*
  * The half-precision lane (csrc/fp8q_h16.hip): K1, min/max and min/max + quantize on IEEE fp16 and bfloat16 tensors.
  * The reference holds maxval and the mantissa width as fp32 tensors, so ATen's type promotion widens a half x exactly,
  * runs quantize_to_fp8_ste_MM (fp8_quantizer.py:105-133) in fp32 and returns fp32.  Contract of the lane:
