@@ -35,6 +35,7 @@
 //   k_int_range   range-set alone: (xmin, xmax) -> delta, zero_float, signed.
 //   k_int_sse<T>  the line search's candidates in one pass (see "The candidate search" below), k_int_sse_final its sums.
 #include "fp8q_common.h"
+#include "fp8q_intq.h"
 
 namespace {
 
@@ -59,19 +60,6 @@ struct IntArgs {
     float n_hi_s;            // 2^(n-1) - 1
     float n_lo_s;            // -2^(n-1)
 };
-
-__device__ __forceinline__ float t_min(float a, float b)   // torch.min(a, b) of the scalar loop: a unless b < a
-{
-    return (a != a) ? a : ((b != b) ? b : (b < a ? b : a));
-}
-__device__ __forceinline__ float t_max(float a, float b)
-{
-    return (a != a) ? a : ((b != b) ? b : (b > a ? b : a));
-}
-__device__ __forceinline__ float t_clamp(float v, float lo, float hi)   // torch.clamp: NaN passes, v when equal
-{
-    return (v != v) ? v : (v < lo ? lo : (v > hi ? hi : v));
-}
 
 // the sign of a symmetric range: no NaN in x_min and some x_min < 0 (x_min' = min(x_min, 0) has the same predicates)
 __device__ __forceinline__ bool block_sign(const float *__restrict__ xmin, int64_t C)
@@ -104,14 +92,6 @@ __device__ __forceinline__ Range range_of(float xmin, float xmax, bool symmetric
         r.zf = -mn / r.delta;
     }
     return r;
-}
-
-// {scale, 1/scale, zp, -}
-__device__ __forceinline__ float4 consts_of(float delta, float zf, bool symmetric, float lo, float hi, float eps)
-{
-    const float s = t_max(delta, eps);
-    const float zp = symmetric ? 0.0f : t_clamp(rintf(zf), lo, hi);
-    return make_float4(s, 1.0f / s, zp, 0.0f);
 }
 
 __device__ __forceinline__ float int_one(float v, const float4 k, float lo, float hi)

@@ -713,6 +713,69 @@ def int_quantize(x, delta, zero_float=None, signed_flag=None, n_bits=8, symmetri
     return res
 
 
+def int_quantize_backward(x, g, delta, zero_float=None, signed_flag=None, n_bits=8, symmetric=False, eps=1e-8, need_gx=True,
+                          need_gdelta=True, need_gzero=False, grad_scale_elems=0, out=None):
+    """Backward of int_quantize (fp8q_int_quantize_bwd_f32): d/dx, d/ddelta and d/dzero_float for the upstream gradient g, in
+    one pass over x and g -- the forward's integers are recomputed in the kernel, nothing but x and the ranges has to be kept.
+    x, g: CUDA float32 of the same shape, contiguous (per tensor: any dense layout they share, as int_quantize()); the range
+    arguments as int_quantize().  grad_scale_elems > 0: LSQ's gradient scaling, both range gradients times
+    1 / sqrt(int_max * grad_scale_elems), int_max read on the device (numel / C per channel, numel per tensor).
+    out (with need_gx): a contiguous CUDA float32 tensor of x's shape that receives gx.
+    Returns (gx | None, gdelta | None, gzero_float | None): gx like x (or out), the others float32 [n_delta]."""
+    _require(x, "x")
+    _require(g, "g", like=x)
+    if out is not None:
+        _require(out, "out", like=x)
+        if not need_gx or out.shape != x.shape or not out.is_contiguous():
+            raise Fp8qError("out must be a contiguous tensor of x's shape, and only with need_gx")
+    if g.shape != x.shape:
+        raise Fp8qError(f"g has shape {tuple(g.shape)}, x {tuple(x.shape)}")
+    if not (need_gx or need_gdelta or need_gzero):
+        raise Fp8qError("int_quantize_backward: nothing requested")
+    if need_gzero and symmetric:
+        raise Fp8qError("int_quantize_backward: a symmetric quantizer has no zero_float")
+    delta = delta.detach().reshape(-1)
+    n = delta.numel()
+    zero_float = zero_float.detach().reshape(-1) if zero_float is not None else None
+    signed_flag = signed_flag.detach().reshape(-1) if signed_flag is not None else None
+    pd, pz, ps = _int_ptrs(x, delta, zero_float, signed_flag, symmetric, n)
+    x, g = x.detach(), g.detach()
+    flat = _dense_flat(x) if (n == 1 and out is None and g.stride() == x.stride()) else None
+    if flat is not None:
+        # per tensor on a dense non-contiguous layout shared by x and g: the storage as it lies, gx keeps the strides
+        res = torch.empty_like(x) if need_gx else None
+        flat_out = _dense_flat(res) if (need_gx and res.stride() == x.stride()) else None
+        if not need_gx or flat_out is not None:
+            _, gd, gz = int_quantize_backward(flat, _dense_flat(g), delta, zero_float, signed_flag, n_bits, symmetric, eps,
+                                              need_gx, need_gdelta, need_gzero, grad_scale_elems, out=flat_out)
+            return res, gd, gz
+    x, g = x.contiguous(), g.contiguous()
+    C, inner = _rows(x, n != 1)
+    if n != 1 and n != C:
+        raise Fp8qError(f"the range has {n} elements, expected 1 or {C}")
+    if x.numel() == 0:
+        raise Fp8qError("int_quantize_backward of an empty tensor")
+    gx = (out if out is not None else torch.empty_like(x)) if need_gx else None
+    gd = torch.empty(n, dtype=torch.float32, device=x.device) if need_gdelta else None
+    gz = torch.empty(n, dtype=torch.float32, device=x.device) if need_gzero else None
+    L = lib()
+    ws_ptr, ws_len = None, 0
+    stream = _stream(x)
+    if need_gdelta or need_gzero:
+        nbytes = _bwd_ws_bytes.get(("int", C, inner, n))
+        if nbytes is None:
+            nbytes = _bwd_ws_bytes[("int", C, inner, n)] = L.fp8q_int_quantize_bwd_workspace_bytes(C, inner, n)
+        ws = _workspace(x.device, nbytes, kind="grad", stream=stream)
+        ws_ptr, ws_len = ws.data_ptr(), ws.numel()
+    with _on_device(x):
+        rc = L.fp8q_int_quantize_bwd_f32(x.data_ptr(), g.data_ptr(), gx.data_ptr() if need_gx else None, C, inner, pd, pz, n,
+                                         ps, int(n_bits), int(bool(symmetric)), float(eps), int(grad_scale_elems),
+                                         gd.data_ptr() if need_gdelta else None, gz.data_ptr() if need_gzero else None,
+                                         ws_ptr, ws_len, stream)
+    check(rc, "fp8q_int_quantize_bwd_f32")
+    return gx, gd, gz
+
+
 def _int_range_out(x_min, delta, zero_float, signed_flag, symmetric):
     n = x_min.numel()
     dev = x_min.device

@@ -1,20 +1,71 @@
 """Uniform (INT) fake-quantizers -- the INT baseline of the FP8 study (compute_quant_error.py config 1, --qmethod-act).
 
-Reference: quantization/quantizers/uniform_quantizers.py:13-331.  On CUDA fp32 tensors in the linear scale domain,
-without autograd, `forward` and `set_quant_range` run the HIP kernels of csrc/fp8q_int.hip (one launch each, the
-symmetric sign read from device memory: no host round trip); everything else -- CPU, other dtypes, the log domain,
-range learning, a custom discretizer -- is the reference's torch op chain.  FP8Q_INT_KERNELS=0 forces that chain.
+Reference: quantization/quantizers/uniform_quantizers.py:13-331.  On CUDA fp32 tensors in the linear scale domain
+`forward` and `set_quant_range` run the HIP kernels of csrc/fp8q_int.hip (one launch each, the symmetric sign read from
+device memory: no host round trip).  Under autograd -- x or a learned range (`make_range_trainable`) wants a gradient --
+`forward` goes through _IntFakeQuantSTE: the same forward kernel, and ONE backward kernel (csrc/fp8q_intgrad.hip) for d/dx,
+d/ddelta and d/dzero_float, LSQ's `grad_scaling` included.  Everything else -- CPU, other dtypes, the log domain, a custom
+discretizer -- is the reference's torch op chain.  FP8Q_INT_KERNELS=0 forces that chain, FP8Q_GRAD_KERNELS=0 forces it
+under autograd only (the switch of the FP quantizer's backward).
 """
 import os
 
 import torch
 
 from fp8q import ops as _ops
-from .fp8 import QuantizerBase, QuantizerNotInitializedError, round_ste_func
+from .fp8 import QuantizerBase, QuantizerNotInitializedError, _grad_kernels, round_ste_func
 
 
 def _int_kernels_enabled():
     return os.environ.get("FP8Q_INT_KERNELS", "1") != "0"
+
+
+class _ScaleGradient(torch.autograd.Function):
+    """identity forward, the gradient times a constant backward (reference rounding_utils.py: scale_grad_func)"""
+
+    @staticmethod
+    def forward(ctx, x, scale):
+        ctx.scale = scale
+        return x
+
+    @staticmethod
+    def backward(ctx, grad):
+        return grad * ctx.scale, None
+
+
+scale_grad_func = _ScaleGradient.apply
+
+
+class _IntFakeQuantSTE(torch.autograd.Function):
+    """fp8q.ops.int_quantize forward, fp8q.ops.int_quantize_backward backward: what autograd derives from the op chain
+    scale * (clamp(round_ste(x / scale) + zp, int_min, int_max) - zp) (include/fp8q.h states the arithmetic), computed
+    only for the inputs that need a gradient.  The forward keeps x and the ranges, not its result."""
+
+    @staticmethod
+    def forward(ctx, x, delta, zero_float, signed_flag, n_bits, symmetric, eps, grad_scale_elems):
+        y = _ops.int_quantize(x.detach(), delta.detach(), None if zero_float is None else zero_float.detach(), signed_flag,
+                              n_bits, symmetric, eps)
+        ctx.save_for_backward(x, delta, zero_float, signed_flag)
+        ctx.cfg = (n_bits, symmetric, eps, grad_scale_elems)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, delta, zero_float, signed_flag = ctx.saved_tensors
+        need_x, need_d = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_z = zero_float is not None and ctx.needs_input_grad[2]
+        if not (grad.is_cuda and grad.dtype == torch.float32):      # y is CUDA float32, so its gradient is too
+            raise _ops.Fp8qError(f"_IntFakeQuantSTE.backward: expected a CUDA float32 gradient, got {grad.dtype} on {grad.device}")
+        if not (need_x or need_d or need_z):
+            return (None,) * 8
+        n_bits, symmetric, eps, gs_elems = ctx.cfg
+        gx, gd, gz = _ops.int_quantize_backward(x, grad, delta, zero_float, signed_flag, n_bits, symmetric, eps, need_x,
+                                                need_d, need_z, gs_elems)
+        if need_d:
+            gd = gd.reshape(delta.shape)
+        if need_z:
+            gz = gz.reshape(zero_float.shape)
+        return gx, gd, gz, None, None, None, None, None
 
 
 class AsymmetricUniformQuantizer(QuantizerBase):
@@ -58,6 +109,32 @@ class AsymmetricUniformQuantizer(QuantizerBase):
                 and not (x.requires_grad and torch.is_grad_enabled())):
             return False
         return n == 1 or (self.per_channel and x.dim() > 0 and x.shape[0] == n)
+
+    def _grad_kernel_ok(self, x, dev):
+        """The autograd route: x CUDA fp32, fp32 ranges on x's device (Parameters or buffers), something wants a gradient."""
+        if not (torch.is_grad_enabled() and _grad_kernels() and isinstance(x, torch.Tensor) and x.is_cuda
+                and x.dtype == torch.float32):
+            return False
+        d, z = self._delta, (None if self.symmetric else self._zero_float)
+
+        def fp32_here(t):
+            return isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == dev
+
+        if not fp32_here(d) or not (d.numel() == 1 or (self.per_channel and x.dim() > 0 and x.shape[0] == d.numel())):
+            return False
+        if self.symmetric:
+            sg = self._signed
+            if not (isinstance(sg, torch.Tensor) and sg.dtype == torch.bool and sg.device == dev and sg.numel() == 1):
+                return False
+        elif not (fp32_here(z) and z.numel() == d.numel()):
+            return False
+        return x.numel() > 0 and (x.requires_grad or d.requires_grad or (z is not None and z.requires_grad))
+
+    def _grad_scale_elems(self, x):
+        """calculate_grad_scale's element count (0: no gradient scaling)"""
+        if not self.grad_scaling:
+            return 0
+        return x.numel() // x.shape[0] if self.per_channel else x.numel()
 
     def _range_out(self, x_min):
         """The range buffers the kernels write: the current ones in place when they fit, fresh ones otherwise."""
@@ -183,8 +260,25 @@ class AsymmetricUniformQuantizer(QuantizerBase):
             zp = zp.view(shape) if torch.is_tensor(zp) and zp.dim() == 1 else zp
         return scale, zp
 
+    def calculate_grad_scale(self, quant_tensor):
+        """LSQ's 1 / sqrt(Qp * N): N the elements of a channel (per channel) or of the tensor"""
+        n = quant_tensor.numel()
+        if self.per_channel:
+            n /= quant_tensor.shape[0]
+        return (self.int_max * n) ** -0.5
+
+    def _chain_params(self, x):
+        """_params_like, with the gradients of scale and zero point scaled when grad_scaling is set"""
+        scale, zp = self._params_like(x)
+        if self.grad_scaling and torch.is_grad_enabled():
+            gs = self.calculate_grad_scale(x)
+            scale = scale_grad_func(scale, gs)
+            if not self.symmetric:
+                zp = scale_grad_func(zp, gs)
+        return scale, zp
+
     def to_integer_forward(self, x_float, *args, **kwargs):
-        scale, zp = self._params_like(x_float)
+        scale, zp = self._chain_params(x_float)
         return torch.clamp(self.discretizer(x_float / scale) + zp, self.int_min, self.int_max)
 
     def forward(self, x_float, *args, **kwargs):
@@ -193,7 +287,11 @@ class AsymmetricUniformQuantizer(QuantizerBase):
                 and self._kernel_x_ok(x_float, d.numel())):
             return _ops.int_quantize(x_float, d, None if self.symmetric else self._zero_float,
                                      self._signed if self.symmetric else None, self.n_bits, self.symmetric, self.eps)
-        scale, zp = self._params_like(x_float)
+        if d is not None and self._kernel_common(x_float.device) and self._grad_kernel_ok(x_float, x_float.device):
+            return _IntFakeQuantSTE.apply(x_float, d, None if self.symmetric else self._zero_float,
+                                          self._signed if self.symmetric else None, self.n_bits, self.symmetric, self.eps,
+                                          self._grad_scale_elems(x_float))
+        scale, zp = self._chain_params(x_float)
         return scale * (self.to_integer_forward(x_float) - zp)
 
     def _tensorize_min_max(self, x_min, x_max):

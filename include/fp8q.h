@@ -578,6 +578,42 @@ int fp8q_quantize_bwd_f32(const float *x, const float *g, float *gx, int64_t C, 
                           float *gmbits, void *ws, size_t ws_bytes, fp8q_stream_t stream);
 size_t fp8q_quantize_bwd_workspace_bytes(int64_t C, int64_t inner, int64_t n_maxval);
 
+/* ---- backward of the uniform (INT) quantizers (csrc/fp8q_intgrad.hip) -------------------------------------------------------
+ * The gradient of fp8q_int_quantize_f32 (uniform_quantizers.py:108-164, linear scale domain, round_ste) with respect to x,
+ * delta and zero_float, in ONE streaming pass over x and the upstream gradient g (contiguous fp32 viewed as [C, inner];
+ * n_delta == 1 treats the whole tensor as one row, n_delta == C gives one sum per row).  The forward, fp32 throughout:
+ *   scale = max(delta, eps);  zp = clamp(rint(zero_float), lo, hi) (0 when symmetric);  [lo, hi] as fp8q_int_quantize_f32,
+ *   the symmetric sign read from the device byte signed_flag;  t = fl32(x / scale), the IEEE quotient;  u = rint(t) + zp;
+ *   v = clamp(u, lo, hi);  y = scale * (v - zp).
+ * With m = 1.0f when lo <= u <= hi (bounds inclusive, as ATen's clamp backward), else 0.0f (a NaN u gives 0):
+ *   gx[i]          = g[i] * m.  Exact (the autograd chain forms (g * scale) * m / scale: the same value up to 1 ULP).
+ *   gdelta[c]      = [delta_c >= eps] * sum over the row of g * w,  w = (v - zp) - fl32(m * t), each term formed in fp32 in
+ *                    that order.  The product m * t is deliberate: x = +-inf gives 0 * inf = NaN, a NaN x is NaN as well,
+ *                    and such a row gets a NaN gradient -- as the chain's 0 * ((x / scale) / scale) does.
+ *   gzero_float[c] = -[lo <= rint(zero_float_c) <= hi] * sum over the row of (1 - m) * fl32(g * scale)   (asymmetric only)
+ * A false mask gives exactly 0.  The sums are accumulated in fp64 in a fixed order (no floating-point atomics): two calls on
+ * the same buffers give the same bits.
+ * grad_scale_elems > 0 (LSQ's gradient scaling, calculate_grad_scale, uniform_quantizers.py:166-173): both sums, after they
+ * are rounded to fp32, are multiplied by gs = (float)(1 / sqrt((double)hi * (double)grad_scale_elems)), hi the positive end
+ * of the integer range -- taken from signed_flag when symmetric, so there is no host read.  The caller passes numel / C per
+ * channel and numel per tensor.  0: no scaling.
+ * Any of gx, gdelta [n_delta], gzero_float [n_delta] may be NULL (not all three); gzero_float with symmetric is
+ * FP8Q_EINVAL.  zero_float may be NULL when symmetric, signed_flag when not.
+ * ws: 8-byte aligned, at least fp8q_int_quantize_bwd_workspace_bytes(C, inner, n_delta) bytes, needed when gdelta or
+ * gzero_float is requested (per-block partial sums; a second small launch adds them up and applies the masks and gs).  The
+ * workspace rule of this library holds: zero before the first use, left zero by every call.
+ * HBM traffic: 12 B / element (x, g, gx), 8 B / element without gx.  Pointers need 4-byte alignment only.
+ * Errors, all reported before any launch: FP8Q_EINVAL for null or misaligned pointers, empty shapes (C or inner <= 0),
+ * n_delta not in {1, C}, a negative grad_scale_elems, gx == gdelta == gzero_float == NULL; FP8Q_EUNSUPPORTED for n_bits
+ * outside [2, 16]; FP8Q_EWORKSPACE for a missing, misaligned or too small workspace.
+ * Enqueue-only, no allocation.  FP8Q_VERSION is unchanged: the entries are additive.
+ */
+size_t fp8q_int_quantize_bwd_workspace_bytes(int64_t C, int64_t inner, int64_t n_delta);
+int fp8q_int_quantize_bwd_f32(const float *x, const float *g, float *gx, int64_t C, int64_t inner, const float *delta,
+                              const float *zero_float, int64_t n_delta, const unsigned char *signed_flag, int n_bits,
+                              int symmetric, float eps, int64_t grad_scale_elems, float *gdelta, float *gzero_float, void *ws,
+                              size_t ws_bytes, fp8q_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
