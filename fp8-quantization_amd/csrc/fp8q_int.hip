@@ -96,10 +96,7 @@ __device__ __forceinline__ Range range_of(float xmin, float xmax, bool symmetric
 
 __device__ __forceinline__ float int_one(float v, const float4 k, float lo, float hi)
 {
-    const float q0 = v * k.y;
-    float rq = rintf(q0);
-    if (fabsf(q0 - rq) >= 0.5f - fabsf(q0) * 0x1p-20f) rq = rintf(v / k.x);
-    const float t = t_clamp(rq + k.z, lo, hi);
+    const float t = int_level(v, k, lo, hi);
     return k.x * (t - k.z);
 }
 

@@ -1,0 +1,386 @@
+// fp8q_intcodec.hip -- the storage form of the uniform (INT) quantizers: the integers themselves.
+//
+// Extends the arithmetic contract at the top of fp8q_int.hip (scale, zp, int_min, int_max exactly as consts_of() and
+// k_int_quant form them, the symmetric sign read from device memory):
+//   t = clamp(rint(x / scale) + zp, int_min, int_max)      int_level(), fp8q_intq.h: fp32, every op rounded on its own
+//   to_integer  t as float32.  NaN stays NaN; -0 + zp is what fp32 gives.  A zero level is stored as +0, as the CUDA chain
+//               stores it: the only -0 the formula can yield is clamp(-0 + -0, 0, hi) of an asymmetric range whose
+//               zero_float is -0 (x_min >= +0), and torch's CUDA clamp computes max(-0, +0), which is +0 on the GPU
+//               (its CPU clamp keeps the -0: the one place where the two torch chains differ here).
+//   encode      t as an integer: one byte for n_bits <= 8, two bytes (little endian) for 9..16, the two's-complement low
+//               bits of t -- unsigned ranges store 0 .. 2^n - 1, the signed symmetric range -2^(n-1) .. 2^(n-1) - 1.
+//               NaN has no code: it stores the code of the value 0, which is zp (asymmetric) or 0 (symmetric), as the FP8
+//               encoder stores 0; a channel whose zp is NaN itself (zero_float NaN) stores 0.
+//   decode      y = scale * (float(code) - zp), the code read as signed exactly when the quantizer is symmetric and its
+//               device sign flag is set.
+// Consequences:
+//   decode(encode(x)) == fp8q_int_quantize_f32(x) bit for bit on every element whose x is not NaN, +-inf inputs and
+//   channels with delta 0 / inf / NaN included: both run the same last two operations on the same exactly representable
+//   integer (the sign of a zero t does not reach y: t - zp is +0 whenever they are equal).
+//   encode(x) == to_integer(x) cast to the storage type wherever to_integer(x) is not NaN.
+//   to_integer(x) == the eager to_integer_forward chain bit for bit on the same range buffers.
+//
+// Kernels -- k_int_quant's geometry: one aligned 4096-element chunk per block, the channel constants {scale, 1/scale, zp}
+// of the rows overlapping the chunk built once per block in LDS, the channel of an element from the magic division:
+//   k_int_encode<W, PC, VEC, NT>  the wide side is the LOAD: a lane owns 16 (W = 1) or 8 (W = 2) consecutive elements,
+//                 issues its four 16-byte loads before any arithmetic and stores the codes as ONE 16-byte word.
+//   k_int_decode<W, PC, VEC, NT>  the wide side is the STORE (the FP8 decoder's mapping): lane <-> 4-element group, one
+//                 4-byte (W = 1) or 8-byte (W = 2) word of codes per group, whole aligned 16-byte fp32 stores.
+//   k_int_level<PC, VEC, NT>      k_int_quant's streaming, storing t.
+// VEC needs both sides aligned to their vector word (host check); anything else, and the ragged tail of the last chunk,
+// goes element by element.  One launch per call, no workspace, nothing read back.
+// HBM traffic: encode / decode 5 B per element (6 B with 2-byte codes), to_integer 8 B.
+#include "fp8q_common.h"
+#include "fp8q_intq.h"
+
+namespace {
+
+constexpr int kIntChunk = 4096;       // elements per block, as fp8q_int.hip
+
+typedef uint32_t vu4 __attribute__((ext_vector_type(4)));
+typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
+
+struct CodecArgs {
+    const float *delta;
+    const float *zf;               // asymmetric
+    const unsigned char *sflag;    // symmetric: the sign
+    int64_t n;                     // elements
+    int inner;                     // row length (PC)
+    uint32_t magic;                // l / inner for l < inner + 4096 (inner < 4096)
+    int nc_max;                    // LDS entries per block
+    int symmetric;
+    float eps;
+    float n_hi_u;                  // 2^n - 1
+    float n_hi_s;                  // 2^(n-1) - 1
+    float n_lo_s;                  // -2^(n-1)
+};
+
+// what a block knows about its chunk [e0, e1)
+struct Chunk {
+    const float4 *kc;
+    float4 k0;
+    float lo, hi;
+    int phase, inner;
+    uint32_t magic;
+    bool sgn;
+
+    // channel constants of the element at offset `off` from e0
+    template <bool PC>
+    __device__ __forceinline__ float4 at(int off) const
+    {
+        if (!PC) return k0;
+        const uint32_t l = (uint32_t)(phase + off);
+        const int ch = inner >= kIntChunk ? (int)(l >= (uint32_t)inner) : div_small(l, magic);
+        return kc[ch];
+    }
+};
+
+template <bool PC>
+__device__ __forceinline__ Chunk chunk_setup(const CodecArgs &a, float4 *kc, int64_t e0, int64_t e1)
+{
+    __shared__ int s_sign;
+    const int tid = threadIdx.x;
+    Chunk c;
+    c.sgn = false;
+    if (a.symmetric) {
+        if (tid == 0) s_sign = a.sflag[0] != 0;
+        __syncthreads();
+        c.sgn = s_sign != 0;
+    }
+    c.lo = c.sgn ? a.n_lo_s : 0.0f;
+    c.hi = c.sgn ? a.n_hi_s : a.n_hi_u;
+    const int64_t c_lo = PC ? e0 / a.inner : 0;
+    c.phase = PC ? (int)(e0 - c_lo * a.inner) : 0;
+    c.inner = a.inner;
+    c.magic = a.magic;
+    const int nc = PC ? (int)((e1 - 1) / a.inner - c_lo) + 1 : 1;
+    for (int i = tid; i < nc; i += kBlock)
+        kc[i] = consts_of(a.delta[c_lo + i], a.symmetric ? 0.0f : a.zf[c_lo + i], a.symmetric, c.lo, c.hi, a.eps);
+    __syncthreads();
+    c.kc = kc;
+    c.k0 = kc[0];
+    return c;
+}
+
+// the two's-complement bits of an element's level (the caller keeps the low 8 or 16)
+__device__ __forceinline__ uint32_t code_of(float v, const float4 k, float lo, float hi)
+{
+    float t = int_level(v, k, lo, hi);
+    t = (t != t) ? k.z : t;
+    t = (t != t) ? 0.0f : t;
+    return (uint32_t)(int)t;      // an integer in [-32768, 65535]: the conversion is exact
+}
+
+template <int W>
+__device__ __forceinline__ float value_of(uint32_t code, bool sgn, const float4 k)
+{
+    const int iv = sgn ? (W == 1 ? (int)(int8_t)code : (int)(int16_t)code) : (int)code;
+    return k.x * ((float)iv - k.z);
+}
+
+template <bool NT, typename V>
+__device__ __forceinline__ V ldv(const V *p)
+{
+    return NT ? __builtin_nontemporal_load(p) : *p;
+}
+
+template <bool NT, typename V>
+__device__ __forceinline__ void stv(V *p, V v)
+{
+    if (NT)
+        __builtin_nontemporal_store(v, p);
+    else
+        *p = v;
+}
+
+// a code, and the word of a 4-element group's codes
+template <int W>
+struct CodeType {
+    typedef uint8_t type;
+    typedef uint32_t word;
+};
+template <>
+struct CodeType<2> {
+    typedef uint16_t type;
+    typedef vu2 word;
+};
+
+template <int W, bool PC, bool VEC, bool NT>
+__global__ void __launch_bounds__(kBlock)
+k_int_encode(const void *__restrict__ in, void *__restrict__ codes, CodecArgs a)
+{
+    typedef typename CodeType<W>::type code_t;
+    const float *__restrict__ x = static_cast<const float *>(in);
+    constexpr uint32_t kMask = W == 1 ? 0xffu : 0xffffu;
+    extern __shared__ float4 kc[];
+    const int tid = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * kIntChunk;
+    const int64_t e1 = e0 + kIntChunk < a.n ? e0 + kIntChunk : a.n;
+    const Chunk c = chunk_setup<PC>(a, kc, e0, e1);
+    code_t *out = static_cast<code_t *>(codes);
+    int64_t tail = e0;
+    if (VEC) {
+        // x and codes 16-byte aligned, e0 a multiple of 4096: a group is EPG elements = LPG loads = one 16-byte code word
+        constexpr int EPG = 16 / W, LPG = EPG / 4, GPL = kIntChunk / EPG / kBlock;
+        const int ngroups = (int)((e1 - e0) / EPG);
+        const vf4 *xv = reinterpret_cast<const vf4 *>(x + e0);
+        vu4 *cv = reinterpret_cast<vu4 *>(out + e0);
+        auto pack = [&](const vf4 *v, int off) -> vu4 {
+            uint32_t q[EPG];
+#pragma unroll
+            for (int j = 0; j < LPG; ++j) {
+                q[4 * j] = code_of(v[j].x, c.at<PC>(off + 4 * j), c.lo, c.hi) & kMask;
+                q[4 * j + 1] = code_of(v[j].y, c.at<PC>(off + 4 * j + 1), c.lo, c.hi) & kMask;
+                q[4 * j + 2] = code_of(v[j].z, c.at<PC>(off + 4 * j + 2), c.lo, c.hi) & kMask;
+                q[4 * j + 3] = code_of(v[j].w, c.at<PC>(off + 4 * j + 3), c.lo, c.hi) & kMask;
+            }
+            uint32_t w[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if constexpr (W == 1)
+                    w[j] = q[4 * j] | (q[4 * j + 1] << 8) | (q[4 * j + 2] << 16) | (q[4 * j + 3] << 24);
+                else
+                    w[j] = q[2 * j] | (q[2 * j + 1] << 16);
+            }
+            return vu4{w[0], w[1], w[2], w[3]};
+        };
+        if (ngroups == kIntChunk / EPG) {
+            vf4 v[GPL * LPG];
+#pragma unroll
+            for (int u = 0; u < GPL; ++u)
+#pragma unroll
+                for (int j = 0; j < LPG; ++j) v[u * LPG + j] = ldv<NT>(xv + (u * kBlock + tid) * LPG + j);
+#pragma unroll
+            for (int u = 0; u < GPL; ++u) stv<NT>(cv + u * kBlock + tid, pack(v + u * LPG, (u * kBlock + tid) * EPG));
+        } else {
+            for (int g = tid; g < ngroups; g += kBlock) {
+                vf4 v[LPG];
+#pragma unroll
+                for (int j = 0; j < LPG; ++j) v[j] = ldv<NT>(xv + g * LPG + j);
+                stv<NT>(cv + g, pack(v, g * EPG));
+            }
+        }
+        tail = e0 + (int64_t)ngroups * EPG;
+    }
+    for (int64_t e = tail + tid; e < e1; e += kBlock)
+        out[e] = (code_t)code_of(x[e], c.at<PC>((int)(e - e0)), c.lo, c.hi);
+}
+
+template <int W, bool PC, bool VEC, bool NT>
+__global__ void __launch_bounds__(kBlock)
+k_int_decode(const void *__restrict__ codes, void *__restrict__ out, CodecArgs a)
+{
+    float *__restrict__ y = static_cast<float *>(out);
+    typedef typename CodeType<W>::type code_t;
+    extern __shared__ float4 kc[];
+    const int tid = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * kIntChunk;
+    const int64_t e1 = e0 + kIntChunk < a.n ? e0 + kIntChunk : a.n;
+    const Chunk c = chunk_setup<PC>(a, kc, e0, e1);
+    const code_t *in = static_cast<const code_t *>(codes);
+    int64_t tail = e0;
+    if (VEC) {
+        // y 16-byte aligned, codes aligned to a group's word (4 W bytes), e0 a multiple of 4096
+        typedef typename CodeType<W>::word word_t;
+        const int ngroups = (int)((e1 - e0) >> 2);
+        const word_t *cw = reinterpret_cast<const word_t *>(in + e0);
+        vf4 *yv = reinterpret_cast<vf4 *>(y + e0);
+        auto unpack = [&](const word_t w, int off) -> vf4 {
+            uint32_t q[4];
+            if constexpr (W == 1) {
+                q[0] = w & 255u;
+                q[1] = (w >> 8) & 255u;
+                q[2] = (w >> 16) & 255u;
+                q[3] = w >> 24;
+            } else {
+                q[0] = w.x & 65535u;
+                q[1] = w.x >> 16;
+                q[2] = w.y & 65535u;
+                q[3] = w.y >> 16;
+            }
+            return vf4{value_of<W>(q[0], c.sgn, c.at<PC>(off)), value_of<W>(q[1], c.sgn, c.at<PC>(off + 1)),
+                       value_of<W>(q[2], c.sgn, c.at<PC>(off + 2)), value_of<W>(q[3], c.sgn, c.at<PC>(off + 3))};
+        };
+        if (ngroups == kIntChunk / 4) {
+            word_t w[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) w[u] = ldv<NT>(cw + u * kBlock + tid);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) st16<NT>(yv + u * kBlock + tid, unpack(w[u], 4 * (u * kBlock + tid)));
+        } else {
+            for (int g = tid; g < ngroups; g += kBlock) st16<NT>(yv + g, unpack(ldv<NT>(cw + g), 4 * g));
+        }
+        tail = e0 + 4 * (int64_t)ngroups;
+    }
+    for (int64_t e = tail + tid; e < e1; e += kBlock) y[e] = value_of<W>(in[e], c.sgn, c.at<PC>((int)(e - e0)));
+}
+
+// to_integer's element: the level, a zero as +0 (see the contract above; x + 0 changes nothing else, NaN included)
+__device__ __forceinline__ float level_of(float v, const float4 k, float lo, float hi)
+{
+    return int_level(v, k, lo, hi) + 0.0f;
+}
+
+template <bool PC, bool VEC, bool NT>
+__global__ void __launch_bounds__(kBlock)
+k_int_level(const void *__restrict__ in, void *__restrict__ out, CodecArgs a)
+{
+    const float *__restrict__ x = static_cast<const float *>(in);
+    float *__restrict__ t = static_cast<float *>(out);
+    extern __shared__ float4 kc[];
+    const int tid = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * kIntChunk;
+    const int64_t e1 = e0 + kIntChunk < a.n ? e0 + kIntChunk : a.n;
+    const Chunk c = chunk_setup<PC>(a, kc, e0, e1);
+    int64_t tail = e0;
+    if (VEC) {
+        // x and t 16-byte aligned, e0 a multiple of 4096: groups of 4 are aligned
+        const int ngroups = (int)((e1 - e0) >> 2);
+        const vf4 *xv = reinterpret_cast<const vf4 *>(x + e0);
+        vf4 *tv = reinterpret_cast<vf4 *>(t + e0);
+        auto level4 = [&](const vf4 v, int off) -> vf4 {
+            return vf4{level_of(v.x, c.at<PC>(off), c.lo, c.hi), level_of(v.y, c.at<PC>(off + 1), c.lo, c.hi),
+                       level_of(v.z, c.at<PC>(off + 2), c.lo, c.hi), level_of(v.w, c.at<PC>(off + 3), c.lo, c.hi)};
+        };
+        if (ngroups == kIntChunk / 4) {
+            vf4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = ld16<NT>(xv + u * kBlock + tid);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) st16<NT>(tv + u * kBlock + tid, level4(v[u], 4 * (u * kBlock + tid)));
+        } else {
+            for (int g = tid; g < ngroups; g += kBlock) st16<NT>(tv + g, level4(ld16<NT>(xv + g), 4 * g));
+        }
+        tail = e0 + 4 * (int64_t)ngroups;
+    }
+    for (int64_t e = tail + tid; e < e1; e += kBlock) t[e] = level_of(x[e], c.at<PC>((int)(e - e0)), c.lo, c.hi);
+}
+
+enum { kEncode, kDecode, kLevel };
+
+// argument checks (those of fp8q_int_quantize_f32) and the one launch; `in` / `out`: x -> codes, codes -> y, x -> t
+int codec_launch(int mode, const void *in, void *out, int64_t C, int64_t inner, const float *delta,
+                 const float *zero_float, int64_t n_delta, const unsigned char *signed_flag, int n_bits, int symmetric,
+                 float eps, hipStream_t st)
+{
+    if (!in || !out || C <= 0 || inner <= 0 || (n_delta != 1 && n_delta != C)) return FP8Q_EINVAL;
+    if ((n_delta > 1 && inner > INT32_MAX) || C > INT64_MAX / inner || cdiv(C * inner, kIntChunk) > (int64_t)UINT32_MAX)
+        return FP8Q_EINVAL;
+    if (!delta || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
+    if (n_bits < 2 || n_bits > 16) return FP8Q_EUNSUPPORTED;
+    const int W = n_bits <= 8 ? 1 : 2;
+    const uintptr_t pin = (uintptr_t)in, pout = (uintptr_t)out;
+    if (((mode == kDecode ? pout : pin) & 3) || (mode == kLevel && (pout & 3))) return FP8Q_EINVAL;   // fp32 sides
+    if (mode != kLevel && ((mode == kEncode ? pout : pin) & (uintptr_t)(W - 1))) return FP8Q_EINVAL;   // codes
+    const bool pc = n_delta > 1;
+    CodecArgs a;
+    a.delta = delta;
+    a.zf = zero_float;
+    a.sflag = signed_flag;
+    a.n = C * inner;
+    a.inner = pc ? (int)inner : 1;
+    a.magic = pc ? magic_of((int)inner) : 0u;
+    a.nc_max = pc ? (int)(kIntChunk / inner + 2 < C ? kIntChunk / inner + 2 : C) : 1;
+    a.symmetric = symmetric != 0;
+    a.eps = eps;
+    a.n_hi_u = ldexpf(1.0f, n_bits) - 1.0f;
+    a.n_hi_s = ldexpf(1.0f, n_bits - 1) - 1.0f;
+    a.n_lo_s = -ldexpf(1.0f, n_bits - 1);
+    const dim3 g((unsigned)cdiv(a.n, kIntChunk)), b(kBlock);
+    const size_t shmem = (size_t)a.nc_max * sizeof(float4);
+    const bool nt = a.n * 4 >= kNtBytes;
+    // both sides on their vector word: 16 bytes, or (decode) a group's 4 W bytes of codes
+    const bool vec = mode == kDecode ? ((pout & 15) == 0 && (pin & (uintptr_t)(4 * W - 1)) == 0) : ((pin | pout) & 15) == 0;
+#define FP8Q_CODEC_LAUNCH(K, ...)                                                                                     \
+    do {                                                                                                              \
+        if (vec && nt) hipLaunchKernelGGL((K<__VA_ARGS__, true, true>), g, b, shmem, st, in, out, a);               \
+        else if (vec) hipLaunchKernelGGL((K<__VA_ARGS__, true, false>), g, b, shmem, st, in, out, a);               \
+        else hipLaunchKernelGGL((K<__VA_ARGS__, false, false>), g, b, shmem, st, in, out, a);                       \
+    } while (0)
+    if (mode == kLevel) {
+        if (pc) FP8Q_CODEC_LAUNCH(k_int_level, true);
+        else FP8Q_CODEC_LAUNCH(k_int_level, false);
+    } else if (mode == kEncode) {
+        if (W == 1 && pc) FP8Q_CODEC_LAUNCH(k_int_encode, 1, true);
+        else if (W == 1) FP8Q_CODEC_LAUNCH(k_int_encode, 1, false);
+        else if (pc) FP8Q_CODEC_LAUNCH(k_int_encode, 2, true);
+        else FP8Q_CODEC_LAUNCH(k_int_encode, 2, false);
+    } else {
+        if (W == 1 && pc) FP8Q_CODEC_LAUNCH(k_int_decode, 1, true);
+        else if (W == 1) FP8Q_CODEC_LAUNCH(k_int_decode, 1, false);
+        else if (pc) FP8Q_CODEC_LAUNCH(k_int_decode, 2, true);
+        else FP8Q_CODEC_LAUNCH(k_int_decode, 2, false);
+    }
+#undef FP8Q_CODEC_LAUNCH
+    return launch_rc();
+}
+
+}  // namespace
+
+extern "C" {
+
+int fp8q_int_to_integer_f32(const float *x, float *t, int64_t C, int64_t inner, const float *delta,
+                            const float *zero_float, int64_t n_delta, const unsigned char *signed_flag, int n_bits,
+                            int symmetric, float eps, fp8q_stream_t stream)
+{
+    return codec_launch(kLevel, x, t, C, inner, delta, zero_float, n_delta, signed_flag, n_bits, symmetric, eps,
+                        (hipStream_t)stream);
+}
+
+int fp8q_int_encode(const float *x, void *codes, int64_t C, int64_t inner, const float *delta, const float *zero_float,
+                    int64_t n_delta, const unsigned char *signed_flag, int n_bits, int symmetric, float eps,
+                    fp8q_stream_t stream)
+{
+    return codec_launch(kEncode, x, codes, C, inner, delta, zero_float, n_delta, signed_flag, n_bits, symmetric, eps,
+                        (hipStream_t)stream);
+}
+
+int fp8q_int_decode(const void *codes, float *y, int64_t C, int64_t inner, const float *delta, const float *zero_float,
+                    int64_t n_delta, const unsigned char *signed_flag, int n_bits, int symmetric, float eps,
+                    fp8q_stream_t stream)
+{
+    return codec_launch(kDecode, codes, y, C, inner, delta, zero_float, n_delta, signed_flag, n_bits, symmetric, eps,
+                        (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -676,10 +676,11 @@ def _int_ptrs(x, delta, zero_float, signed_flag, symmetric, n):
             signed_flag.data_ptr() if symmetric else None)
 
 
-def _int_x(x, out, n_range):
+def _int_x(x, out, n_range, out_dtype=None):
     """(x as the kernel reads it, y, C, inner, result): per tensor on a dense non-contiguous layout the storage as it
-    lies (the result keeps x's strides, as the elementwise ATen chain does); otherwise a contiguous [C, inner] view."""
-    flat = _dense_flat(x) if (n_range == 1 and out is None) else None
+    lies (the result keeps x's strides, as the elementwise ATen chain does); otherwise a contiguous [C, inner] view.
+    out_dtype: the result's dtype when it is not x's (integer codes: always the contiguous view, codes are storage)."""
+    flat = _dense_flat(x) if (n_range == 1 and out is None and out_dtype is None) else None
     if flat is not None:
         res = torch.empty_like(x)
         flat_out = _dense_flat(res) if res.stride() == x.stride() else None
@@ -689,7 +690,7 @@ def _int_x(x, out, n_range):
     C, inner = _rows(x, n_range != 1)
     if n_range != 1 and n_range != C:
         raise Fp8qError(f"the range has {n_range} elements, expected 1 or {C}")
-    y = _out(out, x)
+    y = _out(out, x, out_dtype)
     return x, y, C, inner, y
 
 
@@ -711,6 +712,56 @@ def int_quantize(x, delta, zero_float=None, signed_flag=None, n_bits=8, symmetri
                                          int(bool(symmetric)), float(eps), _stream(xk))
     check(rc, "fp8q_int_quantize_f32")
     return res
+
+
+def _int_code_dtype(n_bits):
+    """storage dtype of the INT codes: one byte up to 8 bits, two from 9 to 16 (raw two's-complement bits)"""
+    return torch.uint8 if int(n_bits) <= 8 else torch.int16
+
+
+def _int_codec(fn, x, in_dtype, out_dtype, delta, zero_float, signed_flag, n_bits, symmetric, eps, out):
+    """The launch shared by int_to_integer / int_encode / int_decode: int_quantize's checks, one kernel."""
+    _require(x, "codes" if in_dtype is not torch.float32 else "x", in_dtype)
+    delta = delta.detach().reshape(-1)
+    n = delta.numel()
+    zero_float = zero_float.detach().reshape(-1) if zero_float is not None else None
+    signed_flag = signed_flag.detach().reshape(-1) if signed_flag is not None else None
+    pd, pz, ps = _int_ptrs(x, delta, zero_float, signed_flag, symmetric, n)
+    xk, y, C, inner, res = _int_x(x, out, n, None if out_dtype is in_dtype else out_dtype)
+    if xk.numel() == 0:
+        return res
+    with _on_device(xk):
+        rc = getattr(lib(), fn)(xk.data_ptr(), y.data_ptr(), C, inner, pd, pz, n, ps, int(n_bits), int(bool(symmetric)),
+                                float(eps), _stream(xk))
+    check(rc, fn)
+    return res
+
+
+def int_to_integer(x, delta, zero_float=None, signed_flag=None, n_bits=8, symmetric=False, eps=1e-8, out=None):
+    """The integer grid of int_quantize as float32 (uniform_quantizers.py to_integer_forward, linear scale domain):
+    t = clamp(rint(x / scale) + zp, int_min, int_max), bit for bit the eager CUDA chain; NaN stays NaN, a zero level is +0
+    (torch's CPU clamp keeps the -0 that -0 + -0 gives when zero_float is -0; its CUDA clamp does not).  Arguments as
+    int_quantize.  One launch."""
+    return _int_codec("fp8q_int_to_integer_f32", x, torch.float32, torch.float32, delta, zero_float, signed_flag, n_bits,
+                      symmetric, eps, out)
+
+
+def int_encode(x, delta, zero_float=None, signed_flag=None, n_bits=8, symmetric=False, eps=1e-8, out=None):
+    """The integers of int_quantize as storage codes, contiguous and shaped like x: torch.uint8 for n_bits <= 8, torch.int16
+    for 9..16.  These are RAW two's-complement bits: `.view(torch.int8)` gives the integers of a signed symmetric quantizer
+    (its codes of -2^(n-1) .. -1 read as 256 - |t| through uint8), and UNSIGNED 16-bit codes of 32768 and above read as
+    negative numbers through int16 (add 65536, or widen and mask with 0xffff).  NaN inputs store the code of the value 0
+    (zp, or 0 when symmetric).  int_decode(int_encode(x)) == int_quantize(x) bit for bit wherever x is not NaN.
+    Arguments as int_quantize.  One launch."""
+    return _int_codec("fp8q_int_encode", x, torch.float32, _int_code_dtype(n_bits), delta, zero_float, signed_flag, n_bits,
+                      symmetric, eps, out)
+
+
+def int_decode(codes, delta, zero_float=None, signed_flag=None, n_bits=8, symmetric=False, eps=1e-8, out=None):
+    """float32 values of int_encode's codes (uint8 for n_bits <= 8, int16 for 9..16): y = scale * (code - zp), the code read
+    as signed exactly when the quantizer is symmetric and its device sign flag is set.  One launch."""
+    return _int_codec("fp8q_int_decode", codes, _int_code_dtype(n_bits), torch.float32, delta, zero_float, signed_flag,
+                      n_bits, symmetric, eps, out)
 
 
 def int_quantize_backward(x, g, delta, zero_float=None, signed_flag=None, n_bits=8, symmetric=False, eps=1e-8, need_gx=True,

@@ -22,7 +22,7 @@ ALIASES = {
     "autoquant_utils": "layers",                           # Quant* / BNQ* layers, quantize_model, fold_bn ...
     "quantized_folded_bn": "layers",                       # BNFusedHijacker
     "base_quantized_classes": "layers",                    # QuantizedModule, QuantizedActivation, FP32Acts
-    "base_quantized_model": "model",                       # QuantizedModel (+ range checkpointing, graphs, FP8 export)
+    "base_quantized_model": "model",                       # QuantizedModel (+ range checkpointing, graphs, FP8 / INT export)
     "quantization_manager": "manager",                     # QuantizationManager, Qstates, QMethods
     "range_estimators": "estimators",                      # the estimators, RangeEstimators, LineSearchEstimator
     "quant_error_estimator": "quant_error",                # compute_expected_quant_mse ...

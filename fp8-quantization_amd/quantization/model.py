@@ -248,6 +248,46 @@ def decode_fp8_weights(exported, device="cuda"):
                                   e["sign_bits"]) for name, e in exported.items()}
 
 
+def export_int_weights(model):
+    """{layer name: {codes, delta, zero_float or None, signed or None, n_bits, symmetric, eps}} for every layer whose
+    weights go through a uniform (INT) quantizer with fixed ranges -- the twin of export_fp8_weights: the integers the
+    layer's quantized weight stands for (uint8 up to 8 bits, int16 beyond: raw two's-complement bits, see
+    fp8q.ops.int_encode) with the ranges that turn them back, all as CPU tensors.  decode(codes) == the layer's quantized
+    weight bit for bit.  The symmetric sign flag is copied to the host here, once per layer; the kernels never do."""
+    from .layers import QuantizationHijacker
+    from .manager import Qstates
+    from .uniform import AsymmetricUniformQuantizer
+    out = {}
+    for name, m in model.named_modules():
+        if not isinstance(m, QuantizationHijacker) or not getattr(m, "_qw", False):
+            continue
+        if type(m).quantize_weights is not QuantizationHijacker.quantize_weights:
+            continue
+        mgr = m.weight_quantizer
+        q = getattr(mgr, "quantizer", None)
+        if not isinstance(q, AsymmetricUniformQuantizer) or mgr.state != Qstates.fix_ranges or not q.is_initialized:
+            continue
+        w = m.get_weight_bias()[0].detach()
+        if not w.is_cuda:
+            continue
+        codes = q.encode(w.contiguous())
+        out[name] = dict(codes=codes.cpu(), delta=q._delta.detach().reshape(-1).cpu(),
+                         zero_float=None if q.symmetric else q._zero_float.detach().reshape(-1).cpu(),
+                         signed=q._signed.detach().reshape(-1).cpu() if q.symmetric else None,
+                         n_bits=int(q.n_bits), symmetric=bool(q.symmetric), eps=float(q.eps))
+    return out
+
+
+def decode_int_weights(exported, device="cuda"):
+    """{layer name: fp32 tensor} from export_int_weights(): the values the layers compute with."""
+    import fp8q
+
+    def dev(t):
+        return None if t is None else t.to(device)
+    return {name: fp8q.ops.int_decode(e["codes"].to(device), dev(e["delta"]), dev(e["zero_float"]), dev(e["signed"]),
+                                      e["n_bits"], e["symmetric"], e["eps"]) for name, e in exported.items()}
+
+
 class GraphedForward:
     """HIP graph of `model(x)` for one input shape.  With FIXED ranges nothing in a quantized forward is decided on
     the host (the engine's entry points only enqueue kernels on the current stream), so the whole forward can be

@@ -7,6 +7,10 @@ device memory: no host round trip).  Under autograd -- x or a learned range (`ma
 d/ddelta and d/dzero_float, LSQ's `grad_scaling` included.  Everything else -- CPU, other dtypes, the log domain, a custom
 discretizer -- is the reference's torch op chain.  FP8Q_INT_KERNELS=0 forces that chain, FP8Q_GRAD_KERNELS=0 forces it
 under autograd only (the switch of the FP quantizer's backward).
+
+The integers themselves (csrc/fp8q_intcodec.hip): `to_integer_forward` runs fp8q.ops.int_to_integer under forward's kernel
+conditions and stays the torch chain otherwise; `encode` / `decode` give and take the 1- or 2-byte storage codes and exist on
+the kernel path only (they raise elsewhere, FP8Q_INT_KERNELS=0 included).
 """
 import os
 
@@ -277,9 +281,39 @@ class AsymmetricUniformQuantizer(QuantizerBase):
                 zp = scale_grad_func(zp, gs)
         return scale, zp
 
+    def _fixed_kernel_ok(self, t, x_like=True):
+        """forward's conditions for ops.int_quantize: kernels on, fixed fp32 range buffers on t's device, and (x_like) t a
+        CUDA fp32 tensor nothing wants a gradient of, shaped for the range."""
+        d = self._delta
+        return (d is not None and isinstance(t, torch.Tensor) and self._kernel_common(t.device)
+                and self._kernel_buffers_ok(t.device) and (not x_like or self._kernel_x_ok(t, d.numel())))
+
+    def _range_args(self):
+        return (self._delta, None if self.symmetric else self._zero_float, self._signed if self.symmetric else None,
+                self.n_bits, self.symmetric, self.eps)
+
     def to_integer_forward(self, x_float, *args, **kwargs):
+        if self._fixed_kernel_ok(x_float):
+            return _ops.int_to_integer(x_float, *self._range_args())
         scale, zp = self._chain_params(x_float)
         return torch.clamp(self.discretizer(x_float / scale) + zp, self.int_min, self.int_max)
+
+    def encode(self, x_float):
+        """The integers of forward(x) as storage codes (fp8q.ops.int_encode: uint8 up to 8 bits, int16 beyond, raw
+        two's-complement bits).  Kernel path only -- the conditions of forward's; anything else raises."""
+        if not self._fixed_kernel_ok(x_float):
+            raise _ops.Fp8qError("encode needs the INT kernels: a CUDA float32 tensor without a gradient, fixed float32 range "
+                                 "buffers on its device, the linear scale domain, and FP8Q_INT_KERNELS not 0")
+        return _ops.int_encode(x_float, *self._range_args())
+
+    def decode(self, codes):
+        """float32 values of encode()'s codes: decode(encode(x)) == forward(x) bit for bit wherever x is not NaN."""
+        d = self._delta
+        if not (self._fixed_kernel_ok(codes, x_like=False) and codes.is_cuda and not codes.is_floating_point()
+                and (d.numel() == 1 or (self.per_channel and codes.dim() > 0 and codes.shape[0] == d.numel()))):
+            raise _ops.Fp8qError("decode needs the INT kernels: CUDA integer codes, fixed float32 range buffers on their "
+                                 "device, the linear scale domain, and FP8Q_INT_KERNELS not 0")
+        return _ops.int_decode(codes, *self._range_args())
 
     def forward(self, x_float, *args, **kwargs):
         d = self._delta

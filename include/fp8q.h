@@ -485,6 +485,40 @@ int fp8q_int_minmax_quantize_f32(const float *x, float *y, int64_t C, int64_t in
                                  float eps, void *ws, size_t ws_bytes, fp8q_stream_t stream);
 
 /*
+ * Integer codes of the uniform (INT) quantizers (csrc/fp8q_intcodec.hip): the storage form of the lane above, and the
+ * reference's to_integer_forward (uniform_quantizers.py:108-133).  With scale, zp, int_min, int_max as above (the symmetric
+ * sign read from signed_flag[0] on the device):
+ *   t = clamp(rint(x / scale) + zp, int_min, int_max)      in fp32, every op rounded on its own
+ *   fp8q_int_to_integer_f32   t as float32.  NaN stays NaN.  A zero level is +0, as torch's CUDA chain gives it (its clamp
+ *                             turns the -0 of -0 + -0, possible only with a zero_float of -0, into +0; the CPU clamp keeps it).
+ *   fp8q_int_encode           t as an integer: ONE byte per element for n_bits <= 8, TWO bytes (little endian) for 9..16,
+ *                             holding the two's-complement low bits of t: unsigned ranges store 0 .. 2^n - 1, the signed
+ *                             symmetric range -2^(n-1) .. 2^(n-1) - 1.  NaN has no code: it stores the code of the value 0,
+ *                             which is zp (asymmetric) or 0 (symmetric), as fp8q_encode_u8 stores 0; a channel whose zp is
+ *                             itself NaN (a NaN zero_float) stores 0.
+ *   fp8q_int_decode           y = scale * (float(code) - zp); the code is read as signed exactly when the quantizer is
+ *                             symmetric and signed_flag[0] is non-zero.
+ * decode of encode equals fp8q_int_quantize_f32 bit for bit on every element whose x is not NaN -- +-inf inputs and channels
+ * whose delta is 0, inf or NaN included: both sides run the same last two operations on the same exactly representable
+ * integer.  encode equals to_integer cast to the storage type wherever to_integer is not NaN.  to_integer equals the eager
+ * to_integer_forward chain bit for bit on the same range buffers.
+ * Arguments and error codes as fp8q_int_quantize_f32: FP8Q_EINVAL for null pointers, empty shapes, n_delta not in {1, C};
+ * FP8Q_EUNSUPPORTED for n_bits outside [2, 16].  codes [C, inner] must be aligned to its element size (FP8Q_EINVAL); the
+ * 16-byte paths need x / y and codes 16-byte aligned (decode: codes aligned to 4 elements), other alignments go element by
+ * element.  HBM traffic: encode and decode 5 B / element (6 B with 2-byte codes), to_integer 8 B.  One launch, no workspace,
+ * enqueue-only.
+ */
+int fp8q_int_to_integer_f32(const float *x, float *t, int64_t C, int64_t inner, const float *delta,
+                            const float *zero_float, int64_t n_delta, const unsigned char *signed_flag, int n_bits,
+                            int symmetric, float eps, fp8q_stream_t stream);
+int fp8q_int_encode(const float *x, void *codes, int64_t C, int64_t inner, const float *delta, const float *zero_float,
+                    int64_t n_delta, const unsigned char *signed_flag, int n_bits, int symmetric, float eps,
+                    fp8q_stream_t stream);
+int fp8q_int_decode(const void *codes, float *y, int64_t C, int64_t inner, const float *delta, const float *zero_float,
+                    int64_t n_delta, const unsigned char *signed_flag, int n_bits, int symmetric, float eps,
+                    fp8q_stream_t stream);
+
+/*
  * The line search of the uniform quantizers (csrc/fp8q_int.hip): LineSearchEstimator's candidates
  * (range_estimators.py:161-169, 236-256) in ONE pass over the data instead of one quantizer pass per candidate.
  *   out[k, c] += sum over row c of (x - q_k(x))^2,   k < n_cand, c < C
