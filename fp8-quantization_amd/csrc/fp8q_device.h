@@ -430,20 +430,32 @@ __device__ __forceinline__ float decode_one(uint32_t code, const float2 *lut, in
     return (sign_shift >= 0 && ((code >> sign_shift) & 1u)) ? -y : y;
 }
 
-// ---- streaming memory access: 16 B per lane, optionally nontemporal -------------------------
-template <bool NT>
-__device__ __forceinline__ vf4 ld16(const vf4 *p)
+// ---- streaming memory access: one vector word per lane (16 B: ld16 / st16), optionally nontemporal ----
+template <bool NT, typename V>
+__device__ __forceinline__ V ldv(const V *p)
 {
     return NT ? __builtin_nontemporal_load(p) : *p;
 }
 
-template <bool NT>
-__device__ __forceinline__ void st16(vf4 *p, vf4 v)
+template <bool NT, typename V>
+__device__ __forceinline__ void stv(V *p, V v)
 {
     if (NT)
         __builtin_nontemporal_store(v, p);
     else
         *p = v;
+}
+
+template <bool NT>
+__device__ __forceinline__ vf4 ld16(const vf4 *p)
+{
+    return ldv<NT>(p);
+}
+
+template <bool NT>
+__device__ __forceinline__ void st16(vf4 *p, vf4 v)
+{
+    stv<NT>(p, v);
 }
 
 template <bool NT>

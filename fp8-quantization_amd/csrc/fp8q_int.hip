@@ -30,6 +30,8 @@
 //                 {scale, 1/scale, zp} of the rows overlapping the chunk are built once per block in LDS, from
 //                 (delta, zero_float) -- or, RANGE, from (xmin, xmax), with the block in which a row starts writing
 //                 that row's delta / zero_float (and block 0 the sign): range-set and quantize in one launch.
+//                 The kernel is fp8q_intq.h's chunk_setup() + chunk_walk() with int_one as the element's operation;
+//                 the integer grid, the argument block, the sign and the launch's host side live there too.
 //   k_int_sign    the global sign of a symmetric per-channel range with more than kSignInline channels (fewer: every
 //                 block of k_int_quant / k_int_range folds it itself from the xmin vector).
 //   k_int_range   range-set alone: (xmin, xmax) -> delta, zero_float, signed.
@@ -39,45 +41,7 @@
 
 namespace {
 
-constexpr int kIntChunk = 4096;       // elements per block: 16 KiB of fp32
 constexpr int kSignInline = 2048;     // symmetric per-channel: up to here every block reduces the xmin vector itself
-
-struct IntArgs {
-    const float *a;          // delta  | RANGE: x_min
-    const float *b;          // zero_float (asymmetric) | RANGE: x_max
-    float *delta_out;        // RANGE: delta written here
-    float *zf_out;           // RANGE, asymmetric: zero_float written here
-    unsigned char *sflag;    // symmetric: the sign (read; RANGE with an inline fold: written by block 0)
-    int64_t n;               // elements
-    int64_t C;               // rows of the range vectors (1: per tensor)
-    int inner;               // row length (PC)
-    uint32_t magic;          // l / inner for l < inner + 4096 (inner < 4096)
-    int nc_max;              // LDS entries per block
-    int symmetric;
-    int sign_inline;         // RANGE + symmetric: fold the sign from the xmin vector in every block
-    float eps;
-    float n_hi_u;            // 2^n - 1
-    float n_hi_s;            // 2^(n-1) - 1
-    float n_lo_s;            // -2^(n-1)
-};
-
-// the sign of a symmetric range: no NaN in x_min and some x_min < 0 (x_min' = min(x_min, 0) has the same predicates)
-__device__ __forceinline__ bool block_sign(const float *__restrict__ xmin, int64_t C)
-{
-    int neg = 0, nan = 0;
-    for (int64_t i = threadIdx.x; i < C; i += kBlock) {
-        const float v = xmin[i];
-        neg |= v < 0.0f;
-        nan |= v != v;
-    }
-    neg = __syncthreads_or(neg);
-    nan = __syncthreads_or(nan);
-    return neg && !nan;
-}
-
-struct Range {
-    float delta, zf;
-};
 
 __device__ __forceinline__ Range range_of(float xmin, float xmax, bool symmetric, float int_max, float eps)
 {
@@ -136,14 +100,13 @@ struct IntCand {
     double s, r, zp; // float64 lane: scale and zp widened, r = 1 / scale in double
 };
 
-__device__ __forceinline__ IntCand int_cand(float thr, bool symmetric, bool one_sided, float eps, float n_hi_u,
-                                            float n_hi_s, float n_lo_s)
+__device__ __forceinline__ IntCand int_cand(float thr, bool symmetric, bool one_sided, float eps, const IntGrid &grid)
 {
     const float xmin = one_sided ? 0.0f : -thr;
     const bool sgn = symmetric && xmin < 0.0f;
     IntCand c;
-    c.lo = sgn ? n_lo_s : 0.0f;
-    c.hi = sgn ? n_hi_s : n_hi_u;
+    c.lo = grid.lo(sgn);
+    c.hi = grid.hi(sgn);
     const Range r = range_of(xmin, thr, symmetric, c.hi, eps);
     c.k = consts_of(r.delta, r.zf, symmetric, c.lo, c.hi, eps);
     c.s = (double)c.k.x;
@@ -172,7 +135,8 @@ struct IntSseArgs {
     int64_t C, inner, ntiles;
     int n_cand, nsplit, tpb;
     int symmetric, one_sided;
-    float eps, n_hi_u, n_hi_s, n_lo_s;
+    float eps;
+    IntGrid grid;
 };
 
 template <typename T>
@@ -186,7 +150,7 @@ k_int_sse(const T *__restrict__ x, const float *__restrict__ thr, double *__rest
     const int64_t c = blockIdx.z;
     const bool active = cand < a.n_cand;
     const float tv = active ? thr[(int64_t)cand * a.C + c] : 1.0f;
-    const IntCand ch = int_cand(tv, a.symmetric != 0, a.one_sided != 0, a.eps, a.n_hi_u, a.n_hi_s, a.n_lo_s);
+    const IntCand ch = int_cand(tv, a.symmetric != 0, a.one_sided != 0, a.eps, a.grid);
     const T *xr = x + c * a.inner;
     double acc = 0.0;
     const int64_t t_begin = (int64_t)split * a.tpb;
@@ -239,135 +203,34 @@ __global__ void __launch_bounds__(kBlock)
 k_int_quant(const float *__restrict__ x, float *__restrict__ y, IntArgs a)
 {
     extern __shared__ float4 kc[];    // nc_max channel constants
-    __shared__ int s_sign;
-    const int tid = threadIdx.x;
-    const int64_t e0 = (int64_t)blockIdx.x * kIntChunk;
-    const int64_t e1 = e0 + kIntChunk < a.n ? e0 + kIntChunk : a.n;
-
-    bool sgn = false;
-    if (a.symmetric) {
-        if (RANGE && a.sign_inline) {
-            sgn = PC ? block_sign(a.a, a.C) : (a.a[0] < 0.0f);
-            if (blockIdx.x == 0 && tid == 0) a.sflag[0] = (unsigned char)sgn;
-        } else {
-            if (tid == 0) s_sign = a.sflag[0] != 0;
-            __syncthreads();
-            sgn = s_sign != 0;
+    // RANGE: a row's range from (x_min, x_max); the block in whose chunk the row starts reports it
+    auto range = [&](int64_t row, bool starts, float hi) -> Range {
+        if (!RANGE) return ReadRange{a}(row, starts, hi);
+        const Range r = range_of(a.a[row], a.b[row], a.symmetric, hi, a.eps);
+        if (starts) {
+            a.delta_out[row] = r.delta;
+            if (!a.symmetric) a.zf_out[row] = r.zf;
         }
-    }
-    const float lo = sgn ? a.n_lo_s : 0.0f;
-    const float hi = (a.symmetric && sgn) ? a.n_hi_s : a.n_hi_u;
-
-    const int64_t c_lo = PC ? e0 / a.inner : 0;
-    const int phase = PC ? (int)(e0 - c_lo * a.inner) : 0;
-    const int nc = PC ? (int)((e1 - 1) / a.inner - c_lo) + 1 : 1;
-    for (int i = tid; i < nc; i += kBlock) {
-        const int64_t c = c_lo + i;
-        float delta, zf;
-        if (RANGE) {
-            const Range r = range_of(a.a[c], a.b[c], a.symmetric, hi, a.eps);
-            delta = r.delta;
-            zf = r.zf;
-            if (PC ? c * a.inner >= e0 : blockIdx.x == 0) {   // the row starts in this chunk: this block reports it
-                a.delta_out[c] = delta;
-                if (!a.symmetric) a.zf_out[c] = zf;
-            }
-        } else {
-            delta = a.a[c];
-            zf = a.symmetric ? 0.0f : a.b[c];
-        }
-        kc[i] = consts_of(delta, zf, a.symmetric, lo, hi, a.eps);
-    }
-    __syncthreads();
-    float4 k0 = kc[0];
-
-    auto chan = [&](int64_t e) -> float4 {
-        if (!PC) return k0;
-        const uint32_t l = (uint32_t)(phase + (int)(e - e0));
-        const int ch = a.inner >= kIntChunk ? (int)(l >= (uint32_t)a.inner) : div_small(l, a.magic);
-        return kc[ch];
+        return r;
     };
-
-    if (VEC) {
-        // x and y 16-byte aligned, e0 a multiple of 4096: groups of 4 are aligned
-        const int ngroups = (int)((e1 - e0) >> 2);
-        const vf4 *xv = reinterpret_cast<const vf4 *>(x + e0);
-        vf4 *yv = reinterpret_cast<vf4 *>(y + e0);
-        if (ngroups == kIntChunk / 4) {
-            vf4 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = ld16<NT>(xv + u * kBlock + tid);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int64_t e = e0 + 4 * (u * kBlock + tid);
-                vf4 o;
-                o.x = int_one(v[u].x, chan(e), lo, hi);
-                o.y = int_one(v[u].y, chan(e + 1), lo, hi);
-                o.z = int_one(v[u].z, chan(e + 2), lo, hi);
-                o.w = int_one(v[u].w, chan(e + 3), lo, hi);
-                st16<NT>(yv + u * kBlock + tid, o);
-            }
-        } else {
-            for (int g = tid; g < ngroups; g += kBlock) {
-                const vf4 w = ld16<NT>(xv + g);
-                const int64_t e = e0 + 4 * (int64_t)g;
-                vf4 o;
-                o.x = int_one(w.x, chan(e), lo, hi);
-                o.y = int_one(w.y, chan(e + 1), lo, hi);
-                o.z = int_one(w.z, chan(e + 2), lo, hi);
-                o.w = int_one(w.w, chan(e + 3), lo, hi);
-                st16<NT>(yv + g, o);
-            }
-            for (int64_t e = e0 + 4 * (int64_t)ngroups + tid; e < e1; e += kBlock)
-                y[e] = int_one(x[e], chan(e), lo, hi);
-        }
-    } else {
-        for (int64_t e = e0 + tid; e < e1; e += kBlock) y[e] = int_one(x[e], chan(e), lo, hi);
-    }
+    const Chunk c = chunk_setup<PC>(a, kc, range, RANGE && a.sign_inline);
+    chunk_walk<PC, VEC, NT, int_one>(x, y, c);
 }
 
 __global__ void __launch_bounds__(1024) k_int_sign(const float *__restrict__ xmin, int64_t C, unsigned char *sflag)
 {
-    int neg = 0, nan = 0;
-    for (int64_t i = threadIdx.x; i < C; i += 1024) {
-        const float v = xmin[i];
-        neg |= v < 0.0f;
-        nan |= v != v;
-    }
-    neg = __syncthreads_or(neg);
-    nan = __syncthreads_or(nan);
-    if (threadIdx.x == 0) sflag[0] = (unsigned char)(neg && !nan);
+    const bool sgn = block_sign(xmin, C);
+    if (threadIdx.x == 0) sflag[0] = (unsigned char)sgn;
 }
 
 __global__ void __launch_bounds__(kBlock) k_int_range(IntArgs a)
 {
-    __shared__ int s_sign;
-    bool sgn = false;
-    if (a.symmetric) {
-        if (a.sign_inline) {
-            sgn = a.C > 1 ? block_sign(a.a, a.C) : (a.a[0] < 0.0f);
-            if (blockIdx.x == 0 && threadIdx.x == 0) a.sflag[0] = (unsigned char)sgn;
-        } else {
-            if (threadIdx.x == 0) s_sign = a.sflag[0] != 0;
-            __syncthreads();
-            sgn = s_sign != 0;
-        }
-    }
-    const float hi = (a.symmetric && sgn) ? a.n_hi_s : a.n_hi_u;
+    const float hi = a.grid.hi(int_sign(a, a.sign_inline != 0, a.C > 1));
     for (int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x; c < a.C; c += (int64_t)gridDim.x * kBlock) {
         const Range r = range_of(a.a[c], a.b[c], a.symmetric, hi, a.eps);
         a.delta_out[c] = r.delta;
         if (!a.symmetric) a.zf_out[c] = r.zf;
     }
-}
-
-int int_bits(int n_bits, IntArgs &a)
-{
-    if (n_bits < 2 || n_bits > 16) return FP8Q_EUNSUPPORTED;
-    a.n_hi_u = ldexpf(1.0f, n_bits) - 1.0f;
-    a.n_hi_s = ldexpf(1.0f, n_bits - 1) - 1.0f;
-    a.n_lo_s = -ldexpf(1.0f, n_bits - 1);
-    return FP8Q_OK;
 }
 
 struct IntSseGeo {
@@ -395,13 +258,12 @@ int int_sse_grid(const T *x, int64_t C, int64_t inner, const float *thr, int64_t
     if (!x || !thr || !out || C <= 0 || inner <= 0 || n_cand <= 0 || n_cand > kIntSseMaxCand ||
         ((uintptr_t)x & (sizeof(T) - 1)) || ((uintptr_t)thr & 3) || ((uintptr_t)out & 7))
         return FP8Q_EINVAL;
-    IntArgs b = {};
-    if (int rc = int_bits(n_bits, b)) return rc;
+    IntSseArgs a;
+    if (int rc = make_int_grid(n_bits, a.grid)) return rc;
     if (C > 65535) return FP8Q_ETOOMANY;
     if (inner > INT64_MAX / C) return FP8Q_EINVAL;
     if (!ws || ((uintptr_t)ws & 7) || ws_bytes < fp8q_int_sse_grid_workspace_bytes(C, inner, n_cand)) return FP8Q_EWORKSPACE;
     const IntSseGeo g = int_sse_geo(C, inner, n_cand);
-    IntSseArgs a;
     a.C = C;
     a.inner = inner;
     a.ntiles = g.ntiles;
@@ -411,9 +273,6 @@ int int_sse_grid(const T *x, int64_t C, int64_t inner, const float *thr, int64_t
     a.symmetric = symmetric != 0;
     a.one_sided = one_sided != 0;
     a.eps = eps;
-    a.n_hi_u = b.n_hi_u;
-    a.n_hi_s = b.n_hi_s;
-    a.n_lo_s = b.n_lo_s;
     hipLaunchKernelGGL(k_int_sse<T>, dim3((unsigned)g.nsplit, (unsigned)g.cgroups, (unsigned)C), dim3(kBlock), 0, st, x, thr,
                        (double *)ws, a);
     if (int rc = launch_rc()) return rc;
@@ -423,39 +282,16 @@ int int_sse_grid(const T *x, int64_t C, int64_t inner, const float *thr, int64_t
 }
 
 // the quantize launch; `range`: a / b are (x_min, x_max) and the launch also writes delta (zero_float, sign)
-int int_quant_launch(bool range, const float *x, float *y, int64_t C, int64_t inner, bool pc, IntArgs a,
-                     hipStream_t st)
+int int_quant_launch(bool range, const float *x, float *y, int64_t C, int64_t inner, IntArgs a, hipStream_t st)
 {
-    a.n = C * inner;
-    a.inner = pc ? (int)inner : 1;
-    a.magic = pc ? magic_of((int)inner) : 0u;
-    a.nc_max = pc ? (int)(kIntChunk / inner + 2 < (int64_t)C ? kIntChunk / inner + 2 : C) : 1;
-    const int64_t nblocks = cdiv(a.n, kIntChunk);
-    const size_t shmem = (size_t)a.nc_max * sizeof(float4);
+    const bool pc = a.C > 1;
+    int_geometry(a, C, inner, pc);
     const bool vec = (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
-    const bool nt = a.n * 4 >= kNtBytes;
-    const dim3 g((unsigned)nblocks), b(kBlock);
-#define FP8Q_INT_LAUNCH(R, P)                                                                                         \
-    do {                                                                                                              \
-        if (vec && nt) hipLaunchKernelGGL((k_int_quant<R, P, true, true>), g, b, shmem, st, x, y, a);               \
-        else if (vec) hipLaunchKernelGGL((k_int_quant<R, P, true, false>), g, b, shmem, st, x, y, a);               \
-        else hipLaunchKernelGGL((k_int_quant<R, P, false, false>), g, b, shmem, st, x, y, a);                       \
-    } while (0)
-    if (range && pc) FP8Q_INT_LAUNCH(true, true);
-    else if (range) FP8Q_INT_LAUNCH(true, false);
-    else if (pc) FP8Q_INT_LAUNCH(false, true);
-    else FP8Q_INT_LAUNCH(false, false);
-#undef FP8Q_INT_LAUNCH
+    if (range && pc) FP8Q_INT_LAUNCH(vec, x, y, a, st, k_int_quant, true, true);
+    else if (range) FP8Q_INT_LAUNCH(vec, x, y, a, st, k_int_quant, true, false);
+    else if (pc) FP8Q_INT_LAUNCH(vec, x, y, a, st, k_int_quant, false, true);
+    else FP8Q_INT_LAUNCH(vec, x, y, a, st, k_int_quant, false, false);
     return launch_rc();
-}
-
-// shared argument checks of the quantize entry points
-int int_check_x(const float *x, const float *y, int64_t C, int64_t inner, int64_t n_range)
-{
-    if (!x || !y || C <= 0 || inner <= 0 || (n_range != 1 && n_range != C)) return FP8Q_EINVAL;
-    if ((n_range > 1 && inner > INT32_MAX) || C > INT64_MAX / inner || cdiv(C * inner, kIntChunk) > (int64_t)UINT32_MAX)
-        return FP8Q_EINVAL;
-    return FP8Q_OK;
 }
 
 // RANGE launches of the symmetric per-channel case: the sign first when the blocks cannot fold it themselves
@@ -478,15 +314,14 @@ int fp8q_int_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, co
     if (int rc = int_check_x(x, y, C, inner, n_delta)) return rc;
     if (!delta || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
     IntArgs a = {};
-    if (int rc = int_bits(n_bits, a)) return rc;
+    if (int rc = make_int_grid(n_bits, a.grid)) return rc;
     a.a = delta;
     a.b = zero_float;
     a.sflag = const_cast<unsigned char *>(signed_flag);   // read only (RANGE == false)
     a.C = n_delta;
     a.symmetric = symmetric != 0;
     a.eps = eps;
-    const bool pc = n_delta > 1;
-    return int_quant_launch(false, x, y, pc ? C : 1, pc ? inner : C * inner, pc, a, (hipStream_t)stream);
+    return int_quant_launch(false, x, y, C, inner, a, (hipStream_t)stream);
 }
 
 int fp8q_int_set_range_f32(const float *x_min, const float *x_max, int64_t n, float *delta, float *zero_float,
@@ -494,7 +329,7 @@ int fp8q_int_set_range_f32(const float *x_min, const float *x_max, int64_t n, fl
 {
     if (!x_min || !x_max || !delta || n <= 0 || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
     IntArgs a = {};
-    if (int rc = int_bits(n_bits, a)) return rc;
+    if (int rc = make_int_grid(n_bits, a.grid)) return rc;
     a.a = x_min;
     a.b = x_max;
     a.delta_out = delta;
@@ -518,7 +353,7 @@ int fp8q_int_range_quantize_f32(const float *x, float *y, int64_t C, int64_t inn
     if (int rc = int_check_x(x, y, C, inner, n_range)) return rc;
     if (!x_min || !x_max || !delta || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
     IntArgs a = {};
-    if (int rc = int_bits(n_bits, a)) return rc;
+    if (int rc = make_int_grid(n_bits, a.grid)) return rc;
     a.a = x_min;
     a.b = x_max;
     a.delta_out = delta;
@@ -529,8 +364,7 @@ int fp8q_int_range_quantize_f32(const float *x, float *y, int64_t C, int64_t inn
     a.eps = eps;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = int_sign_prepass(a, st)) return rc;
-    const bool pc = n_range > 1;
-    return int_quant_launch(true, x, y, pc ? C : 1, pc ? inner : C * inner, pc, a, st);
+    return int_quant_launch(true, x, y, C, inner, a, st);
 }
 
 int fp8q_int_minmax_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, float *row_min, float *row_max,
@@ -539,8 +373,8 @@ int fp8q_int_minmax_quantize_f32(const float *x, float *y, int64_t C, int64_t in
 {
     if (int rc = int_check_x(x, y, C, inner, C)) return rc;
     if (!row_min || !row_max || !delta || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
-    IntArgs probe = {};
-    if (int rc = int_bits(n_bits, probe)) return rc;
+    IntGrid probe;
+    if (int rc = make_int_grid(n_bits, probe)) return rc;
     if (int rc = fp8q_minmax_f32(x, C, inner, row_min, row_max, nullptr, FP8Q_FOLD_CURRENT, 0.0, 1, ws, ws_bytes,
                                  stream))
         return rc;

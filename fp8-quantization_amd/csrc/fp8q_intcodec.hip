@@ -21,7 +21,9 @@
 //   to_integer(x) == the eager to_integer_forward chain bit for bit on the same range buffers.
 //
 // Kernels -- k_int_quant's geometry: one aligned 4096-element chunk per block, the channel constants {scale, 1/scale, zp}
-// of the rows overlapping the chunk built once per block in LDS, the channel of an element from the magic division:
+// of the rows overlapping the chunk built once per block in LDS, the channel of an element from the magic division.  The
+// argument block, that prologue (chunk_setup), k_int_level's streaming loop (chunk_walk) and the host side of the launch
+// are fp8q_intq.h's, shared with fp8q_int.hip; encode and decode keep their own group shapes:
 //   k_int_encode<W, PC, VEC, NT>  the wide side is the LOAD: a lane owns 16 (W = 1) or 8 (W = 2) consecutive elements,
 //                 issues its four 16-byte loads before any arithmetic and stores the codes as ONE 16-byte word.
 //   k_int_decode<W, PC, VEC, NT>  the wide side is the STORE (the FP8 decoder's mapping): lane <-> 4-element group, one
@@ -35,72 +37,8 @@
 
 namespace {
 
-constexpr int kIntChunk = 4096;       // elements per block, as fp8q_int.hip
-
 typedef uint32_t vu4 __attribute__((ext_vector_type(4)));
 typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
-
-struct CodecArgs {
-    const float *delta;
-    const float *zf;               // asymmetric
-    const unsigned char *sflag;    // symmetric: the sign
-    int64_t n;                     // elements
-    int inner;                     // row length (PC)
-    uint32_t magic;                // l / inner for l < inner + 4096 (inner < 4096)
-    int nc_max;                    // LDS entries per block
-    int symmetric;
-    float eps;
-    float n_hi_u;                  // 2^n - 1
-    float n_hi_s;                  // 2^(n-1) - 1
-    float n_lo_s;                  // -2^(n-1)
-};
-
-// what a block knows about its chunk [e0, e1)
-struct Chunk {
-    const float4 *kc;
-    float4 k0;
-    float lo, hi;
-    int phase, inner;
-    uint32_t magic;
-    bool sgn;
-
-    // channel constants of the element at offset `off` from e0
-    template <bool PC>
-    __device__ __forceinline__ float4 at(int off) const
-    {
-        if (!PC) return k0;
-        const uint32_t l = (uint32_t)(phase + off);
-        const int ch = inner >= kIntChunk ? (int)(l >= (uint32_t)inner) : div_small(l, magic);
-        return kc[ch];
-    }
-};
-
-template <bool PC>
-__device__ __forceinline__ Chunk chunk_setup(const CodecArgs &a, float4 *kc, int64_t e0, int64_t e1)
-{
-    __shared__ int s_sign;
-    const int tid = threadIdx.x;
-    Chunk c;
-    c.sgn = false;
-    if (a.symmetric) {
-        if (tid == 0) s_sign = a.sflag[0] != 0;
-        __syncthreads();
-        c.sgn = s_sign != 0;
-    }
-    c.lo = c.sgn ? a.n_lo_s : 0.0f;
-    c.hi = c.sgn ? a.n_hi_s : a.n_hi_u;
-    const int64_t c_lo = PC ? e0 / a.inner : 0;
-    c.phase = PC ? (int)(e0 - c_lo * a.inner) : 0;
-    c.inner = a.inner;
-    c.magic = a.magic;
-    const int nc = PC ? (int)((e1 - 1) / a.inner - c_lo) + 1 : 1;
-    for (int i = tid; i < nc; i += kBlock)
-        kc[i] = consts_of(a.delta[c_lo + i], a.symmetric ? 0.0f : a.zf[c_lo + i], a.symmetric, c.lo, c.hi, a.eps);
-    __syncthreads();
-    c.kc = kc;
-    c.k0 = kc[0];
-    return c;
-}
 
 // the two's-complement bits of an element's level (the caller keeps the low 8 or 16)
 __device__ __forceinline__ uint32_t code_of(float v, const float4 k, float lo, float hi)
@@ -118,21 +56,6 @@ __device__ __forceinline__ float value_of(uint32_t code, bool sgn, const float4 
     return k.x * ((float)iv - k.z);
 }
 
-template <bool NT, typename V>
-__device__ __forceinline__ V ldv(const V *p)
-{
-    return NT ? __builtin_nontemporal_load(p) : *p;
-}
-
-template <bool NT, typename V>
-__device__ __forceinline__ void stv(V *p, V v)
-{
-    if (NT)
-        __builtin_nontemporal_store(v, p);
-    else
-        *p = v;
-}
-
 // a code, and the word of a 4-element group's codes
 template <int W>
 struct CodeType {
@@ -147,16 +70,15 @@ struct CodeType<2> {
 
 template <int W, bool PC, bool VEC, bool NT>
 __global__ void __launch_bounds__(kBlock)
-k_int_encode(const void *__restrict__ in, void *__restrict__ codes, CodecArgs a)
+k_int_encode(const void *__restrict__ in, void *__restrict__ codes, IntArgs a)
 {
     typedef typename CodeType<W>::type code_t;
     const float *__restrict__ x = static_cast<const float *>(in);
     constexpr uint32_t kMask = W == 1 ? 0xffu : 0xffffu;
     extern __shared__ float4 kc[];
     const int tid = threadIdx.x;
-    const int64_t e0 = (int64_t)blockIdx.x * kIntChunk;
-    const int64_t e1 = e0 + kIntChunk < a.n ? e0 + kIntChunk : a.n;
-    const Chunk c = chunk_setup<PC>(a, kc, e0, e1);
+    const Chunk c = chunk_setup<PC>(a, kc, ReadRange{a});
+    const int64_t e0 = c.e0, e1 = c.e1;
     code_t *out = static_cast<code_t *>(codes);
     int64_t tail = e0;
     if (VEC) {
@@ -208,15 +130,14 @@ k_int_encode(const void *__restrict__ in, void *__restrict__ codes, CodecArgs a)
 
 template <int W, bool PC, bool VEC, bool NT>
 __global__ void __launch_bounds__(kBlock)
-k_int_decode(const void *__restrict__ codes, void *__restrict__ out, CodecArgs a)
+k_int_decode(const void *__restrict__ codes, void *__restrict__ out, IntArgs a)
 {
     float *__restrict__ y = static_cast<float *>(out);
     typedef typename CodeType<W>::type code_t;
     extern __shared__ float4 kc[];
     const int tid = threadIdx.x;
-    const int64_t e0 = (int64_t)blockIdx.x * kIntChunk;
-    const int64_t e1 = e0 + kIntChunk < a.n ? e0 + kIntChunk : a.n;
-    const Chunk c = chunk_setup<PC>(a, kc, e0, e1);
+    const Chunk c = chunk_setup<PC>(a, kc, ReadRange{a});
+    const int64_t e0 = c.e0, e1 = c.e1;
     const code_t *in = static_cast<const code_t *>(codes);
     int64_t tail = e0;
     if (VEC) {
@@ -263,37 +184,11 @@ __device__ __forceinline__ float level_of(float v, const float4 k, float lo, flo
 
 template <bool PC, bool VEC, bool NT>
 __global__ void __launch_bounds__(kBlock)
-k_int_level(const void *__restrict__ in, void *__restrict__ out, CodecArgs a)
+k_int_level(const void *__restrict__ in, void *__restrict__ out, IntArgs a)
 {
-    const float *__restrict__ x = static_cast<const float *>(in);
-    float *__restrict__ t = static_cast<float *>(out);
     extern __shared__ float4 kc[];
-    const int tid = threadIdx.x;
-    const int64_t e0 = (int64_t)blockIdx.x * kIntChunk;
-    const int64_t e1 = e0 + kIntChunk < a.n ? e0 + kIntChunk : a.n;
-    const Chunk c = chunk_setup<PC>(a, kc, e0, e1);
-    int64_t tail = e0;
-    if (VEC) {
-        // x and t 16-byte aligned, e0 a multiple of 4096: groups of 4 are aligned
-        const int ngroups = (int)((e1 - e0) >> 2);
-        const vf4 *xv = reinterpret_cast<const vf4 *>(x + e0);
-        vf4 *tv = reinterpret_cast<vf4 *>(t + e0);
-        auto level4 = [&](const vf4 v, int off) -> vf4 {
-            return vf4{level_of(v.x, c.at<PC>(off), c.lo, c.hi), level_of(v.y, c.at<PC>(off + 1), c.lo, c.hi),
-                       level_of(v.z, c.at<PC>(off + 2), c.lo, c.hi), level_of(v.w, c.at<PC>(off + 3), c.lo, c.hi)};
-        };
-        if (ngroups == kIntChunk / 4) {
-            vf4 v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = ld16<NT>(xv + u * kBlock + tid);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) st16<NT>(tv + u * kBlock + tid, level4(v[u], 4 * (u * kBlock + tid)));
-        } else {
-            for (int g = tid; g < ngroups; g += kBlock) st16<NT>(tv + g, level4(ld16<NT>(xv + g), 4 * g));
-        }
-        tail = e0 + 4 * (int64_t)ngroups;
-    }
-    for (int64_t e = tail + tid; e < e1; e += kBlock) t[e] = level_of(x[e], c.at<PC>((int)(e - e0)), c.lo, c.hi);
+    chunk_walk<PC, VEC, NT, level_of>(static_cast<const float *>(in), static_cast<float *>(out),
+                                      chunk_setup<PC>(a, kc, ReadRange{a}));
 }
 
 enum { kEncode, kDecode, kLevel };
@@ -303,55 +198,37 @@ int codec_launch(int mode, const void *in, void *out, int64_t C, int64_t inner, 
                  const float *zero_float, int64_t n_delta, const unsigned char *signed_flag, int n_bits, int symmetric,
                  float eps, hipStream_t st)
 {
-    if (!in || !out || C <= 0 || inner <= 0 || (n_delta != 1 && n_delta != C)) return FP8Q_EINVAL;
-    if ((n_delta > 1 && inner > INT32_MAX) || C > INT64_MAX / inner || cdiv(C * inner, kIntChunk) > (int64_t)UINT32_MAX)
-        return FP8Q_EINVAL;
+    if (int rc = int_check_x(in, out, C, inner, n_delta)) return rc;
     if (!delta || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
-    if (n_bits < 2 || n_bits > 16) return FP8Q_EUNSUPPORTED;
+    IntArgs a = {};
+    if (int rc = make_int_grid(n_bits, a.grid)) return rc;
     const int W = n_bits <= 8 ? 1 : 2;
     const uintptr_t pin = (uintptr_t)in, pout = (uintptr_t)out;
     if (((mode == kDecode ? pout : pin) & 3) || (mode == kLevel && (pout & 3))) return FP8Q_EINVAL;   // fp32 sides
     if (mode != kLevel && ((mode == kEncode ? pout : pin) & (uintptr_t)(W - 1))) return FP8Q_EINVAL;   // codes
     const bool pc = n_delta > 1;
-    CodecArgs a;
-    a.delta = delta;
-    a.zf = zero_float;
-    a.sflag = signed_flag;
-    a.n = C * inner;
-    a.inner = pc ? (int)inner : 1;
-    a.magic = pc ? magic_of((int)inner) : 0u;
-    a.nc_max = pc ? (int)(kIntChunk / inner + 2 < C ? kIntChunk / inner + 2 : C) : 1;
+    a.a = delta;
+    a.b = zero_float;
+    a.sflag = const_cast<unsigned char *>(signed_flag);   // read only
     a.symmetric = symmetric != 0;
     a.eps = eps;
-    a.n_hi_u = ldexpf(1.0f, n_bits) - 1.0f;
-    a.n_hi_s = ldexpf(1.0f, n_bits - 1) - 1.0f;
-    a.n_lo_s = -ldexpf(1.0f, n_bits - 1);
-    const dim3 g((unsigned)cdiv(a.n, kIntChunk)), b(kBlock);
-    const size_t shmem = (size_t)a.nc_max * sizeof(float4);
-    const bool nt = a.n * 4 >= kNtBytes;
+    int_geometry(a, C, inner, pc);
     // both sides on their vector word: 16 bytes, or (decode) a group's 4 W bytes of codes
     const bool vec = mode == kDecode ? ((pout & 15) == 0 && (pin & (uintptr_t)(4 * W - 1)) == 0) : ((pin | pout) & 15) == 0;
-#define FP8Q_CODEC_LAUNCH(K, ...)                                                                                     \
-    do {                                                                                                              \
-        if (vec && nt) hipLaunchKernelGGL((K<__VA_ARGS__, true, true>), g, b, shmem, st, in, out, a);               \
-        else if (vec) hipLaunchKernelGGL((K<__VA_ARGS__, true, false>), g, b, shmem, st, in, out, a);               \
-        else hipLaunchKernelGGL((K<__VA_ARGS__, false, false>), g, b, shmem, st, in, out, a);                       \
-    } while (0)
     if (mode == kLevel) {
-        if (pc) FP8Q_CODEC_LAUNCH(k_int_level, true);
-        else FP8Q_CODEC_LAUNCH(k_int_level, false);
+        if (pc) FP8Q_INT_LAUNCH(vec, in, out, a, st, k_int_level, true);
+        else FP8Q_INT_LAUNCH(vec, in, out, a, st, k_int_level, false);
     } else if (mode == kEncode) {
-        if (W == 1 && pc) FP8Q_CODEC_LAUNCH(k_int_encode, 1, true);
-        else if (W == 1) FP8Q_CODEC_LAUNCH(k_int_encode, 1, false);
-        else if (pc) FP8Q_CODEC_LAUNCH(k_int_encode, 2, true);
-        else FP8Q_CODEC_LAUNCH(k_int_encode, 2, false);
+        if (W == 1 && pc) FP8Q_INT_LAUNCH(vec, in, out, a, st, k_int_encode, 1, true);
+        else if (W == 1) FP8Q_INT_LAUNCH(vec, in, out, a, st, k_int_encode, 1, false);
+        else if (pc) FP8Q_INT_LAUNCH(vec, in, out, a, st, k_int_encode, 2, true);
+        else FP8Q_INT_LAUNCH(vec, in, out, a, st, k_int_encode, 2, false);
     } else {
-        if (W == 1 && pc) FP8Q_CODEC_LAUNCH(k_int_decode, 1, true);
-        else if (W == 1) FP8Q_CODEC_LAUNCH(k_int_decode, 1, false);
-        else if (pc) FP8Q_CODEC_LAUNCH(k_int_decode, 2, true);
-        else FP8Q_CODEC_LAUNCH(k_int_decode, 2, false);
+        if (W == 1 && pc) FP8Q_INT_LAUNCH(vec, in, out, a, st, k_int_decode, 1, true);
+        else if (W == 1) FP8Q_INT_LAUNCH(vec, in, out, a, st, k_int_decode, 1, false);
+        else if (pc) FP8Q_INT_LAUNCH(vec, in, out, a, st, k_int_decode, 2, true);
+        else FP8Q_INT_LAUNCH(vec, in, out, a, st, k_int_decode, 2, false);
     }
-#undef FP8Q_CODEC_LAUNCH
     return launch_rc();
 }
 

@@ -34,7 +34,7 @@ struct IGradArgs {
     int symmetric;
     int scaled;                    // grad_scale_elems > 0
     float eps;
-    float n_hi_u, n_hi_s, n_lo_s;  // 2^n - 1, 2^(n-1) - 1, -2^(n-1)
+    IntGrid grid;
     float gs_u, gs_s;              // gs for hi = n_hi_u / n_hi_s
 };
 
@@ -45,8 +45,8 @@ struct IGrid {
 
 __device__ __forceinline__ IGrid igrad_grid(const IGradArgs &a)
 {
-    const bool sgn = a.symmetric && a.sflag[0] != 0;
-    return IGrid{sgn ? a.n_lo_s : 0.0f, sgn ? a.n_hi_s : a.n_hi_u, sgn ? a.gs_s : a.gs_u};
+    const bool sgn = sign_byte(a.symmetric, a.sflag);
+    return IGrid{a.grid.lo(sgn), a.grid.hi(sgn), sgn ? a.gs_s : a.gs_u};
 }
 
 // one element: returns gx, adds its terms to the two sums; k = consts_of: {scale, -, zp, -}
@@ -261,7 +261,8 @@ int fp8q_int_quantize_bwd_f32(const float *x, const float *g, float *gx, int64_t
           (uintptr_t)gzero_float) & 3) != 0)
         return FP8Q_EINVAL;
     if (C > ((int64_t)1 << 42) / inner) return FP8Q_EINVAL;
-    if (n_bits < 2 || n_bits > 16) return FP8Q_EUNSUPPORTED;
+    IGradArgs a = {};
+    if (int rc = make_int_grid(n_bits, a.grid)) return rc;
     const bool sums = gdelta || gzero_float;
     const BwdPlan p = bwd_plan(C, inner, n_delta);
     if (p.blocks > 0x7fffffffll) return FP8Q_EINVAL;
@@ -269,19 +270,15 @@ int fp8q_int_quantize_bwd_f32(const float *x, const float *g, float *gx, int64_t
         return FP8Q_EWORKSPACE;
     if (sums && (size_t)p.blocks * 2 * sizeof(double) > ws_bytes) return FP8Q_EWORKSPACE;   // (the plan never exceeds its bound)
 
-    IGradArgs a = {};
     a.delta = delta;
     a.zf = symmetric ? nullptr : zero_float;
     a.sflag = signed_flag;
     a.symmetric = symmetric != 0;
     a.scaled = grad_scale_elems > 0;
     a.eps = eps;
-    a.n_hi_u = ldexpf(1.0f, n_bits) - 1.0f;
-    a.n_hi_s = ldexpf(1.0f, n_bits - 1) - 1.0f;
-    a.n_lo_s = -ldexpf(1.0f, n_bits - 1);
     if (a.scaled) {
-        a.gs_u = (float)(1.0 / sqrt((double)a.n_hi_u * (double)grad_scale_elems));
-        a.gs_s = (float)(1.0 / sqrt((double)a.n_hi_s * (double)grad_scale_elems));
+        a.gs_u = (float)(1.0 / sqrt((double)a.grid.n_hi_u * (double)grad_scale_elems));
+        a.gs_s = (float)(1.0 / sqrt((double)a.grid.n_hi_s * (double)grad_scale_elems));
     }
 
     hipStream_t st = (hipStream_t)stream;

@@ -1,6 +1,9 @@
-// fp8q_intq.h -- the uniform quantizers' scalar arithmetic shared by the forward (fp8q_int.hip), the backward
-// (fp8q_intgrad.hip) and the integer codes (fp8q_intcodec.hip): torch's min / max / clamp, the channel constants and the
-// integer level of an element.  Internal linkage, as fp8q_common.h.
+// fp8q_intq.h -- what the uniform quantizers' forward (fp8q_int.hip), backward (fp8q_intgrad.hip) and integer codes
+// (fp8q_intcodec.hip) share: torch's min / max / clamp, the integer grid of n bits, the channel constants and the integer
+// level of an element, and the geometry of the chunked kernels (k_int_quant, k_int_level, k_int_encode, k_int_decode): one
+// aligned 4096-element chunk per block, its prologue (sign, grid ends, the channel constants in LDS, the channel of an
+// element by magic division), the fp32 -> fp32 streaming loop, and the host side of their launch.  Internal linkage, as
+// fp8q_common.h.
 #pragma once
 #include "fp8q_common.h"
 
@@ -17,6 +20,31 @@ __device__ __forceinline__ float t_max(float a, float b)
 __device__ __forceinline__ float t_clamp(float v, float lo, float hi)   // torch.clamp: NaN passes, v when equal
 {
     return (v != v) ? v : (v < lo ? lo : (v > hi ? hi : v));
+}
+
+// [int_min, int_max] of n bits: [n_lo_s, n_hi_s] when signed (a symmetric quantizer whose sign is set), [0, n_hi_u] otherwise
+struct IntGrid {
+    float n_hi_u;            // 2^n - 1
+    float n_hi_s;            // 2^(n-1) - 1
+    float n_lo_s;            // -2^(n-1)
+
+    __device__ __forceinline__ float lo(bool sgn) const { return sgn ? n_lo_s : 0.0f; }
+    __device__ __forceinline__ float hi(bool sgn) const { return sgn ? n_hi_s : n_hi_u; }
+};
+
+inline int make_int_grid(int n_bits, IntGrid &g)
+{
+    if (n_bits < 2 || n_bits > 16) return FP8Q_EUNSUPPORTED;
+    g.n_hi_u = ldexpf(1.0f, n_bits) - 1.0f;
+    g.n_hi_s = ldexpf(1.0f, n_bits - 1) - 1.0f;
+    g.n_lo_s = -ldexpf(1.0f, n_bits - 1);
+    return FP8Q_OK;
+}
+
+// the sign of a symmetric quantizer, as any lane reads it from the device byte
+__device__ __forceinline__ bool sign_byte(int symmetric, const unsigned char *sflag)
+{
+    return symmetric && sflag[0] != 0;
 }
 
 // {scale, 1/scale, zp, -}
@@ -36,5 +64,181 @@ __device__ __forceinline__ float int_level(float v, const float4 k, float lo, fl
     if (fabsf(q0 - rq) >= 0.5f - fabsf(q0) * 0x1p-20f) rq = rintf(v / k.x);
     return t_clamp(rq + k.z, lo, hi);
 }
+
+// ---------------------------------------------------------------------------------------------
+// The chunked kernels
+// ---------------------------------------------------------------------------------------------
+constexpr int kIntChunk = 4096;       // elements per block: 16 KiB of fp32
+
+struct IntArgs {
+    const float *a;          // delta [1] or [C] | range-setting launches: x_min
+    const float *b;          // zero_float (asymmetric) | range-setting launches: x_max
+    unsigned char *sflag;    // symmetric: the sign (read; range-setting launches with an inline fold: written by block 0)
+    int64_t n;               // elements
+    int inner;               // row length (PC)
+    uint32_t magic;          // l / inner for l < inner + 4096 (inner < 4096)
+    int nc_max;              // LDS entries per block
+    int symmetric;
+    float eps;
+    IntGrid grid;
+    // range-setting launches (fp8q_int.hip) only
+    float *delta_out;        // delta written here
+    float *zf_out;           // asymmetric: zero_float written here
+    int64_t C;               // rows of the range vectors (1: per tensor)
+    int sign_inline;         // symmetric: fold the sign from the x_min vector in every block
+};
+
+// the sign of a symmetric range: no NaN in x_min and some x_min < 0 (x_min' = min(x_min, 0) has the same predicates)
+__device__ __forceinline__ bool block_sign(const float *__restrict__ xmin, int64_t C)
+{
+    int neg = 0, nan = 0;
+    for (int64_t i = threadIdx.x; i < C; i += blockDim.x) {
+        const float v = xmin[i];
+        neg |= v < 0.0f;
+        nan |= v != v;
+    }
+    neg = __syncthreads_or(neg);
+    nan = __syncthreads_or(nan);
+    return neg && !nan;
+}
+
+// a block's copy of the symmetric sign (false: asymmetric).  `fold`: this launch sets the range and folds the sign from
+// its x_min vector (`pc`: of more than one entry) in every block, block 0 reporting it; otherwise the device byte, read
+// once per block.
+__device__ __forceinline__ bool int_sign(const IntArgs &a, bool fold, bool pc)
+{
+    __shared__ int s_sign;
+    if (!a.symmetric) return false;
+    if (fold) {
+        const bool sgn = pc ? block_sign(a.a, a.C) : (a.a[0] < 0.0f);
+        if (blockIdx.x == 0 && threadIdx.x == 0) a.sflag[0] = (unsigned char)sgn;
+        return sgn;
+    }
+    if (threadIdx.x == 0) s_sign = sign_byte(a.symmetric, a.sflag);
+    __syncthreads();
+    return s_sign != 0;
+}
+
+struct Range {
+    float delta, zf;
+};
+
+// a row's (delta, zero_float) as the fixed-range kernels have it: read
+struct ReadRange {
+    const IntArgs &a;
+    __device__ __forceinline__ Range operator()(int64_t row, bool, float) const
+    {
+        return Range{a.a[row], a.symmetric ? 0.0f : a.b[row]};
+    }
+};
+
+// what a block knows about its chunk [e0, e1)
+struct Chunk {
+    int64_t e0, e1;
+    const float4 *kc;
+    float4 k0;
+    float lo, hi;
+    int phase, inner;
+    uint32_t magic;
+    bool sgn;
+
+    // channel constants of the element at offset `off` from e0
+    template <bool PC>
+    __device__ __forceinline__ float4 at(int off) const
+    {
+        if (!PC) return k0;
+        const uint32_t l = (uint32_t)(phase + off);
+        const int ch = inner >= kIntChunk ? (int)(l >= (uint32_t)inner) : div_small(l, magic);
+        return kc[ch];
+    }
+};
+
+// The prologue of a block.  kc: nc_max float4 of LDS.  range(row, starts, hi) yields a row's (delta, zero_float) -- `starts`:
+// the row begins in this chunk, so a range-setting launch reports it from here -- and fold_sign is int_sign()'s.
+template <bool PC, typename RangeOf>
+__device__ __forceinline__ Chunk chunk_setup(const IntArgs &a, float4 *kc, RangeOf range, bool fold_sign = false)
+{
+    const int tid = threadIdx.x;
+    Chunk c;
+    c.e0 = (int64_t)blockIdx.x * kIntChunk;
+    c.e1 = c.e0 + kIntChunk < a.n ? c.e0 + kIntChunk : a.n;
+    c.sgn = int_sign(a, fold_sign, PC);
+    c.lo = a.grid.lo(c.sgn);
+    c.hi = a.grid.hi(c.sgn);
+    const int64_t c_lo = PC ? c.e0 / a.inner : 0;
+    c.phase = PC ? (int)(c.e0 - c_lo * a.inner) : 0;
+    c.inner = a.inner;
+    c.magic = a.magic;
+    const int nc = PC ? (int)((c.e1 - 1) / a.inner - c_lo) + 1 : 1;
+    for (int i = tid; i < nc; i += kBlock) {
+        const int64_t row = c_lo + i;
+        const Range r = range(row, PC ? row * a.inner >= c.e0 : blockIdx.x == 0, c.hi);
+        kc[i] = consts_of(r.delta, r.zf, a.symmetric, c.lo, c.hi, a.eps);
+    }
+    __syncthreads();
+    c.kc = kc;
+    c.k0 = kc[0];
+    return c;
+}
+
+// y[e] = OP(x[e], the constants of e's channel, lo, hi) over the chunk.  VEC (x and y 16-byte aligned; e0 is a multiple of
+// 4096, so groups of 4 are aligned): a full chunk with its four 16-byte loads in flight, a partial one group by group, the
+// <= 3 elements behind the last group one by one.  !VEC: element by element.
+template <bool PC, bool VEC, bool NT, float (*OP)(float, const float4, float, float)>
+__device__ __forceinline__ void chunk_walk(const float *__restrict__ x, float *__restrict__ y, const Chunk &c)
+{
+    const int tid = threadIdx.x;
+    int64_t tail = c.e0;
+    if (VEC) {
+        const int ngroups = (int)((c.e1 - c.e0) >> 2);
+        const vf4 *xv = reinterpret_cast<const vf4 *>(x + c.e0);
+        vf4 *yv = reinterpret_cast<vf4 *>(y + c.e0);
+        auto op4 = [&](const vf4 v, int off) -> vf4 {
+            return vf4{OP(v.x, c.at<PC>(off), c.lo, c.hi), OP(v.y, c.at<PC>(off + 1), c.lo, c.hi),
+                       OP(v.z, c.at<PC>(off + 2), c.lo, c.hi), OP(v.w, c.at<PC>(off + 3), c.lo, c.hi)};
+        };
+        if (ngroups == kIntChunk / 4) {
+            vf4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = ld16<NT>(xv + u * kBlock + tid);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) st16<NT>(yv + u * kBlock + tid, op4(v[u], 4 * (u * kBlock + tid)));
+        } else {
+            for (int g = tid; g < ngroups; g += kBlock) st16<NT>(yv + g, op4(ld16<NT>(xv + g), 4 * g));
+        }
+        tail = c.e0 + 4 * (int64_t)ngroups;
+    }
+    for (int64_t e = tail + tid; e < c.e1; e += kBlock) y[e] = OP(x[e], c.at<PC>((int)(e - c.e0)), c.lo, c.hi);
+}
+
+// ---- host side ----
+// argument checks shared by the chunked entry points: C rows of `inner` elements, a range of 1 or C entries
+inline int int_check_x(const void *x, const void *y, int64_t C, int64_t inner, int64_t n_range)
+{
+    if (!x || !y || C <= 0 || inner <= 0 || (n_range != 1 && n_range != C)) return FP8Q_EINVAL;
+    if ((n_range > 1 && inner > INT32_MAX) || C > INT64_MAX / inner || cdiv(C * inner, kIntChunk) > (int64_t)UINT32_MAX)
+        return FP8Q_EINVAL;
+    return FP8Q_OK;
+}
+
+// the chunk geometry of C rows of `inner` elements; pc: one range entry per row
+inline void int_geometry(IntArgs &a, int64_t C, int64_t inner, bool pc)
+{
+    a.n = C * inner;
+    a.inner = pc ? (int)inner : 1;
+    a.magic = pc ? magic_of((int)inner) : 0u;
+    a.nc_max = pc ? (int)(kIntChunk / inner + 2 < C ? kIntChunk / inner + 2 : C) : 1;
+}
+
+// One block per chunk of K<..., VEC, NT>(in, out, a).  vec: both sides on their vector word; NT from the tensor's size.
+#define FP8Q_INT_LAUNCH(vec, in, out, a, st, K, ...)                                                                   \
+    do {                                                                                                              \
+        const dim3 g_((unsigned)cdiv((a).n, kIntChunk)), b_(kBlock);                                                  \
+        const size_t shmem_ = (size_t)(a).nc_max * sizeof(float4);                                                    \
+        const bool nt_ = (a).n * 4 >= kNtBytes;                                                                       \
+        if ((vec) && nt_) hipLaunchKernelGGL((K<__VA_ARGS__, true, true>), g_, b_, shmem_, st, in, out, a);          \
+        else if (vec) hipLaunchKernelGGL((K<__VA_ARGS__, true, false>), g_, b_, shmem_, st, in, out, a);             \
+        else hipLaunchKernelGGL((K<__VA_ARGS__, false, false>), g_, b_, shmem_, st, in, out, a);                     \
+    } while (0)
 
 }  // namespace

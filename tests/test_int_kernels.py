@@ -9,6 +9,7 @@ are therefore compared with the CPU chain, the quantize step with the CUDA chain
 import copy
 import io
 import os
+import types
 
 import numpy as np
 import pytest
@@ -130,6 +131,45 @@ def test_kernel_equals_eager_chain(sym, n_bits, shape, per_channel):
         with _Eager():
             yb = qb(xt)
         assert _same(qa(xt), yb)
+
+
+def _one_float_off(n):
+    """n floats of device memory that start one float behind a 16-byte boundary"""
+    t = torch.empty(n + 1, device="cuda")[1:]
+    assert t.data_ptr() % 16 == 4
+    return t
+
+
+@pytest.mark.parametrize("sym", [True, False])
+@pytest.mark.parametrize("n_bits", [8, 16])
+@pytest.mark.parametrize("shape,per_channel", CASES)
+def test_views_off_a_16_byte_boundary_equal_the_aligned_call(sym, n_bits, shape, per_channel):
+    """x, out=, or both one float off a 16-byte boundary -- the element-by-element (VEC = false) form of k_int_quant, with
+    fixed ranges and range-setting -- against the aligned call, bit for bit."""
+    from fp8q import ops
+    g = torch.Generator().manual_seed(hash((shape, n_bits)) % 1000)
+    x = _adversarial(shape, g)
+    C = shape[0] if per_channel else 1
+    xmin, xmax = (-torch.rand(C, generator=g) * 4).cuda(), (torch.rand(C, generator=g) * 4).cuda()
+    delta, zf, sf = ops.int_set_range(xmin, xmax, n_bits, sym)
+    xg = _ties(x, types.SimpleNamespace(_delta=delta)).cuda()
+    assert xg.data_ptr() % 16 == 0
+    xo = _one_float_off(xg.numel()).view(shape).copy_(xg)
+    ya = ops.int_quantize(xg, delta, zf, sf, n_bits, sym)
+    ra = ops.int_range_quantize(xg, xmin, xmax, n_bits, sym)
+    assert ya.data_ptr() % 16 == 0 and ra[0].data_ptr() % 16 == 0
+    for xi, off_out in ((xo, False), (xg, True), (xo, True)):
+        out = _one_float_off(xg.numel()).view(shape) if off_out else None
+        y = ops.int_quantize(xi, delta, zf, sf, n_bits, sym, out=out)
+        assert (y is out or out is None) and _same(y, ya), (shape, n_bits, sym, off_out)
+        out = _one_float_off(xg.numel()).view(shape) if off_out else None
+        r = ops.int_range_quantize(xi, xmin, xmax, n_bits, sym, out=out)
+        assert (r[0] is out or out is None) and _same(r[0], ra[0]), (shape, n_bits, sym, off_out)
+        assert _same(r[1], ra[1]) and _same(r[1], delta)
+        if sym:
+            assert bool(r[3]) == bool(ra[3]) == bool(sf)
+        else:
+            assert _same(r[2], ra[2]) and _same(r[2], zf)
 
 
 @pytest.mark.parametrize("sym", [True, False])

@@ -424,7 +424,8 @@ def test_half_minmax_quantize(shape, dtype):
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# 4. the uniform (INT) quantizers: fp8q_int.hip int_quant_launch (:436) and fp8q_intcodec.hip codec_launch (:331), both
+# 4. the uniform (INT) quantizers: fp8q_int.hip int_quant_launch and fp8q_intcodec.hip codec_launch, both through
+#    FP8Q_INT_LAUNCH (fp8q_intq.h):
 #    `a.n * 4 >= kNtBytes` with x and y 16-byte aligned -> the <.., VEC = true, NT = true> instances; one aligned
 #    4096-element chunk per block (4097 blocks here, the last one ragged)
 # ------------------------------------------------------------------------------------------------------------------
