@@ -31,61 +31,9 @@
 //                       per 16-byte load.
 // HBM traffic per element: K1 6 B (fp32 out) or 4 B (half out); min/max 2 B; min/max + quantize: a 2 B scan, then K1.
 #include "fp8q_common.h"
+#include "fp8q_half.h"
 
 namespace {
-
-typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-typedef __bf16 b2v __attribute__((ext_vector_type(2)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-typedef uint32_t u4v2 __attribute__((ext_vector_type(4), aligned(2)));   // 16 bytes wherever a half element may start
-
-struct F16 {
-    static __device__ __forceinline__ void widen2(uint32_t w, float &a, float &b)
-    {
-        const h2v h = __builtin_bit_cast(h2v, w);
-        a = (float)h.x;
-        b = (float)h.y;
-    }
-    static __device__ __forceinline__ uint32_t narrow2(float a, float b)
-    {
-        asm volatile("" : "+v"(a), "+v"(b));   // (see narrow1)
-        const f2v v = {a, b};
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, h2v));
-    }
-    static __device__ __forceinline__ float widen1(uint16_t u) { return (float)__builtin_bit_cast(_Float16, u); }
-    static __device__ __forceinline__ uint16_t narrow1(float a)
-    {
-        // the fp32 result is a value of its own: without this the compiler folds the quantizer's last multiplication and
-        // the conversion into v_fma_mixlo_f16, which rounds the exact product ONCE to fp16 -- not fl16(fl32(r * s))
-        asm volatile("" : "+v"(a));
-        return __builtin_bit_cast(uint16_t, (_Float16)a);
-    }
-};
-
-struct BF16 {
-    static __device__ __forceinline__ void widen2(uint32_t w, float &a, float &b)
-    {
-        a = __uint_as_float(w << 16);
-        b = __uint_as_float(w & 0xffff0000u);
-    }
-    static __device__ __forceinline__ uint32_t narrow2(float a, float b)
-    {
-        const f2v v = {a, b};
-        return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, b2v));
-    }
-    static __device__ __forceinline__ float widen1(uint16_t u) { return __uint_as_float((uint32_t)u << 16); }
-    static __device__ __forceinline__ uint16_t narrow1(float a) { return __builtin_bit_cast(uint16_t, (__bf16)a); }
-};
-
-template <class T, bool YF32>
-__device__ __forceinline__ void store1(void *y, int64_t e, float v)
-{
-    if (YF32)
-        reinterpret_cast<float *>(y)[e] = v;
-    else
-        reinterpret_cast<uint16_t *>(y)[e] = T::narrow1(v);
-}
 
 __device__ __forceinline__ ChanLite lite_of(const float4 h)
 {
@@ -343,15 +291,6 @@ k_h16_minmax_part(const uint16_t *__restrict__ x, int64_t inner, int nsplit, uns
 // host side
 // ---------------------------------------------------------------------------------------------
 constexpr int kRowsMmMaxInner = 2048;   // k_h16_minmax_rows up to here
-
-bool half_type(int t) { return t == FP8Q_DT_F16 || t == FP8Q_DT_BF16; }
-
-int check_types(int x_type, int y_type)
-{
-    if (!half_type(x_type)) return FP8Q_EINVAL;
-    if (y_type != FP8Q_DT_F32 && y_type != x_type) return FP8Q_EINVAL;
-    return FP8Q_OK;
-}
 
 template <class T, bool YF32, bool PC>
 void quant_launch_u(int u, bool nt, dim3 g, size_t shmem, hipStream_t st, const uint16_t *x, void *y, const float *maxval,

@@ -41,32 +41,9 @@
 
 namespace {
 
-constexpr int kSignInline = 2048;     // symmetric per-channel: up to here every block reduces the xmin vector itself
-
-__device__ __forceinline__ Range range_of(float xmin, float xmax, bool symmetric, float int_max, float eps)
-{
-    const float mn = t_min(xmin, 0.0f);
-    const float mx = t_max(xmax, eps);
-    Range r;
-    if (symmetric) {
-        r.delta = t_max(fabsf(mn), mx) / int_max;
-        r.zf = 0.0f;
-    } else {
-        r.delta = (mx - mn) / int_max;
-        r.zf = -mn / r.delta;
-    }
-    return r;
-}
-
-__device__ __forceinline__ float int_one(float v, const float4 k, float lo, float hi)
-{
-    const float t = int_level(v, k, lo, hi);
-    return k.x * (t - k.z);
-}
-
 // ---------------------------------------------------------------------------------------------
 // The candidate search (LineSearchEstimator with a uniform quantizer): out[k, c] += sum over row c of (x - q_k(x))^2,
-// q_k the quantizer after set_quant_range(one_sided ? 0 : -thr[k, c], thr[k, c]) -- range_of / consts_of above on a
+// q_k the quantizer after set_quant_range(one_sided ? 0 : -thr[k, c], thr[k, c]) -- range_of / consts_of (fp8q_intq.h) on a
 // one-element range, the symmetric sign being that element's (x_min < 0; a NaN threshold: unsigned).
 //   float32 x: int_one, then d = x - y and d * d in fp32 (the reference's chain on a float32 sample), widened exactly.
 //   float64 x: ATen's promotion with a float64 tensor and 0-dim fp32 scale / zero point: both widened exactly, every op
@@ -205,13 +182,7 @@ k_int_quant(const float *__restrict__ x, float *__restrict__ y, IntArgs a)
     extern __shared__ float4 kc[];    // nc_max channel constants
     // RANGE: a row's range from (x_min, x_max); the block in whose chunk the row starts reports it
     auto range = [&](int64_t row, bool starts, float hi) -> Range {
-        if (!RANGE) return ReadRange{a}(row, starts, hi);
-        const Range r = range_of(a.a[row], a.b[row], a.symmetric, hi, a.eps);
-        if (starts) {
-            a.delta_out[row] = r.delta;
-            if (!a.symmetric) a.zf_out[row] = r.zf;
-        }
-        return r;
+        return RANGE ? SetRange{a}(row, starts, hi) : ReadRange{a}(row, starts, hi);
     };
     const Chunk c = chunk_setup<PC>(a, kc, range, RANGE && a.sign_inline);
     chunk_walk<PC, VEC, NT, int_one>(x, y, c);
@@ -294,16 +265,13 @@ int int_quant_launch(bool range, const float *x, float *y, int64_t C, int64_t in
     return launch_rc();
 }
 
-// RANGE launches of the symmetric per-channel case: the sign first when the blocks cannot fold it themselves
-int int_sign_prepass(IntArgs &a, hipStream_t st)
+}  // namespace
+
+int fp8q_int_sign_launch(const float *xmin, int64_t C, unsigned char *sflag, hipStream_t st)
 {
-    a.sign_inline = !(a.symmetric && a.C > kSignInline);
-    if (a.sign_inline) return FP8Q_OK;
-    hipLaunchKernelGGL(k_int_sign, dim3(1), dim3(1024), 0, st, a.a, a.C, a.sflag);
+    hipLaunchKernelGGL(k_int_sign, dim3(1), dim3(1024), 0, st, xmin, C, sflag);
     return launch_rc();
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -1,13 +1,18 @@
-// fp8q_intq.h -- what the uniform quantizers' forward (fp8q_int.hip), backward (fp8q_intgrad.hip) and integer codes
-// (fp8q_intcodec.hip) share: torch's min / max / clamp, the integer grid of n bits, the channel constants and the integer
-// level of an element, and the geometry of the chunked kernels (k_int_quant, k_int_level, k_int_encode, k_int_decode): one
-// aligned 4096-element chunk per block, its prologue (sign, grid ends, the channel constants in LDS, the channel of an
-// element by magic division), the fp32 -> fp32 streaming loop, and the host side of their launch.  Internal linkage, as
-// fp8q_common.h.
+// fp8q_intq.h -- what the uniform quantizers' forward (fp8q_int.hip; fp8q_inth16.hip on fp16 / bf16 tensors), backward
+// (fp8q_intgrad.hip) and integer codes (fp8q_intcodec.hip) share: torch's min / max / clamp, the integer grid of n bits, the
+// channel constants, the integer level and the quantized value of an element, a row's range from (x_min, x_max), and the
+// geometry of the chunked kernels (k_int_quant, k_inth16_quant, k_int_level, k_int_encode, k_int_decode): one aligned
+// 4096-element chunk per block, its prologue (sign, grid ends, the channel constants in LDS, the channel of an element by
+// magic division), the fp32 -> fp32 streaming loop, and the host side of their launch.  Internal linkage, as fp8q_common.h.
 #pragma once
 #include "fp8q_common.h"
 
+// k_int_sign (fp8q_int.hip): the global sign of a symmetric per-channel range, for the range-setting launches of every lane
+int fp8q_int_sign_launch(const float *xmin, int64_t C, unsigned char *sflag, hipStream_t st);
+
 namespace {
+
+constexpr int kSignInline = 2048;     // symmetric per-channel: up to here every block reduces the xmin vector itself
 
 __device__ __forceinline__ float t_min(float a, float b)   // torch.min(a, b) of the scalar loop: a unless b < a
 {
@@ -63,6 +68,13 @@ __device__ __forceinline__ float int_level(float v, const float4 k, float lo, fl
     float rq = rintf(q0);
     if (fabsf(q0 - rq) >= 0.5f - fabsf(q0) * 0x1p-20f) rq = rintf(v / k.x);
     return t_clamp(rq + k.z, lo, hi);
+}
+
+// y = scale * (t - zp): the quantize-dequantize of one element
+__device__ __forceinline__ float int_one(float v, const float4 k, float lo, float hi)
+{
+    const float t = int_level(v, k, lo, hi);
+    return k.x * (t - k.z);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -129,6 +141,37 @@ struct ReadRange {
     __device__ __forceinline__ Range operator()(int64_t row, bool, float) const
     {
         return Range{a.a[row], a.symmetric ? 0.0f : a.b[row]};
+    }
+};
+
+// set_quant_range of one row: (x_min, x_max) -> (delta, zero_float); hi: int_max of the quantizer's sign
+__device__ __forceinline__ Range range_of(float xmin, float xmax, bool symmetric, float int_max, float eps)
+{
+    const float mn = t_min(xmin, 0.0f);
+    const float mx = t_max(xmax, eps);
+    Range r;
+    if (symmetric) {
+        r.delta = t_max(fabsf(mn), mx) / int_max;
+        r.zf = 0.0f;
+    } else {
+        r.delta = (mx - mn) / int_max;
+        r.zf = -mn / r.delta;
+    }
+    return r;
+}
+
+// ... and as the range-setting launches have it: from (x_min, x_max) = (a.a, a.b); the block in whose chunk the row starts
+// reports it
+struct SetRange {
+    const IntArgs &a;
+    __device__ __forceinline__ Range operator()(int64_t row, bool starts, float hi) const
+    {
+        const Range r = range_of(a.a[row], a.b[row], a.symmetric, hi, a.eps);
+        if (starts) {
+            a.delta_out[row] = r.delta;
+            if (!a.symmetric) a.zf_out[row] = r.zf;
+        }
+        return r;
     }
 };
 
@@ -228,6 +271,14 @@ inline void int_geometry(IntArgs &a, int64_t C, int64_t inner, bool pc)
     a.inner = pc ? (int)inner : 1;
     a.magic = pc ? magic_of((int)inner) : 0u;
     a.nc_max = pc ? (int)(kIntChunk / inner + 2 < C ? kIntChunk / inner + 2 : C) : 1;
+}
+
+// RANGE launches of the symmetric per-channel case: the sign first when the blocks cannot fold it themselves
+inline int int_sign_prepass(IntArgs &a, hipStream_t st)
+{
+    a.sign_inline = !(a.symmetric && a.C > kSignInline);
+    if (a.sign_inline) return FP8Q_OK;
+    return fp8q_int_sign_launch(a.a, a.C, a.sflag, st);
 }
 
 // One block per chunk of K<..., VEC, NT>(in, out, a).  vec: both sides on their vector word; NT from the tensor's size.

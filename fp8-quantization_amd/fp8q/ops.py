@@ -676,13 +676,14 @@ def _int_ptrs(x, delta, zero_float, signed_flag, symmetric, n):
             signed_flag.data_ptr() if symmetric else None)
 
 
-def _int_x(x, out, n_range, out_dtype=None):
+def _int_x(x, out, n_range, out_dtype=None, dense=False):
     """(x as the kernel reads it, y, C, inner, result): per tensor on a dense non-contiguous layout the storage as it
     lies (the result keeps x's strides, as the elementwise ATen chain does); otherwise a contiguous [C, inner] view.
-    out_dtype: the result's dtype when it is not x's (integer codes: always the contiguous view, codes are storage)."""
-    flat = _dense_flat(x) if (n_range == 1 and out is None and out_dtype is None) else None
+    out_dtype: the result's dtype when it is not x's (integer codes: always the contiguous view, codes are storage;
+    `dense`: values of a half input, which keep the layout)."""
+    flat = _dense_flat(x) if (n_range == 1 and out is None and (out_dtype is None or dense)) else None
     if flat is not None:
-        res = torch.empty_like(x)
+        res = torch.empty_like(x, dtype=out_dtype)
         flat_out = _dense_flat(res) if res.stride() == x.stride() else None
         if flat_out is not None:
             return flat, flat_out, 1, flat.numel(), res
@@ -694,18 +695,41 @@ def _int_x(x, out, n_range, out_dtype=None):
     return x, y, C, inner, y
 
 
-def int_quantize(x, delta, zero_float=None, signed_flag=None, n_bits=8, symmetric=False, eps=1e-8, out=None):
+def _int_half(x, out, out_dtype):
+    """The lane of an INT call by x's dtype: None for float32 x (out_dtype, when given, must be float32), the result's
+    dtype for float16 / bfloat16 x (_half_out_dtype: float32 unless `out` / out_dtype ask for x's own).  Argument errors
+    come before the device check: they need no GPU to be told."""
+    if isinstance(x, torch.Tensor) and x.dtype in _HALF:
+        dt = _half_out_dtype(x, out, out_dtype)
+        _require(x, "x", _HALF)
+        return dt
+    if isinstance(x, torch.Tensor):
+        _check_out_dtype(x, out_dtype)
+    _require(x, "x")
+    return None
+
+
+def int_quantize(x, delta, zero_float=None, signed_flag=None, n_bits=8, symmetric=False, eps=1e-8, out=None,
+                 out_dtype=None):
     """Uniform (INT) quantize+dequantize with fixed ranges (uniform_quantizers.py forward, linear scale domain):
     y = scale * (clamp(rint(x / scale) + zp, int_min, int_max) - zp).  delta (and zero_float, asymmetric) [1] or [C]
-    CUDA fp32; symmetric: signed_flag is the quantizer's 1-byte device sign, read by the kernel.  One launch."""
-    _require(x, "x")
+    CUDA fp32; symmetric: signed_flag is the quantizer's 1-byte device sign, read by the kernel.  One launch.
+    x float16 / bfloat16 (fp8q_int_quantize_h16): x widened exactly, the fp32 chain, the result float32 unless `out` or
+    out_dtype=x.dtype ask for x's own dtype (rounded once)."""
+    dt = _int_half(x, out, out_dtype)
     delta = delta.detach().reshape(-1)
     n = delta.numel()
     zero_float = zero_float.detach().reshape(-1) if zero_float is not None else None
     signed_flag = signed_flag.detach().reshape(-1) if signed_flag is not None else None
     pd, pz, ps = _int_ptrs(x, delta, zero_float, signed_flag, symmetric, n)
-    xk, y, C, inner, res = _int_x(x, out, n)
+    xk, y, C, inner, res = _int_x(x, out, n, dt, dense=True)
     if xk.numel() == 0:
+        return res
+    if dt is not None:
+        with _on_device(xk):
+            rc = lib().fp8q_int_quantize_h16(xk.data_ptr(), y.data_ptr(), _DT[x.dtype], _DT[dt], C, inner, pd, pz, n, ps,
+                                             int(n_bits), int(bool(symmetric)), float(eps), _stream(xk))
+        check(rc, "fp8q_int_quantize_h16")
         return res
     with _on_device(xk):
         rc = lib().fp8q_int_quantize_f32(xk.data_ptr(), y.data_ptr(), C, inner, pd, pz, n, ps, int(n_bits),
@@ -858,10 +882,11 @@ def int_set_range(x_min, x_max, n_bits=8, symmetric=False, eps=1e-8, delta=None,
 
 
 def int_range_quantize(x, x_min, x_max, n_bits=8, symmetric=False, eps=1e-8, delta=None, zero_float=None,
-                       signed_flag=None, out=None):
+                       signed_flag=None, out=None, out_dtype=None):
     """int_set_range and int_quantize in ONE launch (the range-estimating forward).  Returns
-    (y, delta, zero_float, signed_flag) like int_set_range."""
-    _require(x, "x")
+    (y, delta, zero_float, signed_flag) like int_set_range.  x float16 / bfloat16 (fp8q_int_range_quantize_h16): y as
+    int_quantize's, the ranges float32 as ever."""
+    dt = _int_half(x, out, out_dtype)
     _require(x_min, "x_min", like=x)
     _require(x_max, "x_max", like=x)
     x_min, x_max = x_min.detach().contiguous(), x_max.detach().contiguous()
@@ -869,9 +894,16 @@ def int_range_quantize(x, x_min, x_max, n_bits=8, symmetric=False, eps=1e-8, del
         raise Fp8qError("x_min and x_max must have the same, non-zero number of elements")
     n, delta, zero_float, signed_flag = _int_range_out(x_min, delta, zero_float, signed_flag, symmetric)
     pd, pz, ps = _int_ptrs(x, delta, zero_float, signed_flag, symmetric, n)
-    xk, y, C, inner, res = _int_x(x, out, n)
+    xk, y, C, inner, res = _int_x(x, out, n, dt, dense=True)
     if xk.numel() == 0:
         return (res,) + int_set_range(x_min, x_max, n_bits, symmetric, eps, delta, zero_float, signed_flag)
+    if dt is not None:
+        with _on_device(xk):
+            rc = lib().fp8q_int_range_quantize_h16(xk.data_ptr(), y.data_ptr(), _DT[x.dtype], _DT[dt], C, inner,
+                                                   x_min.data_ptr(), x_max.data_ptr(), n, pd, pz, ps, int(n_bits),
+                                                   int(bool(symmetric)), float(eps), _stream(xk))
+        check(rc, "fp8q_int_range_quantize_h16")
+        return res, delta, zero_float, signed_flag
     with _on_device(xk):
         rc = lib().fp8q_int_range_quantize_f32(xk.data_ptr(), y.data_ptr(), C, inner, x_min.data_ptr(),
                                                x_max.data_ptr(), n, pd, pz, ps, int(n_bits), int(bool(symmetric)),
@@ -881,15 +913,16 @@ def int_range_quantize(x, x_min, x_max, n_bits=8, symmetric=False, eps=1e-8, del
 
 
 def int_minmax_quantize(x, n_bits=8, symmetric=False, eps=1e-8, delta=None, zero_float=None, signed_flag=None,
-                        out=None):
+                        out=None, out_dtype=None):
     """Per-channel current_minmax + set_quant_range + quantize of a uniform quantizer (weights): row min / max, then
-    range and quantize in one more launch.  Returns (y, row_min, row_max, delta, zero_float, signed_flag)."""
-    _require(x, "x")
+    range and quantize in one more launch.  Returns (y, row_min, row_max, delta, zero_float, signed_flag).
+    x float16 / bfloat16 (fp8q_int_minmax_quantize_h16): y as int_quantize's, row min / max and the ranges float32."""
+    dt = _int_half(x, out, out_dtype)
     x = x.contiguous()
     C, inner = _rows(x, True)
     if C == 0 or inner == 0:
         raise Fp8qError("min/max of an empty tensor")
-    y = _out(out, x)
+    y = _out(out, x, dt)
     mn, mx = torch.empty((2, C), dtype=torch.float32, device=x.device).unbind(0)
     n, delta, zero_float, signed_flag = _int_range_out(mn, delta, zero_float, signed_flag, symmetric)
     pd, pz, ps = _int_ptrs(x, delta, zero_float, signed_flag, symmetric, n)
@@ -898,6 +931,13 @@ def int_minmax_quantize(x, n_bits=8, symmetric=False, eps=1e-8, delta=None, zero
     if nbytes is None:
         nbytes = _mm_ws_bytes[(C, inner)] = L.fp8q_minmax_workspace_bytes(C, inner)
     ws = _workspace(x.device, nbytes, zeroed=True)
+    if dt is not None:
+        with _on_device(x):
+            rc = L.fp8q_int_minmax_quantize_h16(x.data_ptr(), y.data_ptr(), _DT[x.dtype], _DT[dt], C, inner, mn.data_ptr(),
+                                                mx.data_ptr(), pd, pz, ps, int(n_bits), int(bool(symmetric)), float(eps),
+                                                ws.data_ptr(), ws.numel(), _stream(x))
+        check(rc, "fp8q_int_minmax_quantize_h16")
+        return y, mn, mx, delta, zero_float, signed_flag
     with _on_device(x):
         rc = L.fp8q_int_minmax_quantize_f32(x.data_ptr(), y.data_ptr(), C, inner, mn.data_ptr(), mx.data_ptr(), pd,
                                             pz, ps, int(n_bits), int(bool(symmetric)), float(eps), ws.data_ptr(),

@@ -14,9 +14,10 @@ it (:114-122) -- but picks the cheapest kernel sequence for it:
   anything else (custom estimator / quantizer)       -> the generic protocol calls
 
 float16 / bfloat16 inputs take the same FP8 min/max routes on the half-precision kernels (fp8q_minmax_h16,
-fp8q_minmax_quantize_h16, fp8q_quantize_h16); everything else (MSE / line search, allow_unsigned, percentile, INT
-quantizers) is float32-only: the input is widened with .float() and the existing path runs (the output is cast back
-when the quantizer was built with keep_dtype).
+fp8q_minmax_quantize_h16, fp8q_quantize_h16), and a uniform quantizer built with keep_dtype the same INT routes on
+fp8q_minmax_h16 and fp8q_int_{quantize,range_quantize,minmax_quantize}_h16; everything else (MSE / line search,
+allow_unsigned, percentile, INT quantizers without keep_dtype, custom quantizers) is float32-only: the input is widened with
+.float() and the existing path runs (the output is cast back when the quantizer was built with keep_dtype).
 """
 from enum import auto
 
@@ -107,8 +108,8 @@ class QuantizationManager(nn.Module):
     def forward(self, x):
         q, est = self.quantizer, self.range_estimator
         half = isinstance(x, torch.Tensor) and x.dtype in (torch.float16, torch.bfloat16) and x.is_cuda
-        if half and type(q) is not FPQuantizer:
-            x, half = x.float(), False               # INT / custom quantizers: float32-only
+        if half and type(q) is not FPQuantizer and not (type(q) in _UNIFORM and q.keep_dtype):
+            x, half = x.float(), False               # INT without keep_dtype / custom quantizers: float32-only
         if not self._estimating():
             return q(x)
         if type(q) in _UNIFORM and type(est) in _MINMAX and not getattr(est, "percentile", None):

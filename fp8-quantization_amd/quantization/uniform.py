@@ -11,6 +11,12 @@ under autograd only (the switch of the FP quantizer's backward).
 The integers themselves (csrc/fp8q_intcodec.hip): `to_integer_forward` runs fp8q.ops.int_to_integer under forward's kernel
 conditions and stays the torch chain otherwise; `encode` / `decode` give and take the 1- or 2-byte storage codes and exist on
 the kernel path only (they raise elsewhere, FP8Q_INT_KERNELS=0 included).
+
+float16 / bfloat16 tensors (csrc/fp8q_inth16.hip): a quantizer built with `keep_dtype=True` runs `forward` and the
+range-setting forwards on the half kernels under the same conditions and returns x's dtype -- x widened exactly, the fp32
+chain, one rounding back; the ranges stay float32.  Under autograd or with learned ranges such an x is widened, takes the
+float32 route above and the result is cast back.  Without keep_dtype a half tensor is the eager chain, as ever.  The integer
+codes stay float32-only.
 """
 import os
 
@@ -108,8 +114,14 @@ class AsymmetricUniformQuantizer(QuantizerBase):
         return (isinstance(z, torch.Tensor) and not isinstance(z, torch.nn.Parameter) and z.dtype == torch.float32
                 and z.device == dev and z.numel() == d.numel() and not z.requires_grad)
 
-    def _kernel_x_ok(self, x, n):
-        if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.is_cuda
+    def _half_kept(self, x):
+        """x is a CUDA float16 / bfloat16 tensor and this quantizer keeps its dtype"""
+        return (getattr(self, "keep_dtype", False) and isinstance(x, torch.Tensor) and x.is_cuda
+                and x.dtype in (torch.float16, torch.bfloat16))
+
+    def _kernel_x_ok(self, x, n, half_ok=False):
+        """x takes the forward kernels for a range of n entries; half_ok: a kept half tensor does too (the half lane)"""
+        if not (isinstance(x, torch.Tensor) and (x.dtype == torch.float32 or (half_ok and self._half_kept(x))) and x.is_cuda
                 and not (x.requires_grad and torch.is_grad_enabled())):
             return False
         return n == 1 or (self.per_channel and x.dim() > 0 and x.shape[0] == n)
@@ -174,10 +186,11 @@ class AsymmetricUniformQuantizer(QuantizerBase):
 
     def _range_forward(self, x, x_min, x_max):
         """set_quant_range(x_min, x_max) then forward(x); ONE launch on the kernel path."""
-        if self._range_kernel_ok(x_min, x_max) and self._kernel_x_ok(x, x_min.numel()) and x.device == x_min.device:
+        if (self._range_kernel_ok(x_min, x_max) and self._kernel_x_ok(x, x_min.numel(), half_ok=True)
+                and x.device == x_min.device):
             self.x_min_fp32, self.x_max_fp32 = x_min, x_max
             y, d, z, sg = _ops.int_range_quantize(x, x_min, x_max, self.n_bits, self.symmetric, self.eps,
-                                                  *self._range_out(x_min))
+                                                  *self._range_out(x_min), out_dtype=x.dtype)
             self._store_range(d, z, sg)
             return y
         self.set_quant_range(x_min, x_max)
@@ -187,19 +200,22 @@ class AsymmetricUniformQuantizer(QuantizerBase):
         """Per-channel current_minmax + set_quant_range + forward (weights), or None off the kernel path.
         Returns (y, row_min, row_max)."""
         if not (self.per_channel and x.dim() > 0 and x.numel() > 0 and self._kernel_common(x.device)
-                and self._kernel_x_ok(x, x.shape[0]) and not isinstance(self._delta, torch.nn.Parameter)
+                and self._kernel_x_ok(x, x.shape[0], half_ok=True) and not isinstance(self._delta, torch.nn.Parameter)
                 and not isinstance(self._zero_float, torch.nn.Parameter)):
             return None
         like = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
         y, mn, mx, d, z, sg = _ops.int_minmax_quantize(x, self.n_bits, self.symmetric, self.eps,
-                                                       *self._range_out(like))
+                                                       *self._range_out(like), out_dtype=x.dtype)
         self.x_min_fp32, self.x_max_fp32 = mn, mx
         self._store_range(d, z, sg)
         return y, mn, mx
 
     def __init__(self, n_bits, scale_domain="linear", discretizer=round_ste_func, discretizer_args=tuple(),
-                 grad_scaling=False, eps=1e-8, **kwargs):
+                 grad_scaling=False, eps=1e-8, keep_dtype=False, **kwargs):
         super().__init__(n_bits=n_bits, **kwargs)
+        # float16 / bfloat16 inputs: True runs the half kernels and returns x's dtype (widen exactly, the fp32 chain, one
+        # rounding back); False leaves such a tensor to the eager chain (the manager widens it and returns float32)
+        self.keep_dtype = keep_dtype
         assert scale_domain in ("linear", "log")
         self.register_buffer("_delta", None)
         self.register_buffer("_zero_float", None)
@@ -318,9 +334,13 @@ class AsymmetricUniformQuantizer(QuantizerBase):
     def forward(self, x_float, *args, **kwargs):
         d = self._delta
         if (d is not None and self._kernel_common(x_float.device) and self._kernel_buffers_ok(x_float.device)
-                and self._kernel_x_ok(x_float, d.numel())):
+                and self._kernel_x_ok(x_float, d.numel(), half_ok=True)):
             return _ops.int_quantize(x_float, d, None if self.symmetric else self._zero_float,
-                                     self._signed if self.symmetric else None, self.n_bits, self.symmetric, self.eps)
+                                     self._signed if self.symmetric else None, self.n_bits, self.symmetric, self.eps,
+                                     out_dtype=x_float.dtype)
+        if self._half_kept(x_float) and self._kernel_common(x_float.device):
+            # under autograd, or with learned ranges: widen, the float32 route (its kernels where they apply), cast back
+            return self.forward(x_float.float()).to(x_float.dtype)
         if d is not None and self._kernel_common(x_float.device) and self._grad_kernel_ok(x_float, x_float.device):
             return _IntFakeQuantSTE.apply(x_float, d, None if self.symmetric else self._zero_float,
                                           self._signed if self.symmetric else None, self.n_bits, self.symmetric, self.eps,

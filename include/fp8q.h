@@ -583,6 +583,44 @@ int fp8q_minmax_quantize_h16(const void *x, void *y, int x_type, int y_type, int
                              float *row_max, float *maxval_out, float mbits, int n_bits, int sign_bits,
                              fp8q_stream_t stream);
 
+/*
+ * The uniform (INT) quantizers on IEEE fp16 and bfloat16 tensors (csrc/fp8q_inth16.hip): fp8q_int_quantize_f32,
+ * fp8q_int_range_quantize_f32 and fp8q_int_minmax_quantize_f32 with half x -- the argument lists of the _f32 twins, with
+ * x_type / y_type (FP8Q_DT_*) behind x and y as in fp8q_quantize_h16.  Arithmetic contract:
+ *   - every input element is widened to fp32 exactly, as the half-precision lane above does it: fp16 subnormals become
+ *     normal numbers, bf16 is the upper half of an fp32 word, nothing is flushed;
+ *   - from there the fp32 contract of the uniform quantizers applies unchanged, through the same code (the
+ *     reciprocal-then-redo rule for x / scale included): the fp32 result is bit-identical to fp8q_int_quantize_f32 on the
+ *     widened input.  Ranges (delta, zero_float, the sign byte, row min / max) are fp32;
+ *   - y_type == FP8Q_DT_F32 stores that fp32 result; y_type == x_type rounds it ONCE to the storage type (round to nearest
+ *     even, overflow to infinity: torch.Tensor.to(dtype)).  The fp32 value scale * (t - zp) exists before it is narrowed --
+ *     the multiplication and the conversion are never fused into one rounding.  y may alias x then;
+ *   - this is deliberately NOT the reference's arithmetic on a half tensor (with a 0-dim delta ATen rounds every op to the
+ *     half type): it is the contract of the half-precision lane -- widen, compute in fp32, round once.
+ * x (and a half y) need only their natural 2-byte alignment, an fp32 y 4 bytes; views at any element offset, y need not
+ * share x's phase against the 16-byte grid; rows of any length (rows shorter than 8 elements and odd row lengths included).
+ * Errors, all reported before any launch: FP8Q_EINVAL for null pointers, an x_type that is not a half type, a y_type that
+ * is neither FP8Q_DT_F32 nor x_type, n_delta / n_range not in {1, C}, EMPTY tensors (C or inner <= 0), misaligned x / y and
+ * the size limits of the _f32 twins (per-channel rows beyond 2^31 - 1 elements, more than 2^32 - 1 chunks of 4096 elements);
+ * FP8Q_EUNSUPPORTED for n_bits outside [2, 16]; fp8q_int_minmax_quantize_h16: FP8Q_EWORKSPACE as fp8q_minmax_h16.
+ *   fp8q_int_quantize_h16         fixed ranges: one launch.  HBM traffic: 4 B / element (half out), 6 B (fp32 out).
+ *   fp8q_int_range_quantize_h16   int_set_range and the quantize in ONE launch (two for more than 2048 symmetric channels):
+ *                                 delta / zero_float / signed_flag are bit-identical to fp8q_int_set_range_f32's.
+ *   fp8q_int_minmax_quantize_h16  per-channel current_minmax: fp8q_minmax_h16's row scan (FP8Q_FOLD_CURRENT; ws / ws_bytes
+ *                                 as there) writes row_min / row_max, then fp8q_int_range_quantize_h16 on them.  Two launches
+ *                                 (three beyond 2048 symmetric channels), 2 B / element more.
+ * Enqueue-only, no allocation.  FP8Q_VERSION is unchanged: the entries are additive.
+ */
+int fp8q_int_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t C, int64_t inner, const float *delta,
+                          const float *zero_float, int64_t n_delta, const unsigned char *signed_flag, int n_bits,
+                          int symmetric, float eps, fp8q_stream_t stream);
+int fp8q_int_range_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t C, int64_t inner,
+                                const float *x_min, const float *x_max, int64_t n_range, float *delta, float *zero_float,
+                                unsigned char *signed_flag, int n_bits, int symmetric, float eps, fp8q_stream_t stream);
+int fp8q_int_minmax_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t C, int64_t inner, float *row_min,
+                                 float *row_max, float *delta, float *zero_float, unsigned char *signed_flag, int n_bits,
+                                 int symmetric, float eps, void *ws, size_t ws_bytes, fp8q_stream_t stream);
+
 /* ---- backward of the FP quantizer (csrc/fp8q_grad.hip) --------------------------------------------------------------------
  * The gradient of quantize_to_fp8_ste_MM (fp8_quantizer.py:105-133) with respect to x, maxval and the mantissa width, in
  * ONE streaming pass over x and the upstream gradient g (contiguous fp32 viewed as [C, inner], the layout rules of
