@@ -11,12 +11,15 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <climits>
+#include <type_traits>
+
 #include "../../include/fp8q.h"
 #include "fp8q_device.h"
 
 using namespace fp8q;
 
-// short-row path of the storage codec: lives with k_rows_flat in fp8q_quant.hip, called from fp8q_codec.hip
+// short-row path of the storage codec: lives with k_rows_flat in fp8q_rows.hip, called from fp8q_codec.hip
 constexpr int FP8Q_CODEC_NOT_FLAT = -1000;
 int fp8q_codec_flat_launch(bool encode, const void *in, void *out, int64_t C, int64_t inner, const float *maxval,
                            const QFmt &f, int n_bits, hipStream_t st);
@@ -33,6 +36,29 @@ static const int64_t kNtBytes = [] {
     const long v = e ? atol(e) : 0;
     return (int64_t)(v >= 1 ? v : 64) << 20;
 }();
+
+// An integer tuning knob read from the environment: `dflt` when unset, otherwise the value clamped to [lo, hi]
+// (unparsable text reads as 0).  Knobs that fall back to their default on an out-of-range value keep their own code.
+inline int env_int(const char *name, int dflt, int lo = INT_MIN, int hi = INT_MAX)
+{
+    const char *e = getenv(name);
+    if (!e) return dflt;
+    const long v = atol(e);
+    return v < lo ? lo : (v > hi ? hi : (int)v);
+}
+
+// A runtime bool / small int as a template argument: dispatch<A, B, ...>(v, f) calls f(Const<V>{}) for the first listed V
+// equal to v, for the last listed one if none is; inside a generic lambda `auto V`, V() is the constant.
+template <auto V>
+using Const = std::integral_constant<decltype(V), V>;
+
+template <auto V0, auto... Vs, class F>
+inline void dispatch(decltype(V0) v, F &&f)
+{
+    if constexpr (sizeof...(Vs) == 0) f(Const<V0>{});
+    else if (v == V0) f(Const<V0>{});
+    else dispatch<Vs...>(v, f);
+}
 
 // Blocks for `pieces` equal pieces of work with at most `cap` blocks: every block gets the same number of
 // steps (a persistent grid of exactly `cap` blocks over 6.1 steps' worth of pieces runs 7 steps: -12 %).

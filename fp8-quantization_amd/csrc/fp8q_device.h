@@ -247,6 +247,17 @@ __device__ __forceinline__ ChanLite lite(const Chan &c)
     return l;
 }
 
+// ... and from the float4 {maxv, minv, bias, pthr} the chunk kernels keep per table row in LDS
+__device__ __forceinline__ ChanLite lite_of(const float4 h)
+{
+    ChanLite l;
+    l.maxv = h.x;
+    l.minv = h.y;
+    l.bias = h.z;
+    l.pthr = h.w;
+    return l;
+}
+
 // exact path of one element (rare lanes only)
 __device__ __noinline__ float quant_exact(float x, float maxv, float minv, float bias,
                                           const float2 *lut, float pmaxf)

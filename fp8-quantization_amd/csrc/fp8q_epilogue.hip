@@ -444,10 +444,7 @@ static void affine_grid_store(int64_t N, const AffineArgs &a, int64_t *bx, int64
 // FP8Q_EPI_SMALL_KIND: 0 = the staged kernel for small tensors too (round 3), 1 = k_affine_act_small, 2 = with early loads
 static int small_kind()
 {
-    static const int v = [] {
-        const char *e = getenv("FP8Q_EPI_SMALL_KIND");
-        return e ? atoi(e) : 2;
-    }();
+    static const int v = env_int("FP8Q_EPI_SMALL_KIND", 2);
     return v;
 }
 
@@ -576,10 +573,7 @@ static int affine_minmax_impl(const float *x, const float *residual, int64_t N, 
     if (!ws || ws_bytes < fp8q_affine_act_minmax_workspace_bytes(N, C, HW) || ((uintptr_t)ws & 7)) return FP8Q_EWORKSPACE;
     if ((((uintptr_t)x | (uintptr_t)residual) & 15) || ((uintptr_t)packed & 15)) return FP8Q_EINVAL;
     {
-        static const bool debug_ws = [] {
-            const char *e = getenv("FP8Q_DEBUG_WS");
-            return e && atoi(e) != 0;
-        }();
+        static const bool debug_ws = env_int("FP8Q_DEBUG_WS", 0) != 0;
         if (debug_ws)
             if (int rc = fp8q_minmax_workspace_check(ws, fp8q_affine_act_minmax_workspace_bytes(N, C, HW), 0, stream)) return rc;
     }

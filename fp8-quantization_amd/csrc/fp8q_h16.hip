@@ -35,16 +35,6 @@
 
 namespace {
 
-__device__ __forceinline__ ChanLite lite_of(const float4 h)
-{
-    ChanLite l;
-    l.maxv = h.x;
-    l.minv = h.y;
-    l.bias = h.z;
-    l.pthr = h.w;
-    return l;
-}
-
 // quant_group<8> (fp8q_device.h) for a group whose elements b..7 belong to a second channel
 __device__ __forceinline__ void quant_group_2rows(float (&v)[8], int b, const ChanLite &ca, const float2 *la, const ChanLite &cb,
                                                   const float2 *lb, float pmaxf, float qthr)

@@ -796,10 +796,7 @@ int fp8q_quantize_select_f32(const float *x, float *y, int64_t n, const float *m
 // element (the self-check of the cell logic the tests use); 3 = the route for every per-tensor row of >= 2^12 elements (tuning)
 static int mse_hist_mode()
 {
-    static const int v = [] {
-        const char *e = getenv("FP8Q_MSE_HIST");
-        return e ? atoi(e) : 1;
-    }();
+    static const int v = env_int("FP8Q_MSE_HIST", 1);
     return v;
 }
 
@@ -890,10 +887,7 @@ struct RowGeo {
 
 static bool mse_use_row(int64_t C, int64_t inner)
 {
-    static const int env = [] {   // FP8Q_MSE_ROW=0: the lane-per-candidate kernel everywhere (A/B)
-        const char *e = getenv("FP8Q_MSE_ROW");
-        return e ? atoi(e) : 1;
-    }();
+    static const int env = env_int("FP8Q_MSE_ROW", 1);   // FP8Q_MSE_ROW=0: the lane-per-candidate kernel everywhere (A/B)
     return env && inner >= kMseRowMinInner && C <= 65535;
 }
 
@@ -946,10 +940,7 @@ size_t fp8q_mse_workspace_bytes(int64_t C, int64_t inner, int64_t n_cand, int n_
 // that can also make the first batch's ranges and grid itself (MseArgs::first_grid)
 static bool mse_first_batch_in_grid_kernel(const float *x, int64_t C, int64_t inner, int64_t n_cand, int n_m)
 {
-    static const bool on = [] {   // FP8Q_MSE_FIRST_IN_GRID=0: the separate abs-max + grid launch (A/B)
-        const char *e = getenv("FP8Q_MSE_FIRST_IN_GRID");
-        return !e || atoi(e) != 0;
-    }();
+    static const bool on = env_int("FP8Q_MSE_FIRST_IN_GRID", 1) != 0;   // =0: the separate abs-max + grid launch (A/B)
     if (!on || C <= 1 || mse_use_hist_shape(C, inner, n_cand, n_m)) return false;
     return !(mse_use_row(C, inner) && ((uintptr_t)x & 3) == 0);
 }
@@ -1091,7 +1082,7 @@ int fp8q_mse_calibrate_f32(float *x, float *y, int64_t C, int64_t inner, const f
     // per-tensor quantizer, the batch quantized right away: the selection rides in the prologue of that K1 launch
     // (k_quant_rows_sel) instead of behind a ticket in the launch that finishes the table (k_mse_eval 20.6 -> 11.0 us with six
     // widths, 11.1 -> 7.7 with one, K1 + 1..2 us; FP8Q_SEL_IN_K1=0: tickets, =1: only with the mantissa search)
-    static const int sel_in_k1 = getenv("FP8Q_SEL_IN_K1") ? atoi(getenv("FP8Q_SEL_IN_K1")) : 2;
+    static const int sel_in_k1 = env_int("FP8Q_SEL_IN_K1", 2);
     const bool late = sel_in_k1 && y && C == 1 && (n_m > 1 || sel_in_k1 == 2) && n_m <= kSelMaxM && (int64_t)n_m * n_cand <= 4096 &&
                       (((uintptr_t)x ^ (uintptr_t)y) & 15) == 0 && ((uintptr_t)x & 3) == 0;
     if (late) so.enabled = 0;

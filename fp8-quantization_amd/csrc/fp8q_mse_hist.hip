@@ -1447,14 +1447,6 @@ k_mse_eval(const float *__restrict__ x, const float *__restrict__ grid, const fl
 // ---- host -----------------------------------------------------------------------------------------------------------------
 size_t align_up(size_t v, size_t al) { return (v + al - 1) / al * al; }
 
-int env_int(const char *name, int dflt, int lo, int hi)
-{
-    const char *e = getenv(name);
-    if (!e) return dflt;
-    const long v = atol(e);
-    return v < lo ? lo : (v > hi ? hi : (int)v);
-}
-
 // tuning knobs (defaults are the measured best): borders per k_moments chunk, smallest key slice
 int hist_bcap() { static const int v = env_int("FP8Q_MSE_BCAP", 1024, 16, 6144); return v; }
 // Smallest key slice of a k_moments unit.  The launch has 2048 workgroups; a tensor of a few million keys cut into 16 K-key
