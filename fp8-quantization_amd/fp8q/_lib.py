@@ -115,6 +115,9 @@ SIGNATURES = {
     "fp8q_int_to_integer_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i, _i, _f, _vp]),
     "fp8q_int_encode": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i, _i, _f, _vp]),
     "fp8q_int_decode": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i, _i, _f, _vp]),
+    "fp8q_percentile_resident_max_inner": (_i64, []),
+    "fp8q_percentile_workspace_bytes": (ctypes.c_size_t, [_i64, _i64]),
+    "fp8q_percentile_f32": (_i, [_vp, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 

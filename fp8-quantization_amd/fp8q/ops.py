@@ -628,6 +628,44 @@ def fused_max_inner():
     return int(lib().fp8q_fused_max_inner())
 
 
+_pct_ws_bytes = {}
+
+
+def percentile_resident_max_inner():
+    return int(lib().fp8q_percentile_resident_max_inner())
+
+
+def percentile(x, per_channel, pct, lo=None, hi=None):
+    """Percentile range of every row (range_estimators.py:61-70: np.percentile(x, (pct, 100 - pct))) by exact selection
+    (fp8q_percentile_f32; contract: include/fp8q.h).  x: CUDA float32; returns (lo, hi), float32 [C] ([1] per tensor).
+    lo= / hi=: contiguous float32 tensors of C elements to write into."""
+    _require(x, "x")
+    flat = None if per_channel else _dense_flat(x)      # per tensor: a multiset statistic, any dense layout, no copy
+    x = flat if flat is not None else x.contiguous()
+    C, inner = _rows(x, per_channel)
+    if C == 0 or inner == 0:
+        raise Fp8qError("percentile of an empty tensor")
+    pct = float(pct)
+    if lo is None or hi is None:
+        fresh = torch.empty((2, C), dtype=torch.float32, device=x.device)
+        lo, hi = (fresh[0] if lo is None else lo), (fresh[1] if hi is None else hi)
+    for t, name in ((lo, "lo"), (hi, "hi")):
+        _require(t, name, like=x)
+        if t.numel() != C or not t.is_contiguous():
+            raise Fp8qError(f"{name} must be a contiguous tensor of {C} elements (got {tuple(t.shape)})")
+    L = lib()
+    nbytes = _pct_ws_bytes.get((C, inner))
+    if nbytes is None:
+        nbytes = _pct_ws_bytes[(C, inner)] = L.fp8q_percentile_workspace_bytes(C, inner)
+    stream = _stream(x)
+    ws = _workspace(x.device, nbytes, stream=stream) if nbytes else None
+    with _on_device(x):
+        rc = L.fp8q_percentile_f32(x.data_ptr(), C, inner, pct, lo.data_ptr(), hi.data_ptr(),
+                                   ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, stream)
+    check(rc, "fp8q_percentile_f32")
+    return lo, hi
+
+
 def minmax_quantize(x, mbits, n_bits=8, sign_bits=1, out=None, out_dtype=None):
     """K2+K5+K1 fused per-channel weight quantization (current_minmax, set_maxval=True).
     x float16 / bfloat16 (fp8q_minmax_quantize_h16): y is float32 unless `out` / out_dtype=x.dtype ask for x's dtype.

@@ -7,6 +7,8 @@ Same registry names, constructor arguments, buffers (`current_xmin`, `current_xm
 Each forward is one two-output reduction kernel (fp8q_minmax_f32) that also folds the batch
 estimate into the running one on the device -- no host synchronisation.
 """
+import os
+
 import numpy as np
 import torch
 from torch import nn
@@ -107,8 +109,18 @@ class CurrentMinMaxEstimator(RangeEstimatorBase):
 
     def forward(self, x):
         if self.percentile:
-            # unreachable from the reference CLI (hijacker.py:57 compares a class with an enum
-            # member); kept for API completeness through torch.quantile on the device
+            # unreachable from the reference CLI (hijacker.py:57 compares a class with an enum member); kept for API
+            # completeness.  CUDA float32 / float16 / bfloat16: exact selection on the device (fp8q_percentile_f32, contract in
+            # include/fp8q.h; half inputs are widened first), any size.  float64 and CPU tensors, and
+            # FP8Q_PERCENTILE_KERNELS=0, keep torch.quantile (at most 2^24 elements)
+            if x.is_cuda and x.dtype in (torch.float32, torch.float16, torch.bfloat16) \
+                    and os.environ.get("FP8Q_PERCENTILE_KERNELS", "1") != "0":
+                lo, hi = _ops.percentile(x.float(), self.per_channel, self.percentile)
+                if not self.per_channel:      # reference returns 0-dim tensors for per-tensor ranges
+                    lo, hi = lo.reshape(()), hi.reshape(())
+                self.current_xmin, self.current_xmax = lo, hi
+                self.last_maxval = None
+                return lo, hi
             # (in float64, as numpy's percentile interpolates: with a float32 `q` the position 0.999 * (n - 1) is already off by
             # 1e-5 of a step; the result is narrowed to float32 -- the reference keeps numpy's float64, which would drag the whole
             # quantizer into float64)

@@ -686,6 +686,36 @@ int fp8q_int_quantize_bwd_f32(const float *x, const float *g, float *gx, int64_t
                               int symmetric, float eps, int64_t grad_scale_elems, float *gdelta, float *gzero_float, void *ws,
                               size_t ws_bytes, fp8q_stream_t stream);
 
+/*
+ * Percentile ranges (CurrentMinMaxEstimator(percentile=p), range_estimators.py:61-70: np.percentile(x, (p, 100 - p))):
+ * lo[c], hi[c] of every row of a contiguous [C, inner] float32 tensor by EXACT selection -- a radix select over integer
+ * keys, no sort, no floating-point sums (csrc/fp8q_select.hip).  Arithmetic contract, for one row of n = inner elements:
+ *   1. Ordering: by the monotone unsigned key of the bit pattern (non-negative numbers set the sign bit, negative numbers
+ *      invert all bits): -inf < ... < -0.0 < +0.0 < ... < +inf, the -0.0 < +0.0 rule of the min/max folds.  s[0 .. n-1] is
+ *      the row in that order.
+ *   2. Ranks, on the host in double (they depend on the shape only: nothing is read back from the device): the quantiles are
+ *      q_lo = pct / 100.0 and q_hi = (100.0 - pct) / 100.0, the reference's operands; for each,
+ *      pos = q * (double)(n - 1), k = min(max((int64)floor(pos), 0), n - 1), k1 = min(k + 1, n - 1), t = pos - (double)k.
+ *   3. Interpolation, in double: a = s[k], b = s[k1], d = (double)(float)(b - a) -- the difference is rounded to float32
+ *      first, as numpy does with float32 data; t < 0.5: v = (double)a + d * t, otherwise v = (double)b - d * (1.0 - t);
+ *      the result is (float)v, one rounding.  +-inf follow the formula (inf - inf gives NaN, as in numpy).
+ *   4. NaN: a row that holds a NaN anywhere gives NaN for both lo and hi, as np.percentile does; other rows are unaffected.
+ * The result is a function of the row's multiset of values only: deterministic, independent of the launch geometry.
+ * Rows up to fp8q_percentile_resident_max_inner() elements are selected from an LDS copy in one launch and need no
+ * workspace (ws may be NULL with ws_bytes == 0).  Longer rows take three counting passes over x (11 + 11 + 10 key bits) with
+ * a tiny launch after each -- six launches and one memset node, none waits on another -- and need
+ * fp8q_percentile_workspace_bytes(C, inner) bytes at `ws`, 8-byte aligned; the workspace need not be initialised (the
+ * call clears what it counts into) and holds nothing between calls.
+ * Errors, all reported before any HIP call: FP8Q_EINVAL for null pointers, C < 1 or inner < 1, pct NaN or outside
+ * [0, 100], pointers that are not 4-byte aligned, a missing, misaligned or too small workspace; FP8Q_EUNSUPPORTED for
+ * streaming rows of 2^32 elements or more, or more than 2^30 such rows.
+ * Enqueue-only, no allocation.  FP8Q_VERSION is unchanged: the entries are additive.
+ */
+int64_t fp8q_percentile_resident_max_inner(void);
+size_t fp8q_percentile_workspace_bytes(int64_t C, int64_t inner);
+int fp8q_percentile_f32(const float *x, int64_t C, int64_t inner, double pct, float *lo, float *hi, void *ws, size_t ws_bytes,
+                        fp8q_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
