@@ -351,6 +351,25 @@ __device__ __forceinline__ float quant_direct(float x, const Chan &c, float M)
 //                                     r == 2^(M+1) (rounded up)   ->  exponent code p+1, fraction 0
 //                                     otherwise                   ->  exponent code p, fraction r - 2^M
 // so decode(code) = +/- (fraction + [exp != 0] * 2^M) * s_max(exp,1), the very product K1 forms.
+// the code of K1's integers: r = rint(xc / s_p) with its sign, ls = p as a float
+__device__ __forceinline__ uint32_t code_of_r(float r, float ls, int M, int sign_shift)
+{
+    // r is an integer in [0, 2^(M+1)] unless the channel is degenerate (s = 0 / NaN: K1 gives NaN): code 0
+    if (__builtin_expect(!(fabsf(r) <= (float)(2u << M)), 0)) return 0u;
+    const uint32_t ri = (uint32_t)fabsf(r);
+    const uint32_t m2 = 1u << M;
+    uint32_t e = (uint32_t)ls, f = ri - m2;
+    if (ri < m2) {
+        e = 0u;
+        f = ri;
+    } else if (ri == 2u * m2) {
+        e += 1u;
+        f = 0u;
+    }
+    const uint32_t sign = sign_shift >= 0 ? ((__float_as_uint(r) >> 31) << sign_shift) : 0u;
+    return sign | (e << M) | f;
+}
+
 __device__ __forceinline__ uint32_t encode_one(float x, const ChanLite &c, const float2 *lut, float pmaxf,
                                                float qthr, int M, int sign_shift)
 {
@@ -372,20 +391,25 @@ __device__ __forceinline__ uint32_t encode_one(float x, const ChanLite &c, const
         t = lut[(int)ls];
         r = rintf(xc / t.x);
     }
-    // r is an integer in [0, 2^(M+1)] unless the channel is degenerate (s = 0 / NaN: K1 gives NaN): code 0
-    if (__builtin_expect(!(fabsf(r) <= (float)(2u << M)), 0)) return 0u;
-    const uint32_t ri = (uint32_t)fabsf(r);
-    const uint32_t m2 = 1u << M;
-    uint32_t e = (uint32_t)ls, f = ri - m2;
-    if (ri < m2) {
-        e = 0u;
-        f = ri;
-    } else if (ri == 2u * m2) {
-        e += 1u;
-        f = 0u;
-    }
-    const uint32_t sign = sign_shift >= 0 ? ((__float_as_uint(r) >> 31) << sign_shift) : 0u;
-    return sign | (e << M) | f;
+    return code_of_r(r, ls, M, sign_shift);
+}
+
+// encode_one() for a caller without a table (scalars around a chunk, rows too short to amortise one): the scale of the
+// binade is the table's own entry, computed on the spot, and the division is the IEEE one -- what encode_one()'s fast path
+// is proven equal to -- so the code is the one encode_one() gives with the channel's table.
+__device__ __forceinline__ uint32_t encode_direct(float x, const Chan &c, const QFmt &f, int sign_shift)
+{
+    if (x != x) return 0u;
+    const float xc = __builtin_amdgcn_fmed3f(x, c.minv, c.maxv);
+    const float a = fabsf(xc);
+    const float v = __builtin_amdgcn_logf(a) + c.bias;
+    float fl = floorf(v);
+    const float fr = v - fl;
+    const bool risky = __builtin_amdgcn_classf(x, 0x90) | (fabsf(fr - 0.5f) > c.pthr) | (c.pthr < 0.0f);
+    if (__builtin_expect(risky, 0)) fl = floorf(log2_tab(a, kFastTab) + c.bias);
+    const float ls = __builtin_amdgcn_fmed3f(fl, 1.0f, (float)f.pmax);
+    const float r = rintf(xc / lut_entry(c, (int)ls, f.M).x);
+    return code_of_r(r, ls, (int)f.M, sign_shift);
 }
 
 // Four elements of one channel -> their four codes packed into a dword (byte k = element k): one rare-case branch for
@@ -394,8 +418,11 @@ __device__ __forceinline__ uint32_t encode_one(float x, const ChanLite &c, const
 // covers all three cases of encode_one(): ri < 2^M happens only for p == 1 and gives (0, ri); ri == 2^(M+1) carries into
 // the exponent and gives (p + 1, 0); otherwise (p, ri - 2^M).  Degenerate channels (s = 0 / NaN: K1 gives NaN, r is not
 // an integer in range) and NaN inputs encode as 0, as documented.
-__device__ __forceinline__ uint32_t encode_group4(const float (&v)[4], const ChanLite &c, const float2 *lut, float pmaxf,
-                                                  float qthr, int M, int sign_shift)
+// `rows` names the channel of each element: rows.chan(j) its constants, rows.lut(j) its table (OneRow: the same for all four;
+// a group that straddles a row border selects per element, fp8q_codec_h16.hip).
+template <class Rows>
+__device__ __forceinline__ uint32_t encode_group4_of(const float (&v)[4], const Rows &rows, float pmaxf, float qthr, int M,
+                                                     int sign_shift)
 {
     // The field (p << M) + |r| - 2^M is formed in FLOAT -- the binade index is there as a float (ls), r is a finite
     // integer in [0, 2^(M+1)] unless `any` ends up set -- and v_cvt_pk_u8_f32 converts it and places it in its byte in one
@@ -403,23 +430,26 @@ __device__ __forceinline__ uint32_t encode_group4(const float (&v)[4], const Cha
     // -0 keeps its sign: encode_one), so the four sign bits come from the top bytes of the inputs with two v_perm_b32.
     const float m2f = (float)(1u << M);
     float cf[4];
-    bool any = c.pthr < 0.0f;
+    bool any = rows.always_exact();
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
+        const ChanLite &c = rows.chan(j);
         const float xc = __builtin_amdgcn_fmed3f(v[j], c.minv, c.maxv);
         const float w = __builtin_amdgcn_logf(fabsf(xc)) + c.bias;
         const float fl = floorf(w);
         const float fr = w - fl;
         const float ls = __builtin_amdgcn_fmed3f(fl, 1.0f, pmaxf);
-        const float2 t = lut[(int)ls];
+        const float2 t = rows.lut(j)[(int)ls];
         const float q0 = xc * t.y;
         const float r = rintf(q0);
         cf[j] = fmaf(ls, m2f, fabsf(r)) - m2f;
         any |= __builtin_amdgcn_classf(v[j], 0x93) | (fabsf(fr - 0.5f) > c.pthr) | (fabsf(q0 - r) > qthr);
     }
     if (__builtin_expect(any, 0))   // rare: the exact path decides every element of the group (NaN inputs, degenerate channels)
-        return encode_one(v[0], c, lut, pmaxf, qthr, M, sign_shift) | (encode_one(v[1], c, lut, pmaxf, qthr, M, sign_shift) << 8) |
-               (encode_one(v[2], c, lut, pmaxf, qthr, M, sign_shift) << 16) | (encode_one(v[3], c, lut, pmaxf, qthr, M, sign_shift) << 24);
+        return encode_one(v[0], rows.chan(0), rows.lut(0), pmaxf, qthr, M, sign_shift) |
+               (encode_one(v[1], rows.chan(1), rows.lut(1), pmaxf, qthr, M, sign_shift) << 8) |
+               (encode_one(v[2], rows.chan(2), rows.lut(2), pmaxf, qthr, M, sign_shift) << 16) |
+               (encode_one(v[3], rows.chan(3), rows.lut(3), pmaxf, qthr, M, sign_shift) << 24);
     uint32_t word = 0u;
 #pragma unroll
     for (int j = 0; j < 4; ++j) word = __builtin_amdgcn_cvt_pk_u8_f32(cf[j], j, word);
@@ -431,6 +461,20 @@ __device__ __forceinline__ uint32_t encode_group4(const float (&v)[4], const Cha
     return word;
 }
 
+struct OneRow {
+    const ChanLite &c;
+    const float2 *l;
+    __device__ __forceinline__ bool always_exact() const { return c.pthr < 0.0f; }
+    __device__ __forceinline__ const ChanLite &chan(int) const { return c; }
+    __device__ __forceinline__ const float2 *lut(int) const { return l; }
+};
+
+__device__ __forceinline__ uint32_t encode_group4(const float (&v)[4], const ChanLite &c, const float2 *lut, float pmaxf,
+                                                  float qthr, int M, int sign_shift)
+{
+    return encode_group4_of(v, OneRow{c, lut}, pmaxf, qthr, M, sign_shift);
+}
+
 __device__ __forceinline__ float decode_one(uint32_t code, const float2 *lut, int M, int sign_shift)
 {
     const uint32_t m2 = 1u << M;
@@ -438,6 +482,18 @@ __device__ __forceinline__ float decode_one(uint32_t code, const float2 *lut, in
     const uint32_t e = body >> M, f = body & (m2 - 1u);
     const float r = (float)(f + (e ? m2 : 0u));
     const float y = r * lut[e ? e : 1u].x;
+    return (sign_shift >= 0 && ((code >> sign_shift) & 1u)) ? -y : y;
+}
+
+// decode_one() for a caller without a table: the scale is the table's own entry, computed on the spot
+__device__ __forceinline__ float decode_direct(uint32_t code, const Chan &c, float Mf, int sign_shift)
+{
+    const int M = (int)Mf;
+    const uint32_t m2 = 1u << M;
+    const uint32_t body = sign_shift >= 0 ? (code & ((1u << sign_shift) - 1u)) : code;
+    const uint32_t e = body >> M, f = body & (m2 - 1u);
+    const float r = (float)(f + (e ? m2 : 0u));
+    const float y = r * lut_entry(c, (int)(e ? e : 1u), Mf).x;
     return (sign_shift >= 0 && ((code >> sign_shift) & 1u)) ? -y : y;
 }
 

@@ -40,22 +40,6 @@ namespace {
 typedef uint32_t vu4 __attribute__((ext_vector_type(4)));
 typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
 
-// the two's-complement bits of an element's level (the caller keeps the low 8 or 16)
-__device__ __forceinline__ uint32_t code_of(float v, const float4 k, float lo, float hi)
-{
-    float t = int_level(v, k, lo, hi);
-    t = (t != t) ? k.z : t;
-    t = (t != t) ? 0.0f : t;
-    return (uint32_t)(int)t;      // an integer in [-32768, 65535]: the conversion is exact
-}
-
-template <int W>
-__device__ __forceinline__ float value_of(uint32_t code, bool sgn, const float4 k)
-{
-    const int iv = sgn ? (W == 1 ? (int)(int8_t)code : (int)(int16_t)code) : (int)code;
-    return k.x * ((float)iv - k.z);
-}
-
 // a code, and the word of a 4-element group's codes
 template <int W>
 struct CodeType {

@@ -1,9 +1,10 @@
 // fp8q_intq.h -- what the uniform quantizers' forward (fp8q_int.hip; fp8q_inth16.hip on fp16 / bf16 tensors), backward
-// (fp8q_intgrad.hip) and integer codes (fp8q_intcodec.hip) share: torch's min / max / clamp, the integer grid of n bits, the
-// channel constants, the integer level and the quantized value of an element, a row's range from (x_min, x_max), and the
-// geometry of the chunked kernels (k_int_quant, k_inth16_quant, k_int_level, k_int_encode, k_int_decode): one aligned
-// 4096-element chunk per block, its prologue (sign, grid ends, the channel constants in LDS, the channel of an element by
-// magic division), the fp32 -> fp32 streaming loop, and the host side of their launch.  Internal linkage, as fp8q_common.h.
+// (fp8q_intgrad.hip) and integer codes (fp8q_intcodec.hip; fp8q_codec_h16.hip on fp16 / bf16 tensors) share: torch's
+// min / max / clamp, the integer grid of n bits, the channel constants, the integer level and the quantized value of an
+// element, the code of an element and the value of a code, a row's range from (x_min, x_max), and the geometry of the
+// chunked kernels (k_int_quant, k_inth16_quant, k_int_level, k_int_encode, k_int_decode): one aligned 4096-element chunk
+// per block, its prologue (sign, grid ends, the channel constants in LDS, the channel of an element by magic division),
+// the fp32 -> fp32 streaming loop, and the host side of their launch.  Internal linkage, as fp8q_common.h.
 #pragma once
 #include "fp8q_common.h"
 
@@ -75,6 +76,24 @@ __device__ __forceinline__ float int_one(float v, const float4 k, float lo, floa
 {
     const float t = int_level(v, k, lo, hi);
     return k.x * (t - k.z);
+}
+
+// ---- the integer codes (fp8q_intcodec.hip; fp8q_codec_h16.hip on fp16 / bf16 tensors) ----
+// the two's-complement bits of an element's level (the caller keeps the low 8 or 16)
+__device__ __forceinline__ uint32_t code_of(float v, const float4 k, float lo, float hi)
+{
+    float t = int_level(v, k, lo, hi);
+    t = (t != t) ? k.z : t;
+    t = (t != t) ? 0.0f : t;
+    return (uint32_t)(int)t;      // an integer in [-32768, 65535]: the conversion is exact
+}
+
+// the value of a code of W bytes, read as signed when sgn
+template <int W>
+__device__ __forceinline__ float value_of(uint32_t code, bool sgn, const float4 k)
+{
+    const int iv = sgn ? (W == 1 ? (int)(int8_t)code : (int)(int16_t)code) : (int)code;
+    return k.x * ((float)iv - k.z);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -107,6 +107,10 @@ SIGNATURES = {
     "fp8q_int_range_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "fp8q_int_minmax_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp,
                                           ctypes.c_size_t, _vp]),
+    "fp8q_encode_h16": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _i64, _f, _i, _i, _vp]),
+    "fp8q_decode_h16": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _i64, _f, _i, _i, _vp]),
+    "fp8q_int_encode_h16": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _vp, _i64, _vp, _i, _i, _f, _vp]),
+    "fp8q_int_decode_h16": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _vp, _i64, _vp, _i, _i, _f, _vp]),
     "fp8q_quantize_bwd_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _f, _vp, _i, _i, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "fp8q_quantize_bwd_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
     "fp8q_int_quantize_bwd_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i, _i, _f, _i64, _vp, _vp, _vp,

@@ -136,6 +136,20 @@ def _check_out_dtype(x, out_dtype):
         raise Fp8qError(f"out_dtype: a {x.dtype} input gives a {x.dtype} result (float16 / bfloat16 inputs: float32 or their own)")
 
 
+_VALUES = (torch.float32,) + _HALF     # what the storage codes are made from and decoded to
+
+
+def _decode_out_dtype(out, out_dtype):
+    """result dtype of a decode: out.dtype when `out` is given, else out_dtype, else float32; codes carry no dtype of their
+    own, so float32 and both half types exist.  Argument errors come before the device check, as in _half_out_dtype."""
+    dt = out.dtype if isinstance(out, torch.Tensor) else (torch.float32 if out_dtype is None else out_dtype)
+    if dt not in _VALUES:
+        raise Fp8qError(f"decoded values are float32 or float16 / bfloat16, not {dt}")
+    if out is not None and out_dtype is not None and out_dtype != dt:
+        raise Fp8qError(f"out is {dt} but out_dtype is {out_dtype}")
+    return dt
+
+
 def _quantize_h16(x, maxval, mbits, n_bits, sign_bits, out, out_dtype):
     """K1 on float16 / bfloat16 (fp8q_quantize_h16): x widened exactly, the fp32 contract, the result stored as float32
     or rounded once to x.dtype"""
@@ -781,20 +795,22 @@ def _int_code_dtype(n_bits):
     return torch.uint8 if int(n_bits) <= 8 else torch.int16
 
 
-def _int_codec(fn, x, in_dtype, out_dtype, delta, zero_float, signed_flag, n_bits, symmetric, eps, out):
-    """The launch shared by int_to_integer / int_encode / int_decode: int_quantize's checks, one kernel."""
-    _require(x, "codes" if in_dtype is not torch.float32 else "x", in_dtype)
+def _int_codec(fn, x, name, in_dtype, out_dtype, delta, zero_float, signed_flag, n_bits, symmetric, eps, out, half=None):
+    """The launch shared by int_to_integer / int_encode / int_decode: int_quantize's checks, one kernel.  `half`: the
+    float16 / bfloat16 side of an _h16 entry point, whose FP8Q_DT_* follows the two tensors."""
+    _require(x, name, in_dtype)
     delta = delta.detach().reshape(-1)
     n = delta.numel()
     zero_float = zero_float.detach().reshape(-1) if zero_float is not None else None
     signed_flag = signed_flag.detach().reshape(-1) if signed_flag is not None else None
     pd, pz, ps = _int_ptrs(x, delta, zero_float, signed_flag, symmetric, n)
-    xk, y, C, inner, res = _int_x(x, out, n, None if out_dtype is in_dtype else out_dtype)
+    xk, y, C, inner, res = _int_x(x, out, n, None if out_dtype is x.dtype else out_dtype)
     if xk.numel() == 0:
         return res
+    types = () if half is None else (_DT[half],)
     with _on_device(xk):
-        rc = getattr(lib(), fn)(xk.data_ptr(), y.data_ptr(), C, inner, pd, pz, n, ps, int(n_bits), int(bool(symmetric)),
-                                float(eps), _stream(xk))
+        rc = getattr(lib(), fn)(xk.data_ptr(), y.data_ptr(), *types, C, inner, pd, pz, n, ps, int(n_bits),
+                                int(bool(symmetric)), float(eps), _stream(xk))
     check(rc, fn)
     return res
 
@@ -804,7 +820,7 @@ def int_to_integer(x, delta, zero_float=None, signed_flag=None, n_bits=8, symmet
     t = clamp(rint(x / scale) + zp, int_min, int_max), bit for bit the eager CUDA chain; NaN stays NaN, a zero level is +0
     (torch's CPU clamp keeps the -0 that -0 + -0 gives when zero_float is -0; its CUDA clamp does not).  Arguments as
     int_quantize.  One launch."""
-    return _int_codec("fp8q_int_to_integer_f32", x, torch.float32, torch.float32, delta, zero_float, signed_flag, n_bits,
+    return _int_codec("fp8q_int_to_integer_f32", x, "x", torch.float32, torch.float32, delta, zero_float, signed_flag, n_bits,
                       symmetric, eps, out)
 
 
@@ -814,16 +830,27 @@ def int_encode(x, delta, zero_float=None, signed_flag=None, n_bits=8, symmetric=
     (its codes of -2^(n-1) .. -1 read as 256 - |t| through uint8), and UNSIGNED 16-bit codes of 32768 and above read as
     negative numbers through int16 (add 65536, or widen and mask with 0xffff).  NaN inputs store the code of the value 0
     (zp, or 0 when symmetric).  int_decode(int_encode(x)) == int_quantize(x) bit for bit wherever x is not NaN.
-    Arguments as int_quantize.  One launch."""
-    return _int_codec("fp8q_int_encode", x, torch.float32, _int_code_dtype(n_bits), delta, zero_float, signed_flag, n_bits,
+    Arguments as int_quantize.  One launch.
+    x float16 / bfloat16 (fp8q_int_encode_h16): x widened exactly, the same codes as int_encode(x.float())."""
+    if isinstance(x, torch.Tensor) and x.dtype in _HALF:
+        return _int_codec("fp8q_int_encode_h16", x, "x", _HALF, _int_code_dtype(n_bits), delta, zero_float, signed_flag,
+                          n_bits, symmetric, eps, out, half=x.dtype)
+    _require(x, "x", _VALUES)
+    return _int_codec("fp8q_int_encode", x, "x", torch.float32, _int_code_dtype(n_bits), delta, zero_float, signed_flag, n_bits,
                       symmetric, eps, out)
 
 
-def int_decode(codes, delta, zero_float=None, signed_flag=None, n_bits=8, symmetric=False, eps=1e-8, out=None):
-    """float32 values of int_encode's codes (uint8 for n_bits <= 8, int16 for 9..16): y = scale * (code - zp), the code read
-    as signed exactly when the quantizer is symmetric and its device sign flag is set.  One launch."""
-    return _int_codec("fp8q_int_decode", codes, _int_code_dtype(n_bits), torch.float32, delta, zero_float, signed_flag,
-                      n_bits, symmetric, eps, out)
+def int_decode(codes, delta, zero_float=None, signed_flag=None, n_bits=8, symmetric=False, eps=1e-8, out=None,
+               out_dtype=None):
+    """Values of int_encode's codes (uint8 for n_bits <= 8, int16 for 9..16): y = scale * (code - zp), the code read as
+    signed exactly when the quantizer is symmetric and its device sign flag is set.  float32 unless a float16 / bfloat16
+    `out` or out_dtype asks for a half type (fp8q_int_decode_h16): the float32 value rounded once.  One launch."""
+    dt = _decode_out_dtype(out, out_dtype)
+    if dt in _HALF:
+        return _int_codec("fp8q_int_decode_h16", codes, "codes", _int_code_dtype(n_bits), dt, delta, zero_float, signed_flag,
+                          n_bits, symmetric, eps, out, half=dt)
+    return _int_codec("fp8q_int_decode", codes, "codes", _int_code_dtype(n_bits), torch.float32, delta, zero_float,
+                      signed_flag, n_bits, symmetric, eps, out)
 
 
 def int_quantize_backward(x, g, delta, zero_float=None, signed_flag=None, n_bits=8, symmetric=False, eps=1e-8, need_gx=True,
@@ -1373,8 +1400,9 @@ def mse_grid_f64(x, per_channel, grid, mbits_list, n_bits, sign_bits, out, reduc
 
 
 def encode(x, maxval, mbits, n_bits=8, sign_bits=1, out=None):
-    """N3: uint8 storage codes of quantize(x) ([sign | exponent | fraction], fp8_quantizer.py:13-41)."""
-    _require(x, "x")
+    """N3: uint8 storage codes of quantize(x) ([sign | exponent | fraction], fp8_quantizer.py:13-41).
+    x float16 / bfloat16 (fp8q_encode_h16): x widened exactly, the same codes as encode(x.float())."""
+    _require(x, "x", _VALUES)
     _require(maxval, "maxval", like=x)
     x = x.contiguous()
     maxval = maxval.contiguous().view(-1)
@@ -1383,6 +1411,14 @@ def encode(x, maxval, mbits, n_bits=8, sign_bits=1, out=None):
     if n_mv != 1 and n_mv != C:
         raise Fp8qError(f"maxval has {n_mv} elements, expected 1 or {C}")
     codes = _out(out, x, torch.uint8)
+    if x.dtype in _HALF:
+        if x.numel() == 0:      # (nothing to launch: fp8q_encode_u8 answers FP8Q_OK here, the _h16 entries refuse empty shapes)
+            return codes
+        with _on_device(x):
+            rc = lib().fp8q_encode_h16(x.data_ptr(), codes.data_ptr(), _DT[x.dtype], C, inner, maxval.data_ptr(), n_mv,
+                                       float(mbits), int(n_bits), int(sign_bits), _stream(x))
+        check(rc, "fp8q_encode_h16")
+        return codes
     with _on_device(x):
         rc = lib().fp8q_encode_u8(x.data_ptr(), codes.data_ptr(), C, inner, maxval.data_ptr(), n_mv, float(mbits),
                                   int(n_bits), int(sign_bits), _stream(x))
@@ -1390,10 +1426,13 @@ def encode(x, maxval, mbits, n_bits=8, sign_bits=1, out=None):
     return codes
 
 
-def decode(codes, maxval, mbits, n_bits=8, sign_bits=1, out=None):
-    """N3: fp32 values of uint8 storage codes; decode(encode(x)) == quantize(x) bit for bit when the channel's
+def decode(codes, maxval, mbits, n_bits=8, sign_bits=1, out=None, out_dtype=None):
+    """N3: values of uint8 storage codes; decode(encode(x)) == quantize(x) bit for bit when the channel's
     scale table is exactly geometric in fp32 (all weight-sized ranges), else within a few ULP (<= 5e-6 relative) on elements that round up
-    into the next binade (see include/fp8q.h)."""
+    into the next binade (see include/fp8q.h).  float32 unless a float16 / bfloat16 `out` or out_dtype asks for a half type
+    (fp8q_decode_h16): the float32 value rounded once, so decode(encode(x), out_dtype=x.dtype) == quantize(x,
+    out_dtype=x.dtype) under the same condition."""
+    dt = _decode_out_dtype(out, out_dtype)
     if not isinstance(codes, torch.Tensor) or not codes.is_cuda or codes.dtype != torch.uint8:
         raise Fp8qError("codes must be a CUDA(HIP) uint8 tensor")
     _require(maxval, "maxval", like=codes)
@@ -1403,7 +1442,15 @@ def decode(codes, maxval, mbits, n_bits=8, sign_bits=1, out=None):
     C, inner = _rows(codes, n_mv != 1)
     if n_mv != 1 and n_mv != C:
         raise Fp8qError(f"maxval has {n_mv} elements, expected 1 or {C}")
-    y = _out(out, codes, torch.float32)
+    y = _out(out, codes, dt)
+    if dt in _HALF:
+        if codes.numel() == 0:  # (as in encode: the same empty result as the float32 route)
+            return y
+        with _on_device(codes):
+            rc = lib().fp8q_decode_h16(codes.data_ptr(), y.data_ptr(), _DT[dt], C, inner, maxval.data_ptr(), n_mv,
+                                       float(mbits), int(n_bits), int(sign_bits), _stream(codes))
+        check(rc, "fp8q_decode_h16")
+        return y
     with _on_device(codes):
         rc = lib().fp8q_decode_u8(codes.data_ptr(), y.data_ptr(), C, inner, maxval.data_ptr(), n_mv, float(mbits),
                                   int(n_bits), int(sign_bits), _stream(codes))

@@ -214,7 +214,8 @@ def export_fp8_weights(model):
     layer whose weights go through an FP8 quantizer with fixed ranges: the 1-byte storage form of what the layer
     computes with (the reference only simulates the format; its enumerator
     fp8_quantizer.py:13-41 defines the byte layout).  decode(codes) == the layer's quantized weight (bit for bit for weight-sized
-    ranges; within a few ULP on round-ups into the next binade otherwise, see include/fp8q.h)."""
+    ranges; within a few ULP on round-ups into the next binade otherwise, see include/fp8q.h).  float16 / bfloat16 weights are
+    encoded as they are (fp8q_encode_h16: the codes of the exactly widened weight, no float32 copy)."""
     import torch
 
     import fp8q
@@ -241,11 +242,12 @@ def export_fp8_weights(model):
     return out
 
 
-def decode_fp8_weights(exported, device="cuda"):
-    """{layer name: fp32 tensor} from export_fp8_weights(): the values the layers compute with."""
+def decode_fp8_weights(exported, device="cuda", dtype=None):
+    """{layer name: tensor} from export_fp8_weights(): the values the layers compute with, float32 or `dtype` (float16 /
+    bfloat16: what a model of that dtype built with keep_dtype=True computes with)."""
     import fp8q
     return {name: fp8q.ops.decode(e["codes"].to(device), e["maxval"].to(device), e["mantissa_bits"], e["n_bits"],
-                                  e["sign_bits"]) for name, e in exported.items()}
+                                  e["sign_bits"], out_dtype=dtype) for name, e in exported.items()}
 
 
 def export_int_weights(model):
@@ -253,7 +255,8 @@ def export_int_weights(model):
     weights go through a uniform (INT) quantizer with fixed ranges -- the twin of export_fp8_weights: the integers the
     layer's quantized weight stands for (uint8 up to 8 bits, int16 beyond: raw two's-complement bits, see
     fp8q.ops.int_encode) with the ranges that turn them back, all as CPU tensors.  decode(codes) == the layer's quantized
-    weight bit for bit.  The symmetric sign flag is copied to the host here, once per layer; the kernels never do."""
+    weight bit for bit.  The symmetric sign flag is copied to the host here, once per layer; the kernels never do.
+    float16 / bfloat16 weights of quantizers built with keep_dtype=True are encoded as they are (fp8q_int_encode_h16)."""
     from .layers import QuantizationHijacker
     from .manager import Qstates
     from .uniform import AsymmetricUniformQuantizer
@@ -278,14 +281,16 @@ def export_int_weights(model):
     return out
 
 
-def decode_int_weights(exported, device="cuda"):
-    """{layer name: fp32 tensor} from export_int_weights(): the values the layers compute with."""
+def decode_int_weights(exported, device="cuda", dtype=None):
+    """{layer name: tensor} from export_int_weights(): the values the layers compute with, float32 or `dtype` (float16 /
+    bfloat16: what a model of that dtype built with keep_dtype=True computes with)."""
     import fp8q
 
     def dev(t):
         return None if t is None else t.to(device)
     return {name: fp8q.ops.int_decode(e["codes"].to(device), dev(e["delta"]), dev(e["zero_float"]), dev(e["signed"]),
-                                      e["n_bits"], e["symmetric"], e["eps"]) for name, e in exported.items()}
+                                      e["n_bits"], e["symmetric"], e["eps"], out_dtype=dtype)
+            for name, e in exported.items()}
 
 
 class GraphedForward:

@@ -15,8 +15,12 @@ the kernel path only (they raise elsewhere, FP8Q_INT_KERNELS=0 included).
 float16 / bfloat16 tensors (csrc/fp8q_inth16.hip): a quantizer built with `keep_dtype=True` runs `forward` and the
 range-setting forwards on the half kernels under the same conditions and returns x's dtype -- x widened exactly, the fp32
 chain, one rounding back; the ranges stay float32.  Under autograd or with learned ranges such an x is widened, takes the
-float32 route above and the result is cast back.  Without keep_dtype a half tensor is the eager chain, as ever.  The integer
-codes stay float32-only.
+float32 route above and the result is cast back.  Without keep_dtype a half tensor is the eager chain, as ever.
+
+The integer codes of half tensors (csrc/fp8q_codec_h16.hip): with `keep_dtype=True`, `encode` takes a float16 / bfloat16
+tensor under forward's kernel conditions (the codes of the exactly widened tensor) and `decode(codes, out_dtype=...)` returns
+float16 / bfloat16 values (the float32 value rounded once), so decode(encode(x), out_dtype=x.dtype) == forward(x) bit for bit
+wherever x is not NaN.  `to_integer_forward` stays float32-only.
 """
 import os
 
@@ -316,20 +320,24 @@ class AsymmetricUniformQuantizer(QuantizerBase):
 
     def encode(self, x_float):
         """The integers of forward(x) as storage codes (fp8q.ops.int_encode: uint8 up to 8 bits, int16 beyond, raw
-        two's-complement bits).  Kernel path only -- the conditions of forward's; anything else raises."""
-        if not self._fixed_kernel_ok(x_float):
-            raise _ops.Fp8qError("encode needs the INT kernels: a CUDA float32 tensor without a gradient, fixed float32 range "
-                                 "buffers on its device, the linear scale domain, and FP8Q_INT_KERNELS not 0")
+        two's-complement bits).  Kernel path only -- the conditions of forward's, a float16 / bfloat16 tensor with keep_dtype
+        included; anything else raises."""
+        d = self._delta
+        if not (self._fixed_kernel_ok(x_float, x_like=False) and self._kernel_x_ok(x_float, d.numel(), half_ok=True)):
+            raise _ops.Fp8qError("encode needs the INT kernels: a CUDA float32 tensor (float16 / bfloat16 with keep_dtype) "
+                                 "without a gradient, fixed float32 range buffers on its device, the linear scale domain, and "
+                                 "FP8Q_INT_KERNELS not 0")
         return _ops.int_encode(x_float, *self._range_args())
 
-    def decode(self, codes):
-        """float32 values of encode()'s codes: decode(encode(x)) == forward(x) bit for bit wherever x is not NaN."""
+    def decode(self, codes, out_dtype=None):
+        """Values of encode()'s codes, float32 or out_dtype (float16 / bfloat16: the float32 value rounded once):
+        decode(encode(x)) == forward(x) bit for bit wherever x is not NaN."""
         d = self._delta
         if not (self._fixed_kernel_ok(codes, x_like=False) and codes.is_cuda and not codes.is_floating_point()
                 and (d.numel() == 1 or (self.per_channel and codes.dim() > 0 and codes.shape[0] == d.numel()))):
             raise _ops.Fp8qError("decode needs the INT kernels: CUDA integer codes, fixed float32 range buffers on their "
                                  "device, the linear scale domain, and FP8Q_INT_KERNELS not 0")
-        return _ops.int_decode(codes, *self._range_args())
+        return _ops.int_decode(codes, *self._range_args(), out_dtype=out_dtype)
 
     def forward(self, x_float, *args, **kwargs):
         d = self._delta

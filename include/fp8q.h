@@ -621,6 +621,47 @@ int fp8q_int_minmax_quantize_h16(const void *x, void *y, int x_type, int y_type,
                                  float *row_max, float *delta, float *zero_float, unsigned char *signed_flag, int n_bits,
                                  int symmetric, float eps, void *ws, size_t ws_bytes, fp8q_stream_t stream);
 
+/*
+ * Storage codes of the half-precision lane (csrc/fp8q_codec_h16.hip): fp8q_encode_u8 / fp8q_decode_u8 and fp8q_int_encode /
+ * fp8q_int_decode straight from and to IEEE fp16 and bfloat16 tensors -- the argument lists of those twins, with x_type /
+ * y_type behind (x, codes) and (codes, y) as in fp8q_quantize_h16.  x_type / y_type is FP8Q_DT_F16 or FP8Q_DT_BF16; float32
+ * values stay with the existing entry points.  Arithmetic contract:
+ *   - every half input is widened to fp32 exactly, as the half-precision lane above does it: fp16 subnormals become normal
+ *     numbers, bf16 is the upper half of an fp32 word, nothing is flushed.  From there the fp32 code runs unchanged, through
+ *     the same device functions (the channel constants and scale tables, the encode assembly, the INT chain with its
+ *     reciprocal-then-redo rule);
+ *   - fp8q_encode_h16(x) == fp8q_encode_u8(widen(x)) byte for byte: NaN inputs and degenerate channels (maxval 0, inf or NaN)
+ *     encode as 0; formats with n_bits > 8 or no exponent bit return FP8Q_EUNSUPPORTED;
+ *   - fp8q_decode_h16(codes, y_type) takes the fp32 value of fp8q_decode_u8 and rounds it ONCE to y_type (round to nearest
+ *     even, overflow to infinity: torch.Tensor.to(dtype)).  The fp32 value exists before it is narrowed -- the multiplication
+ *     and the conversion are never fused into one rounding;
+ *   - fp8q_int_encode_h16(x) == fp8q_int_encode(widen(x)): one byte for n_bits <= 8, two bytes (little endian) for 9..16, the
+ *     same NaN and sign rules;
+ *   - fp8q_int_decode_h16 takes fp8q_int_decode's fp32 value and rounds it once to y_type, in the same way.
+ * Consequences: fp8q_decode_h16(fp8q_encode_h16(x), T) == fp8q_quantize_h16(x, y_type = T) bit for bit wherever the fp32
+ * round trip equals K1 (the geometric-scale condition stated at fp8q_decode_u8: all weight-sized ranges); for INT,
+ * fp8q_int_decode_h16(fp8q_int_encode_h16(x), T) == fp8q_int_quantize_h16(x, y_type = T) wherever x is not NaN.
+ * Pointers need only natural alignment (2 bytes for halves and 2-byte INT codes, 1 byte for 1-byte codes); views at any
+ * element offset, the codes need not share x's phase against the 16-byte grid; rows of any length (rows shorter than 8
+ * elements and odd row lengths included).
+ * Errors, all reported before any launch: FP8Q_EINVAL for null pointers, EMPTY tensors (C or inner <= 0), n_maxval / n_delta
+ * not in {1, C}, a type that is not a half type, an odd address of a 2-byte element (2-byte INT codes included) and the size
+ * limits of the twins (FP8: those of fp8q_quantize_h16; INT: those of fp8q_int_encode); FP8Q_EUNSUPPORTED as above, and for
+ * INT n_bits outside [2, 16].
+ * Each is ONE launch: enqueue-only, no allocation, no workspace.  HBM traffic: 3 B / element each way, 4 B with 2-byte INT
+ * codes.  FP8Q_VERSION is unchanged: the entries are additive.
+ */
+int fp8q_encode_h16(const void *x, uint8_t *codes, int x_type, int64_t C, int64_t inner, const float *maxval,
+                    int64_t n_maxval, float mbits, int n_bits, int sign_bits, fp8q_stream_t stream);
+int fp8q_decode_h16(const uint8_t *codes, void *y, int y_type, int64_t C, int64_t inner, const float *maxval,
+                    int64_t n_maxval, float mbits, int n_bits, int sign_bits, fp8q_stream_t stream);
+int fp8q_int_encode_h16(const void *x, void *codes, int x_type, int64_t C, int64_t inner, const float *delta,
+                        const float *zero_float, int64_t n_delta, const unsigned char *signed_flag, int n_bits,
+                        int symmetric, float eps, fp8q_stream_t stream);
+int fp8q_int_decode_h16(const void *codes, void *y, int y_type, int64_t C, int64_t inner, const float *delta,
+                        const float *zero_float, int64_t n_delta, const unsigned char *signed_flag, int n_bits,
+                        int symmetric, float eps, fp8q_stream_t stream);
+
 /* ---- backward of the FP quantizer (csrc/fp8q_grad.hip) --------------------------------------------------------------------
  * The gradient of quantize_to_fp8_ste_MM (fp8_quantizer.py:105-133) with respect to x, maxval and the mantissa width, in
  * ONE streaming pass over x and the upstream gradient g (contiguous fp32 viewed as [C, inner], the layout rules of
