@@ -97,6 +97,9 @@ SIGNATURES = {
     "fp8q_int_range_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "fp8q_int_minmax_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp,
                                           ctypes.c_size_t, _vp]),
+    "fp8q_int_affine_act_quantize_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "fp8q_int_affine_act_range_quantize_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i,
+                                                    _f, _vp]),
     "fp8q_int_sse_grid_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),
     "fp8q_int_sse_grid_f32": (_i, [_vp, _i64, _i64, _vp, _i64, _i, _i, _i, _f, _vp, _vp, ctypes.c_size_t, _vp]),
     "fp8q_int_sse_grid_f64": (_i, [_vp, _i64, _i64, _vp, _i64, _i, _i, _i, _f, _vp, _vp, ctypes.c_size_t, _vp]),

@@ -1559,9 +1559,8 @@ def affine_act_quantize(x, maxval, mbits, n_bits=8, sign_bits=1, bn=None, residu
     return y
 
 
-def affine_act(x, bn_ab=None, residual=None, act=0, out=None):
-    """act(bn(x) + residual) without a quantizer (fp8q_affine_act_f32): what an MSE estimator behind a BN + activation searches
-    on.  bn_ab: the folded [C, 2] vector of bn_fold(), or None."""
+def _affine_args(x, bn_ab, residual, out):
+    """(x, residual, y, N, C, HW, alpha_beta pointer) of the epilogues that take the folded BN vector (affine_act, the INT fused epilogue)"""
     _require(x, "x")
     x = x.contiguous()
     N, C, HW = _nchw(x)
@@ -1574,12 +1573,57 @@ def affine_act(x, bn_ab=None, residual=None, act=0, out=None):
         _require(bn_ab, "bn_ab", like=x)
         if bn_ab.numel() != 2 * C or not bn_ab.is_contiguous():
             raise Fp8qError("bn_ab must be a contiguous [C, 2] tensor (fp8q.ops.bn_fold)")
-    y = _out(out, x)
+    return x, residual, _out(out, x), N, C, HW, bn_ab.data_ptr() if bn_ab is not None else None
+
+
+def affine_act(x, bn_ab=None, residual=None, act=0, out=None):
+    """act(bn(x) + residual) without a quantizer (fp8q_affine_act_f32): what an MSE estimator behind a BN + activation searches
+    on.  bn_ab: the folded [C, 2] vector of bn_fold(), or None."""
+    x, residual, y, N, C, HW, pab = _affine_args(x, bn_ab, residual, out)
     with _on_device(x):
         rc = lib().fp8q_affine_act_f32(x.data_ptr(), residual.data_ptr() if residual is not None else None, y.data_ptr(), N, C, HW,
-                                       bn_ab.data_ptr() if bn_ab is not None else None, int(act), _stream(x))
+                                       pab, int(act), _stream(x))
     check(rc, "fp8q_affine_act_f32")
     return y
+
+
+def int_affine_act_quantize(x, delta, zero_float, signed_flag, n_bits, symmetric, eps, bn_ab=None, residual=None, act=0,
+                            out=None):
+    """N2 for the uniform quantizers: int_quantize(affine_act(x, bn_ab, residual, act)) in ONE pass
+    (fp8q_int_affine_act_quantize_f32), bit for bit that composition.  Per-tensor ranges only: delta (and zero_float,
+    asymmetric) of one element, signed_flag the symmetric quantizer's device byte; bn_ab: the folded [C, 2] vector of
+    bn_fold() or None; act: 0 none, 1 ReLU, 2 ReLU6.  `out` may be x or residual."""
+    x, residual, y, N, C, HW, pab = _affine_args(x, bn_ab, residual, out)
+    pd, pz, ps = _int_ptrs(x, delta, zero_float, signed_flag, symmetric, 1)      # per tensor: one element each
+    with _on_device(x):
+        rc = lib().fp8q_int_affine_act_quantize_f32(x.data_ptr(), residual.data_ptr() if residual is not None else None,
+                                                    y.data_ptr(), N, C, HW, pab, int(act), pd, pz, ps, int(n_bits),
+                                                    int(bool(symmetric)), float(eps), _stream(x))
+    check(rc, "fp8q_int_affine_act_quantize_f32")
+    return y
+
+
+def int_affine_act_range_quantize(x, x_min, x_max, n_bits, symmetric, eps, delta=None, zero_float=None, signed_flag=None,
+                                  bn_ab=None, residual=None, act=0, out=None):
+    """int_set_range(x_min, x_max) and int_affine_act_quantize in ONE launch (fp8q_int_affine_act_range_quantize_f32): the
+    range-estimating forward behind a BN / residual / activation.  x_min, x_max: one element each.  Returns
+    (y, delta, zero_float, signed_flag) like int_range_quantize; buffers passed in are written in place."""
+    x, residual, y, N, C, HW, pab = _affine_args(x, bn_ab, residual, out)
+    _require(x_min, "x_min", like=x)
+    _require(x_max, "x_max", like=x)
+    x_min, x_max = x_min.detach().contiguous(), x_max.detach().contiguous()
+    if x_min.numel() != 1 or x_max.numel() != 1:
+        raise Fp8qError("the fused epilogue quantizes per tensor: x_min and x_max must have one element")
+    n, delta, zero_float, signed_flag = _int_range_out(x_min, delta, zero_float, signed_flag, symmetric)
+    pd, pz, ps = _int_ptrs(x, delta, zero_float, signed_flag, symmetric, 1)
+    if N == 0:
+        return (y,) + int_set_range(x_min, x_max, n_bits, symmetric, eps, delta, zero_float, signed_flag)
+    with _on_device(x):
+        rc = lib().fp8q_int_affine_act_range_quantize_f32(
+            x.data_ptr(), residual.data_ptr() if residual is not None else None, y.data_ptr(), N, C, HW, pab, int(act),
+            x_min.data_ptr(), x_max.data_ptr(), pd, pz, ps, int(n_bits), int(bool(symmetric)), float(eps), _stream(x))
+    check(rc, "fp8q_int_affine_act_range_quantize_f32")
+    return y, delta, zero_float, signed_flag
 
 
 def affine_act_minmax(x, cur_min=None, cur_max=None, mode=FOLD_CURRENT, momentum=0.9, bn=None, residual=None,

@@ -11,6 +11,9 @@ it (:114-122) -- but picks the cheapest kernel sequence for it:
   INT (uniform) quantizer, min/max estimator         -> the estimator's launch + 1 (fp8q_int_range_quantize_f32);
                            per-channel current_minmax -> 2 launches (fp8q_int_minmax_quantize_f32)
   INT, fixed ranges                                  -> 1 launch  (fp8q_int_quantize_f32)
+  INT built with fuse_epilogue, behind BN / residual / activation (forward_fused)
+                                                     -> the epilogue's min/max launch + 1 (fp8q_int_affine_act_range_quantize_f32)
+                                                        when estimating, 1 launch (fp8q_int_affine_act_quantize_f32) when fixed
   anything else (custom estimator / quantizer)       -> the generic protocol calls
 
 float16 / bfloat16 inputs take the same FP8 min/max routes on the half-precision kernels (fp8q_minmax_h16,
@@ -165,10 +168,26 @@ class QuantizationManager(nn.Module):
     def can_fuse(self, x):
         """True when quantize(act(bn(x) + residual)) can run as ONE kernel with the same result as the
         unfused chain: FP8 per-tensor quantizer on a contiguous CUDA fp32 [N, C, ...] tensor, ranges
-        fixed or followed by a plain min/max estimator."""
+        fixed or followed by a plain min/max estimator -- or a uniform (INT) per-tensor quantizer built with
+        fuse_epilogue=True under its kernel conditions (linear domain, fp32 range buffers, FP8Q_INT_KERNELS not 0),
+        ranges fixed or followed by a plain min/max estimator; line search, learned ranges, autograd, half tensors, the log
+        domain and custom discretizers keep the unfused chain."""
         import os
         q, est = self.quantizer, self.range_estimator
-        if os.environ.get("FP8Q_FUSE_EPILOGUE", "1") == "0" or type(q) is not FPQuantizer or self.per_channel:
+        if os.environ.get("FP8Q_FUSE_EPILOGUE", "1") == "0" or self.per_channel:
+            return False
+        if type(q) in _UNIFORM:
+            if not (getattr(q, "fuse_epilogue", False) and isinstance(x, torch.Tensor) and x.is_cuda
+                    and x.dtype == torch.float32 and x.dim() >= 2 and x.is_contiguous() and not x.requires_grad
+                    and q._kernel_common(x.device) and _ops.affine_act_supported(x)):
+                return False
+            if isinstance(q._delta, nn.Parameter) or isinstance(q._zero_float, nn.Parameter):
+                return False
+            if self._estimating():
+                return type(est) in _MINMAX and not getattr(est, "percentile", None)
+            d = q._delta
+            return d is not None and d.numel() == 1 and q._kernel_buffers_ok(x.device)
+        if type(q) is not FPQuantizer:
             return False
         if not (x.is_cuda and x.dtype.is_floating_point and x.dim() >= 2 and not x.requires_grad):
             return False
@@ -183,6 +202,8 @@ class QuantizationManager(nn.Module):
     def forward_fused(self, x, bn=None, residual=None, act=0, bn_ab=None):
         """quantize(act(bn(x) + residual)); range update first when estimating (reference order)."""
         q, est = self.quantizer, self.range_estimator
+        if type(q) in _UNIFORM:
+            return self._forward_fused_int(x, bn, residual, act, bn_ab)
         if self._estimating() and type(est) is FP_MSE_Estimator:
             # the search needs the tensor the quantizer will see: the epilogue with the quantizer switched off (8 B / element
             # instead of torch's batch_norm + activation passes; the first batch's abs-max and search grid come out of the same
@@ -197,20 +218,7 @@ class QuantizationManager(nn.Module):
                 return y
             return self.forward(_ops.affine_act(x, ab, residual, act))
         if self._estimating():
-            cur_min, cur_max = est.current_xmin, est.current_xmax
-            if cur_min is not None and est._fold_mode != _ops.FOLD_CURRENT:
-                cur_min, cur_max = cur_min.reshape(-1), cur_max.reshape(-1)
-            else:
-                cur_min = cur_max = None
-            packed = est._packed(x.device)
-            if packed is None:
-                mn, mx, mv = _ops.affine_act_minmax(x, cur_min, cur_max, mode=est._fold_mode, momentum=est.momentum,
-                                                    bn=bn, residual=residual, act=act)
-            else:                                    # data-parallel calibration: global range before quantizing
-                mn, mx, mv = _ops.affine_act_minmax(x, cur_min, cur_max, mode=est._fold_mode, momentum=est.momentum,
-                                                    bn=bn, residual=residual, act=act, packed=packed)
-                est._exchange(packed, mn, mx, mv)
-            est.current_xmin, est.current_xmax, est.last_maxval = mn.reshape(()), mx.reshape(()), mv
+            self._epilogue_minmax(x, bn, residual, act)
             if q.set_maxval:
                 q._set_maxval_tensor(est.last_maxval)
         if q.maxval.device != x.device:
@@ -219,6 +227,43 @@ class QuantizationManager(nn.Module):
         prep = q._prepared() if not self._estimating() and hasattr(_ops, "quantizer_prepare") else None
         return _ops.affine_act_quantize(x, q.maxval, float(q.mantissa_bits), q.n_bits, q.sign_bits, bn=bn,
                                         residual=residual, act=act, bn_ab=bn_ab if bn is not None else None, prep=prep)
+
+    def _epilogue_minmax(self, x, bn, residual, act):
+        """The estimating half of forward_fused, for either quantizer family: the range of act(bn(x) + residual) in one launch
+        (fp8q.ops.affine_act_minmax), folded into the min/max estimator's running estimate, exchanged between ranks when the
+        calibration is data-parallel.  Stores and returns the estimator's (current_xmin, current_xmax)."""
+        est = self.range_estimator
+        cur_min, cur_max = est.current_xmin, est.current_xmax
+        if cur_min is not None and est._fold_mode != _ops.FOLD_CURRENT:
+            cur_min, cur_max = cur_min.reshape(-1), cur_max.reshape(-1)
+        else:
+            cur_min = cur_max = None
+        packed = est._packed(x.device)
+        if packed is None:
+            mn, mx, mv = _ops.affine_act_minmax(x, cur_min, cur_max, mode=est._fold_mode, momentum=est.momentum,
+                                                bn=bn, residual=residual, act=act)
+        else:                                    # data-parallel calibration: global range before quantizing
+            mn, mx, mv = _ops.affine_act_minmax(x, cur_min, cur_max, mode=est._fold_mode, momentum=est.momentum,
+                                                bn=bn, residual=residual, act=act, packed=packed)
+            est._exchange(packed, mn, mx, mv)
+        est.current_xmin, est.current_xmax, est.last_maxval = mn.reshape(()), mx.reshape(()), mv
+        return est.current_xmin, est.current_xmax
+
+    def _forward_fused_int(self, x, bn, residual, act, bn_ab):
+        """forward_fused of a uniform quantizer (can_fuse has checked the conditions): the epilogue's min/max launch and
+        fp8q_int_affine_act_range_quantize_f32 when estimating, fp8q_int_affine_act_quantize_f32 with fixed ranges."""
+        q = self.quantizer
+        ab = None
+        if bn is not None:
+            ab = bn_ab if bn_ab is not None else _ops.bn_fold(bn)
+        if not self._estimating():
+            return _ops.int_affine_act_quantize(x, *q._range_args(), bn_ab=ab, residual=residual, act=act)
+        mn, mx = self._epilogue_minmax(x, bn, residual, act)
+        q.x_min_fp32, q.x_max_fp32 = mn, mx
+        y, d, z, sg = _ops.int_affine_act_range_quantize(x, mn, mx, q.n_bits, q.symmetric, q.eps, *q._range_out(mn),
+                                                         bn_ab=ab, residual=residual, act=act)
+        q._store_range(d, z, sg)
+        return y
 
     def extra_repr(self):
         return f"state={self.state.name}"

@@ -17,6 +17,11 @@ range-setting forwards on the half kernels under the same conditions and returns
 chain, one rounding back; the ranges stay float32.  Under autograd or with learned ranges such an x is widened, takes the
 float32 route above and the result is cast back.  Without keep_dtype a half tensor is the eager chain, as ever.
 
+The producer epilogue (csrc/fp8q_intepilogue.hip): a per-tensor quantizer built with `fuse_epilogue=True` lets its
+QuantizationManager run eval-mode batch norm + residual + ReLU / ReLU6 + this quantizer as ONE kernel (`can_fuse` /
+`forward_fused`), bit for bit fp8q.ops.int_quantize of fp8q.ops.affine_act.  Off by default, because the fused batch norm
+rounds as ATen's CPU kernel does and the CUDA batch_norm of the unfused chain differs from it in the last bit.
+
 The integer codes of half tensors (csrc/fp8q_codec_h16.hip): with `keep_dtype=True`, `encode` takes a float16 / bfloat16
 tensor under forward's kernel conditions (the codes of the exactly widened tensor) and `decode(codes, out_dtype=...)` returns
 float16 / bfloat16 values (the float32 value rounded once), so decode(encode(x), out_dtype=x.dtype) == forward(x) bit for bit
@@ -215,8 +220,12 @@ class AsymmetricUniformQuantizer(QuantizerBase):
         return y, mn, mx
 
     def __init__(self, n_bits, scale_domain="linear", discretizer=round_ste_func, discretizer_args=tuple(),
-                 grad_scaling=False, eps=1e-8, keep_dtype=False, **kwargs):
+                 grad_scaling=False, eps=1e-8, keep_dtype=False, fuse_epilogue=False, **kwargs):
         super().__init__(n_bits=n_bits, **kwargs)
+        # True lets QuantizationManager.can_fuse hand the producer's batch norm / residual / activation to the fused INT
+        # epilogue (csrc/fp8q_intepilogue.hip).  Off by default: the fused batch norm is ATen's CPU arithmetic (the fma form),
+        # which differs in the last bit from the CUDA batch_norm kernel of the unfused chain.  A setting, not state.
+        self.fuse_epilogue = fuse_epilogue
         # float16 / bfloat16 inputs: True runs the half kernels and returns x's dtype (widen exactly, the fp32 chain, one
         # rounding back); False leaves such a tensor to the eager chain (the manager widens it and returns float32)
         self.keep_dtype = keep_dtype

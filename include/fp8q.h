@@ -485,6 +485,35 @@ int fp8q_int_minmax_quantize_f32(const float *x, float *y, int64_t C, int64_t in
                                  float eps, void *ws, size_t ws_bytes, fp8q_stream_t stream);
 
 /*
+ * N2 for the uniform (INT) quantizers (csrc/fp8q_intepilogue.hip): the producer epilogue of fp8q_affine_act_f32 fused with the
+ * per-tensor INT quantizer above, in one pass (8 B / element, 12 with a residual):
+ *   t = fma(x, alpha_c, beta'_c)     alpha_beta: the folded [C, 2] vector of fp8q_bn_fold_f32, or NULL (no batch norm)
+ *   t = t + residual                 residual NULL: skipped
+ *   t = relu(t) / relu6(t)           act: 0 none, 1 ReLU, 2 ReLU6; NaN stays NaN
+ *   y = scale * (clamp(rint(t / scale) + zp, int_min, int_max) - zp)
+ * Bit for bit fp8q_int_quantize_f32 (n_delta = 1) applied to the output of fp8q_affine_act_f32, NaN positions, +-inf and -0
+ * included.  x, residual, y: [N, C, HW] fp32, 16-byte aligned; y may alias x or residual.  The quantizer is per tensor:
+ * delta, zero_float (asymmetric; unused and may be NULL when symmetric) and x_min, x_max have ONE element; the symmetric sign
+ * is the device byte signed_flag[0] (unused and may be NULL when not symmetric).
+ *   fp8q_int_affine_act_quantize_f32        fixed ranges.
+ *   fp8q_int_affine_act_range_quantize_f32  set_quant_range(x_min[0], x_max[0]) and the quantizer in the same launch, as
+ *       fp8q_int_range_quantize_f32: every block derives the range, one block writes delta_out[0], zero_float_out[0]
+ *       (asymmetric) and signed_flag_out[0] (symmetric).  As there, the three outputs must not overlap x_min, x_max, x,
+ *       residual or y (other blocks still read those).
+ * FP8Q_EINVAL: a null or misaligned pointer (x, residual, y: 16 bytes; alpha_beta: 8), act outside 0..2, C or HW not
+ * positive.  FP8Q_EUNSUPPORTED: C * HW not a multiple of 4, C * HW >= 2^31, HW >= 2^24, C * HW * HW >= 2^48, n_bits outside
+ * [2, 16].  N == 0: nothing is launched.  One launch per 65535 images.  Enqueue-only.
+ */
+int fp8q_int_affine_act_quantize_f32(const float *x, const float *residual, float *y, int64_t N, int64_t C, int64_t HW,
+                                     const float *alpha_beta, int act, const float *delta, const float *zero_float,
+                                     const unsigned char *signed_flag, int n_bits, int symmetric, float eps,
+                                     fp8q_stream_t stream);
+int fp8q_int_affine_act_range_quantize_f32(const float *x, const float *residual, float *y, int64_t N, int64_t C, int64_t HW,
+                                           const float *alpha_beta, int act, const float *x_min, const float *x_max,
+                                           float *delta_out, float *zero_float_out, unsigned char *signed_flag_out, int n_bits,
+                                           int symmetric, float eps, fp8q_stream_t stream);
+
+/*
  * Integer codes of the uniform (INT) quantizers (csrc/fp8q_intcodec.hip): the storage form of the lane above, and the
  * reference's to_integer_forward (uniform_quantizers.py:108-133).  With scale, zp, int_min, int_max as above (the symmetric
  * sign read from signed_flag[0] on the device):
