@@ -215,8 +215,33 @@ struct Chunk {
     }
 };
 
-// The prologue of a block.  kc: nc_max float4 of LDS.  range(row, starts, hi) yields a row's (delta, zero_float) -- `starts`:
-// the row begins in this chunk, so a range-setting launch reports it from here -- and fold_sign is int_sign()'s.
+// The rows of a block's chunk for a lane without sign or grid (the OCP FP8 lane, fp8q_ocp.hip: {scale, 1/scale}): the
+// chunk's ends, the phase of its first row, and the constants of every row overlapping it in kc (nc_max float4 of LDS), one
+// lane per row: kc[i] = consts(row, starts) -- `starts`: the row begins in this chunk (per tensor: in block 0), so a launch
+// that reports something per row reports it from here.
+template <bool PC, typename ConstsOf>
+__device__ __forceinline__ void chunk_rows(Chunk &c, const IntArgs &a, float4 *kc, ConstsOf consts)
+{
+    const int tid = threadIdx.x;
+    c.e0 = (int64_t)blockIdx.x * kIntChunk;
+    c.e1 = c.e0 + kIntChunk < a.n ? c.e0 + kIntChunk : a.n;
+    const int64_t c_lo = PC ? c.e0 / a.inner : 0;
+    c.phase = PC ? (int)(c.e0 - c_lo * a.inner) : 0;
+    c.inner = a.inner;
+    c.magic = a.magic;
+    const int nc = PC ? (int)((c.e1 - 1) / a.inner - c_lo) + 1 : 1;
+    for (int i = tid; i < nc; i += kBlock) {
+        const int64_t row = c_lo + i;
+        kc[i] = consts(row, PC ? row * a.inner >= c.e0 : blockIdx.x == 0);
+    }
+    __syncthreads();
+    c.kc = kc;
+    c.k0 = kc[0];
+}
+
+// The prologue of a block of the INT kernels.  kc: nc_max float4 of LDS.  range(row, starts, hi) yields a row's (delta,
+// zero_float) -- `starts`: the row begins in this chunk, so a range-setting launch reports it from here -- and fold_sign is
+// int_sign()'s.  (The geometry is chunk_rows()'s, written out: the sign's barrier sits between the chunk's ends and its rows.)
 template <bool PC, typename RangeOf>
 __device__ __forceinline__ Chunk chunk_setup(const IntArgs &a, float4 *kc, RangeOf range, bool fold_sign = false)
 {

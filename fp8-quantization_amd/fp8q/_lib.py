@@ -125,6 +125,13 @@ SIGNATURES = {
     "fp8q_percentile_resident_max_inner": (_i64, []),
     "fp8q_percentile_workspace_bytes": (ctypes.c_size_t, [_i64, _i64]),
     "fp8q_percentile_f32": (_i, [_vp, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "fp8q_ocp_encode_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _f, _vp, _vp]),
+    "fp8q_ocp_encode_h16": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _i64, _i, _f, _vp, _vp]),
+    "fp8q_ocp_decode_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _vp]),
+    "fp8q_ocp_decode_h16": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _i64, _i, _vp]),
+    "fp8q_ocp_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _f, _vp]),
+    "fp8q_ocp_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _i64, _i, _f, _vp]),
+    "fp8q_ocp_scale_f32": (_i, [_vp, _i64, _i, _f, _vp, _vp]),
 }
 
 

@@ -1458,6 +1458,143 @@ def decode(codes, maxval, mbits, n_bits=8, sign_bits=1, out=None, out_dtype=None
     return y
 
 
+# ---- hardware FP8: OCP E4M3FN / E5M2 (csrc/fp8q_ocp.hip; the contract is in include/fp8q.h) ----
+_OCP_FMT = {torch.float8_e4m3fn: 0, torch.float8_e5m2: 1}          # FP8Q_OCP_* (include/fp8q.h)
+OCP_FMAX = {torch.float8_e4m3fn: 448.0, torch.float8_e5m2: 57344.0}
+
+
+def _ocp_fmt(fmt):
+    if fmt not in _OCP_FMT:
+        raise Fp8qError(f"fmt must be torch.float8_e4m3fn or torch.float8_e5m2, got {fmt}")
+    return _OCP_FMT[fmt]
+
+
+def _ocp_range(t, name, like):
+    """a range / scale vector as the kernels read it: float32, contiguous, flat, on `like`'s device"""
+    _require(t, name, like=like)
+    return t.detach().contiguous().view(-1)
+
+
+def _ocp_rows(x, n):
+    C, inner = _rows(x, n != 1)
+    if n != 1 and n != C:
+        raise Fp8qError(f"the range has {n} elements, expected 1 or {C}")
+    return C, inner
+
+
+def ocp_scale(maxval, fmt, eps=1e-8):
+    """scale = max(maxval, eps) / fmax as the OCP kernels form it (fp8q_ocp_scale_f32), float32, shaped like maxval.flatten()"""
+    f = _ocp_fmt(fmt)
+    _require(maxval, "maxval")
+    maxval = maxval.detach().contiguous().view(-1)
+    scale = torch.empty_like(maxval)
+    if maxval.numel():
+        with _on_device(maxval):
+            rc = lib().fp8q_ocp_scale_f32(maxval.data_ptr(), maxval.numel(), f, float(eps), scale.data_ptr(), _stream(maxval))
+        check(rc, "fp8q_ocp_scale_f32")
+    return scale
+
+
+def ocp_encode(x, maxval, fmt, eps=1e-8, out=None, want_scale=True):
+    """Hardware FP8 codes of x: (codes, scale).  fmt: torch.float8_e4m3fn or torch.float8_e5m2; maxval [1] or [C] CUDA float32.
+    scale = max(maxval, eps) / fmax, codes = RNE(clamp(x / scale, -fmax, fmax)) as OCP bytes -- what
+    torch.clamp(x / scale, -fmax, fmax).to(fmt) gives on the CPU, every NaN as 0x7F.  codes is a tensor of dtype `fmt` shaped
+    like x (a view of the uint8 buffer the kernel wrote; `out`: a contiguous uint8 or `fmt` tensor), scale float32 [1] or [C]
+    (None with want_scale=False).  x float32, or float16 / bfloat16 (widened exactly: the codes of x.float()).  One launch.
+    Dynamic scaling is minmax(x, per_channel, want_maxval=True) followed by this call."""
+    f = _ocp_fmt(fmt)
+    _require(x, "x", _VALUES)
+    maxval = _ocp_range(maxval, "maxval", x)
+    n = maxval.numel()
+    x = x.contiguous()
+    C, inner = _ocp_rows(x, n)
+    if out is not None and isinstance(out, torch.Tensor) and out.dtype == fmt:
+        out = out.view(torch.uint8)
+    codes = _out(out, x, torch.uint8)
+    scale = torch.empty_like(maxval) if want_scale else None
+    if x.numel() == 0:
+        return codes.view(fmt), (ocp_scale(maxval, fmt, eps) if want_scale else None)
+    ps = scale.data_ptr() if want_scale else None
+    with _on_device(x):
+        if x.dtype in _HALF:
+            fn = "fp8q_ocp_encode_h16"
+            rc = lib().fp8q_ocp_encode_h16(x.data_ptr(), codes.data_ptr(), _DT[x.dtype], C, inner, maxval.data_ptr(), n, f,
+                                           float(eps), ps, _stream(x))
+        else:
+            fn = "fp8q_ocp_encode_f32"
+            rc = lib().fp8q_ocp_encode_f32(x.data_ptr(), codes.data_ptr(), C, inner, maxval.data_ptr(), n, f, float(eps), ps,
+                                           _stream(x))
+    check(rc, fn)
+    return codes.view(fmt), scale
+
+
+def ocp_decode(codes, scale, out=None, out_dtype=None, fmt=None):
+    """Values of hardware FP8 codes: value(code) * scale, one float32 multiplication -- codes.float() * scale of the CPU.
+    codes: a CUDA tensor of dtype torch.float8_e4m3fn / torch.float8_e5m2, or uint8 with `fmt` naming the format; scale [1] or
+    [C] CUDA float32 (ocp_encode's).  float32 unless a float16 / bfloat16 `out` or out_dtype asks for a half type (the float32
+    product rounded once).  One launch."""
+    dt = _decode_out_dtype(out, out_dtype)
+    if not isinstance(codes, torch.Tensor) or not codes.is_cuda:
+        raise Fp8qError("codes must be a CUDA(HIP) tensor: the FP8 engine has no CPU path")
+    if codes.dtype in _OCP_FMT:
+        if fmt is not None and fmt != codes.dtype:
+            raise Fp8qError(f"codes are {codes.dtype} but fmt is {fmt}")
+        fmt = codes.dtype
+    elif codes.dtype != torch.uint8:
+        raise Fp8qError(f"codes must be float8_e4m3fn, float8_e5m2 or uint8, got {codes.dtype}")
+    elif fmt is None:
+        raise Fp8qError("uint8 codes carry no format: pass fmt=torch.float8_e4m3fn or torch.float8_e5m2")
+    f = _ocp_fmt(fmt)
+    scale = _ocp_range(scale, "scale", codes)
+    n = scale.numel()
+    codes = codes.contiguous().view(torch.uint8)
+    C, inner = _ocp_rows(codes, n)
+    y = _out(out, codes, dt)
+    if codes.numel() == 0:
+        return y
+    with _on_device(codes):
+        if dt in _HALF:
+            fn = "fp8q_ocp_decode_h16"
+            rc = lib().fp8q_ocp_decode_h16(codes.data_ptr(), y.data_ptr(), _DT[dt], C, inner, scale.data_ptr(), n, f,
+                                           _stream(codes))
+        else:
+            fn = "fp8q_ocp_decode_f32"
+            rc = lib().fp8q_ocp_decode_f32(codes.data_ptr(), y.data_ptr(), C, inner, scale.data_ptr(), n, f, _stream(codes))
+    check(rc, fn)
+    return y
+
+
+def ocp_quantize(x, maxval, fmt, eps=1e-8, out=None, out_dtype=None):
+    """Fake-quantize to hardware FP8: ocp_decode(*ocp_encode(x, maxval, fmt, eps)) bit for bit, in one launch.  x float32
+    gives float32; x float16 / bfloat16 gives float32 unless `out` or out_dtype=x.dtype ask for x's own dtype (the float32
+    result rounded once)."""
+    f = _ocp_fmt(fmt)
+    _require(x, "x", _VALUES)
+    if x.dtype in _HALF:
+        dt = _half_out_dtype(x, out, out_dtype)
+    else:
+        _check_out_dtype(x, out_dtype)
+        dt = torch.float32
+    maxval = _ocp_range(maxval, "maxval", x)
+    n = maxval.numel()
+    x = x.contiguous()
+    C, inner = _ocp_rows(x, n)
+    y = _out(out, x, dt)
+    if x.numel() == 0:
+        return y
+    with _on_device(x):
+        if x.dtype in _HALF:
+            fn = "fp8q_ocp_quantize_h16"
+            rc = lib().fp8q_ocp_quantize_h16(x.data_ptr(), y.data_ptr(), _DT[x.dtype], _DT[dt], C, inner, maxval.data_ptr(), n,
+                                             f, float(eps), _stream(x))
+        else:
+            fn = "fp8q_ocp_quantize_f32"
+            rc = lib().fp8q_ocp_quantize_f32(x.data_ptr(), y.data_ptr(), C, inner, maxval.data_ptr(), n, f, float(eps),
+                                             _stream(x))
+    check(rc, fn)
+    return y
+
+
 def _nchw(x):
     """[N, C, *spatial] -> (N, C, HW)."""
     if x.dim() < 2:

@@ -293,6 +293,42 @@ def decode_int_weights(exported, device="cuda", dtype=None):
             for name, e in exported.items()}
 
 
+def export_ocp_weights(model):
+    """{layer name: {codes, scale, fmt}} for every layer whose weights go through an OCPFP8Quantizer with fixed ranges -- the
+    twin of export_fp8_weights / export_int_weights for hardware FP8: codes is a CPU tensor of dtype torch.float8_e4m3fn /
+    torch.float8_e5m2 shaped like the weight, scale the float32 [1] or [C] factor the kernel used (max(maxval, eps) / fmax),
+    fmt the dtype.  decode(codes) * scale == the layer's quantized weight bit for bit.  float16 / bfloat16 weights are encoded
+    as they are (fp8q_ocp_encode_h16: the codes of the exactly widened weight)."""
+    import fp8q
+    from .layers import QuantizationHijacker
+    from .manager import Qstates
+    from .ocp import OCPFP8Quantizer
+    out = {}
+    for name, m in model.named_modules():
+        if not isinstance(m, QuantizationHijacker) or not getattr(m, "_qw", False):
+            continue
+        if type(m).quantize_weights is not QuantizationHijacker.quantize_weights:
+            continue
+        mgr = m.weight_quantizer
+        q = getattr(mgr, "quantizer", None)
+        if not isinstance(q, OCPFP8Quantizer) or mgr.state != Qstates.fix_ranges or not q.is_initialized:
+            continue
+        w = m.get_weight_bias()[0].detach()
+        if not w.is_cuda:
+            continue
+        codes, scale = fp8q.ops.ocp_encode(w.contiguous(), q._range_for(w), q.fmt, q.eps)
+        out[name] = dict(codes=codes.cpu(), scale=scale.cpu(), fmt=q.fmt)
+    return out
+
+
+def decode_ocp_weights(exported, device="cuda", dtype=None):
+    """{layer name: tensor} from export_ocp_weights(): the values the layers compute with, float32 or `dtype` (float16 /
+    bfloat16: the float32 value rounded once)."""
+    import fp8q
+    return {name: fp8q.ops.ocp_decode(e["codes"].to(device), e["scale"].to(device), out_dtype=dtype, fmt=e["fmt"])
+            for name, e in exported.items()}
+
+
 class GraphedForward:
     """HIP graph of `model(x)` for one input shape.  With FIXED ranges nothing in a quantized forward is decided on
     the host (the engine's entry points only enqueue kernels on the current stream), so the whole forward can be

@@ -1,0 +1,116 @@
+"""Hardware FP8 fake-quantizer: the OCP encodings the MI355X's matrix cores and torch.float8_e4m3fn / torch.float8_e5m2 read.
+
+FPQuantizer computes the reference's emulated formats (a real-valued exponent bias, no NaN or infinity codes); its storage
+codes cannot be read as hardware FP8.  OCPFP8Quantizer is the other kind: a fixed format (E4M3FN, fmax 448, or E5M2, fmax
+57344) under a float32 scale = max(maxval, eps) / fmax per tensor or per output channel, with
+    forward(x) = decode(encode(x)),  encode(x) = RNE(clamp(x / scale, -fmax, fmax)) as OCP bytes,  decode(c) = value(c) * scale
+on the kernels of csrc/fp8q_ocp.hip (include/fp8q.h states the arithmetic; the oracle is torch's CPU cast).  The codes with
+`scale` as a per-row [C, 1] or per-tensor [1] factor are the operands a scaled FP8 matrix multiplication takes.
+
+It follows the quantizer protocol (QuantizerBase), so QuantizationManager drives it with the min/max estimators and the
+model zoo takes it as `method=OCPFP8Quantizer`; it is deliberately NOT a member of QMethods (the CLI's choices).  Forward
+only: there is no backward kernel, and a call that would need a gradient raises NotImplementedError.  The MSE and line-search
+estimators are not supported with it.  There is no CPU path.
+"""
+import torch
+
+from fp8q import ops as _ops
+from .fp8 import QuantizerBase, QuantizerNotInitializedError
+
+_HALF = (torch.float16, torch.bfloat16)
+
+
+class OCPFP8Quantizer(QuantizerBase):
+    def __init__(self, n_bits=8, fmt=torch.float8_e4m3fn, per_channel=False, eps=1e-8, keep_dtype=False, scale_domain=None,
+                 **kwargs):
+        if n_bits != 8:
+            raise ValueError(f"hardware FP8 has 8 bits, got n_bits={n_bits}")
+        if fmt not in _ops.OCP_FMAX:
+            raise ValueError(f"fmt must be torch.float8_e4m3fn or torch.float8_e5m2, got {fmt}")
+        super().__init__(n_bits=n_bits, per_channel=per_channel, **kwargs)
+        self.fmt = fmt
+        self.eps = eps
+        # float16 / bfloat16 inputs: False returns float32 (the manager widens them), True the input's dtype (rounded once)
+        self.keep_dtype = keep_dtype
+        # the range, float32 [1] or [C] on the device; named apart from FPQuantizer's `maxval`, whose holders the layers'
+        # quantized-weight cache takes for FPQuantizers
+        self.register_buffer("_maxval", None)
+
+    def __setattr__(self, name, value):
+        if name == "_maxval":       # every assignment of the range starts a new range epoch, as on the other quantizers
+            object.__setattr__(self, "_range_epoch", getattr(self, "_range_epoch", 0) + 1)
+        super().__setattr__(name, value)
+
+    @property
+    def is_initialized(self):
+        return self._maxval is not None
+
+    @property
+    def symmetric(self):
+        return True
+
+    @property
+    def fmax(self):
+        return _ops.OCP_FMAX[self.fmt]
+
+    @property
+    def range_maxval(self):
+        if self._maxval is None:
+            raise QuantizerNotInitializedError()
+        return self._maxval
+
+    @property
+    def scale(self):
+        """max(maxval, eps) / fmax, float32 [1] or [C]: the kernels' own values (fp8q.ops.ocp_scale)"""
+        return _ops.ocp_scale(self.range_maxval, self.fmt, self.eps)
+
+    def reset(self):
+        self._maxval = None
+
+    def set_quant_range(self, x_min, x_max):
+        """maxval = max(|x_min|, |x_max|), kept on the device: nothing is read back"""
+        self.x_min_fp32, self.x_max_fp32 = x_min, x_max
+        if not isinstance(x_min, torch.Tensor):
+            x_min, x_max = torch.tensor(float(x_min)), torch.tensor(float(x_max))
+        if x_min.numel() > 1 and not self.per_channel:
+            raise ValueError("x_min and x_max must be a float or 1-element tensor for per-tensor quantization "
+                             "(per_channel=False)")
+        mv = torch.max(x_min.detach().abs(), x_max.detach().abs()).to(torch.float32).reshape(-1)
+        if self._maxval is not None and self._maxval.device != mv.device:
+            mv = mv.to(self._maxval.device)
+        self._maxval = mv
+
+    def _range_for(self, t):
+        mv = self.range_maxval
+        if mv.device != t.device:
+            mv = self._maxval = mv.to(t.device)
+        if mv.numel() != 1 and not (self.per_channel and t.dim() > 0 and t.shape[0] == mv.numel()):
+            raise _ops.Fp8qError(f"the range has {mv.numel()} entries, the tensor {tuple(t.shape)}")
+        return mv
+
+    def forward(self, x_float):
+        if torch.is_grad_enabled() and x_float.requires_grad:
+            raise NotImplementedError("OCPFP8Quantizer is forward-only: there is no backward kernel for the hardware FP8 "
+                                      "lane (call it under torch.no_grad(), or on a detached tensor)")
+        out_dtype = x_float.dtype if (self.keep_dtype and x_float.dtype in _HALF) else None
+        return _ops.ocp_quantize(x_float, self._range_for(x_float), self.fmt, self.eps, out_dtype=out_dtype)
+
+    def encode(self, x_float):
+        """The codes of forward(x): a torch.float8_e4m3fn / torch.float8_e5m2 tensor shaped like x; `scale` goes with them."""
+        return _ops.ocp_encode(x_float.detach(), self._range_for(x_float), self.fmt, self.eps, want_scale=False)[0]
+
+    def decode(self, codes, out_dtype=None):
+        """Values of encode()'s codes, float32 or out_dtype (float16 / bfloat16: the float32 value rounded once):
+        decode(encode(x)) == forward(x) bit for bit."""
+        self._range_for(codes)
+        return _ops.ocp_decode(codes, self.scale, out_dtype=out_dtype, fmt=self.fmt)
+
+    def make_range_trainable(self):
+        raise NotImplementedError("OCPFP8Quantizer is forward-only: its range cannot be learned")
+
+    def fix_ranges(self):
+        pass
+
+    def extra_repr(self):
+        name = "E4M3FN" if self.fmt == torch.float8_e4m3fn else "E5M2"
+        return f"{super().extra_repr()}, fmt={name}, eps={self.eps}"

@@ -786,6 +786,54 @@ size_t fp8q_percentile_workspace_bytes(int64_t C, int64_t inner);
 int fp8q_percentile_f32(const float *x, int64_t C, int64_t inner, double pct, float *lo, float *hi, void *ws, size_t ws_bytes,
                         fp8q_stream_t stream);
 
+/* ---- hardware FP8: the OCP encodings E4M3FN and E5M2 (csrc/fp8q_ocp.hip) ---------------------------------------------------
+ * Every other lane of this library computes the reference's emulated formats (a real-valued exponent bias, the top exponent
+ * code an ordinary binade); their storage codes cannot be fed to gfx950's matrix cores or read as torch.float8_e4m3fn /
+ * torch.float8_e5m2: the byte of a channel's largest element is all ones below the sign, which E4M3FN reads as NaN.  These
+ * entries produce and read the OCP bytes themselves, with the chip's conversion instructions.
+ * Arithmetic contract.  fmt is FP8Q_OCP_E4M3FN (fmax = 448) or FP8Q_OCP_E5M2 (fmax = 57344); maxval holds 1 or C entries:
+ *   scale = max(maxval, eps) / fmax          float32, IEEE division, torch.max: a NaN maxval gives a NaN scale
+ *   q     = clamp(x / scale, -fmax, fmax)    float32 IEEE division, then torch.clamp: NaN passes, +-inf saturate to +-fmax
+ *   code  = RNE(q) as an OCP byte            subnormals as OCP defines them, -0 -> 0x80, every NaN -> 0x7F in both formats
+ *                                            (the sign of a NaN is not kept).  Overflow codes -- E4M3FN's NaN, E5M2's
+ *                                            infinity -- are never produced from finite or infinite x: the clamp comes first,
+ *                                            so the conversion instruction's own overflow behaviour is never relied on.
+ *   decode(code) = value(code) * scale       ONE float32 multiplication; a half output rounds that product once (round to
+ *                                            nearest even, as torch.Tensor.to(dtype)).  A NaN code is not multiplied: it
+ *                                            decodes to the NaN torch's widening gives it (sign, quiet bit, the code's
+ *                                            mantissa field left aligned: 0x7FF00000 for E4M3FN 0x7F).
+ *   quantize(x) = decode(encode(x))          bit for bit, in one pass.
+ * The oracle is torch's CPU cast: torch.clamp(x / scale, -fmax, fmax).to(torch.float8_e4m3fn) and c.float() * scale.  The
+ * kernels multiply by 1 / scale and redo the division wherever the product lies within the reciprocal's error of a rounding
+ * boundary (the bound is derived at the top of fp8q_ocp.hip), so the codes are those of the division.
+ * Half inputs (x_type = FP8Q_DT_F16 / FP8Q_DT_BF16) are widened exactly; fp8q_ocp_quantize_h16's y_type is FP8Q_DT_F32 or
+ * x_type, as in fp8q_quantize_h16.  scale_out (encode, may be NULL) receives the 1 or C scales, each written by the block
+ * in whose chunk the row starts; fp8q_ocp_scale_f32 computes the same n values from a range alone.  fp8q_ocp_decode_* take
+ * those scales, not the range.  codes with scale as a per-row [C, 1] or per-tensor [1] factor are the operands a scaled
+ * FP8 matrix multiplication takes; nothing here performs one.
+ * Per tensor (n_maxval == 1) and per channel (n_maxval == C), rows of any length.  fp32 pointers need 4-byte, half pointers
+ * 2-byte alignment (FP8Q_EINVAL); 16-byte aligned x / y / codes take the vector route (a lane converts 16 consecutive
+ * elements and stores 16 codes as one word), anything else goes element by element with the same results.
+ * Errors, all reported before the launch: FP8Q_EINVAL for null pointers, empty shapes (C or inner <= 0), n_maxval / n_scale
+ * not in {1, C}, misaligned pointers, a type that is not a half type (y_type: nor FP8Q_DT_F32); FP8Q_EUNSUPPORTED for any
+ * other fmt.  One launch per call, enqueue-only, no workspace.  FP8Q_VERSION is unchanged: the entries are additive.
+ */
+#define FP8Q_OCP_E4M3FN 0
+#define FP8Q_OCP_E5M2 1
+int fp8q_ocp_encode_f32(const float *x, uint8_t *codes, int64_t C, int64_t inner, const float *maxval, int64_t n_maxval,
+                        int fmt, float eps, float *scale_out, fp8q_stream_t stream);
+int fp8q_ocp_encode_h16(const void *x, uint8_t *codes, int x_type, int64_t C, int64_t inner, const float *maxval,
+                        int64_t n_maxval, int fmt, float eps, float *scale_out, fp8q_stream_t stream);
+int fp8q_ocp_decode_f32(const uint8_t *codes, float *y, int64_t C, int64_t inner, const float *scale, int64_t n_scale, int fmt,
+                        fp8q_stream_t stream);
+int fp8q_ocp_decode_h16(const uint8_t *codes, void *y, int y_type, int64_t C, int64_t inner, const float *scale,
+                        int64_t n_scale, int fmt, fp8q_stream_t stream);
+int fp8q_ocp_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, const float *maxval, int64_t n_maxval, int fmt,
+                          float eps, fp8q_stream_t stream);
+int fp8q_ocp_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t C, int64_t inner, const float *maxval,
+                          int64_t n_maxval, int fmt, float eps, fp8q_stream_t stream);
+int fp8q_ocp_scale_f32(const float *maxval, int64_t n, int fmt, float eps, float *scale, fp8q_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
