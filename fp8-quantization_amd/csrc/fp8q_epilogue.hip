@@ -59,58 +59,22 @@ k_affine_act(const float *__restrict__ x, const float *__restrict__ res, float *
     const bool direct = a.has_bn && a.cpp <= 2;
     __syncthreads();       // lut is complete
     for (int base = blockIdx.x * (kBlock * U); base < nvec; base += gridDim.x * (kBlock * U)) {
-        uint32_t phase = 0;
-        float2 p0 = make_float2(1.0f, 0.0f), p1 = p0;
-        if (direct) {
-            const uint32_t e0 = (uint32_t)base * 4u;
-            const uint32_t ch_lo = e0 / HW;
-            phase = e0 - ch_lo * HW;
-            const uint32_t ch_hi = ch_lo + 1u < (uint32_t)a.C ? ch_lo + 1u : ch_lo;
-            p0 = bn_ab(mean, invstd, gamma, beta, ch_lo, a.has_bn);
-            p1 = bn_ab(mean, invstd, gamma, beta, ch_hi, a.has_bn);
-        }
-        if (a.has_bn && !direct) {
-            __syncthreads();   // the previous step's constants are no longer read
-            const uint32_t e0 = (uint32_t)base * 4u;
-            const uint32_t ch_lo = e0 / HW;
-            phase = e0 - ch_lo * HW;
-            for (int k = tid; k < a.cpp; k += kBlock) {
-                const uint32_t ch = ch_lo + (uint32_t)k;
-                if (ch < (uint32_t)a.C) cst[k] = bn_ab(mean, invstd, gamma, beta, ch, a.has_bn);
-            }
-            __syncthreads();
-        }
+        float2 p0, p1;
+        const uint32_t phase = affine_step_planes(base, direct, a, p0, p1, cst, [&](uint32_t ch) {
+            return bn_ab(mean, invstd, gamma, beta, ch, a.has_bn);
+        });
         auto transform = [&](int q, float (&e)[4], const vf4 &r) {   // q: piece-local group index
             const float rr[4] = {r.x, r.y, r.z, r.w};
             if (direct) {
                 const uint32_t o = phase + 4u * (uint32_t)q;
                 const bool hi = o >= HW;                    // second plane of the piece
-                uint32_t off = hi ? o - HW : o;
-                float2 p = hi ? p1 : p0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    e[k] = res_act(fmaf(e[k], p.x, p.y), rr[k], a);
-                    if (++off == HW && k < 3) {
-                        off = 0;
-                        p = p1;
-                    }
-                }
+                affine_walk(e, rr, hi ? o - HW : o, HW, hi ? p1 : p0, a, [&] { return p1; });
             } else if (a.has_bn) {
                 const uint32_t o = phase + 4u * (uint32_t)q;
-                uint32_t lch = HW > (uint32_t)kAffineMagicMaxHW ? (o >= HW ? 1u : 0u) : (uint32_t)div_small(o, a.magic);
-                uint32_t off = o - lch * HW;
-                float2 p = cst[lch];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    e[k] = res_act(fmaf(e[k], p.x, p.y), rr[k], a);
-                    if (++off == HW && k < 3) {      // the group crosses into the next plane
-                        off = 0;                     // (still inside the image: groups never straddle images)
-                        p = cst[++lch];
-                    }
-                }
+                uint32_t lch = affine_local_plane(o, a);
+                affine_walk(e, rr, o - lch * HW, HW, cst[lch], a, [&] { return cst[++lch]; });
             } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) e[k] = res_act(e[k], rr[k], a);
+                affine_plain(e, rr, a);
             }
         };
         if (base + kBlock * U <= nvec) {   // whole piece: unpredicated loads, one branch for all its elements
@@ -154,7 +118,8 @@ k_affine_act(const float *__restrict__ x, const float *__restrict__ res, float *
 // barrier -> {BN vectors -> LDS} -> barrier -> {x} -> arithmetic -> store: three memory round trips behind each other
 // where the plain K1 has two.  Here a lane handles ONE 16-byte group per step and fetches the BN vectors of its own
 // plane(s) straight from global memory (L2 hits: <= 20 KB per model layer) next to x itself, so x, residual and the BN
-// vectors are one round trip, issued BEFORE the table is built (EARLY) so that the table's arithmetic hides it.
+// vectors are one round trip, issued BEFORE the table is built so that the table's arithmetic hides it (issuing it behind
+// the table, as the first version of this kernel did, was slower and is no longer built).
 // rocprofv3 kernel durations at batch 64 (round 3's staged kernel -> this one): [64,160,7,7] 5.4 -> 4.4 us, [64,96,14,14]
 // 6.7 -> 5.3, [64,576,7,7] 6.7 -> 5.5, [64,384,14,14] 12.2 -> 9.5, [64,144,28,28] 16.0 -> 13.1 (plain K1 on the same
 // tensors: 3.9 / 5.1 / 5.1 / 7.3 / 10.4); it wins up to the nontemporal threshold ([64,192,28,28] 19.7 -> 14.8 us,
@@ -164,7 +129,6 @@ k_affine_act(const float *__restrict__ x, const float *__restrict__ res, float *
 // nontemporal accesses below 64 MiB (+10 %), grids of 1024...16384 blocks (2048...4096 equal, the rest worse), requesting
 // the next step's group before the arithmetic of the current one (no change).  With the folded BN vector (has_bn == 2:
 // two 8-byte loads per group instead of eight 4-byte ones) another 5-8 %: [64,64,56,56] 19.9 -> 18.5 us (K1: 17.9).
-template <bool EARLY, bool NT, int U>
 __global__ void __launch_bounds__(kBlock)
 k_affine_act_small(const float *__restrict__ x, const float *__restrict__ res, float *__restrict__ y,
                    const float *__restrict__ mean, const float *__restrict__ invstd, const float *__restrict__ gamma,
@@ -178,40 +142,10 @@ k_affine_act_small(const float *__restrict__ x, const float *__restrict__ res, f
     const vf4 *xv = reinterpret_cast<const vf4 *>(x + base0);
     const vf4 *rv = reinterpret_cast<const vf4 *>(res + (a.has_res ? base0 : 0));
     vf4 *yv = reinterpret_cast<vf4 *>(y + base0);
-    const uint32_t HW = (uint32_t)a.HW;
-    const int step = gridDim.x * (kBlock * U);
-    int base = blockIdx.x * (kBlock * U);
-
-    struct Grp {
-        vf4 v, r;
-        float al0, bp0, al1, bp1;   // {alpha, beta'} of the group's plane and of the next one (HW >= 4: a group spans <= 2)
-        uint32_t off;               // offset of the group's first element inside its plane
-    };
-    auto fetch = [&](int jj, Grp &g) {
-        g.v = ld16<NT>(xv + jj);
-        g.r = a.has_res ? ld16<NT>(rv + jj) : vf4{0.0f, 0.0f, 0.0f, 0.0f};
-        g.off = 0;
-        g.al0 = g.al1 = 1.0f;
-        g.bp0 = g.bp1 = 0.0f;
-        if (a.has_bn) {
-            const uint32_t i0 = (uint32_t)jj * 4u;
-            const uint32_t ch = (uint32_t)(((uint64_t)i0 * a.magic48) >> 48);      // plane == channel
-            g.off = i0 - ch * HW;
-            const uint32_t ch1 = ch + 1u < (uint32_t)a.C ? ch + 1u : ch;
-            const float2 q0 = bn_ab(mean, invstd, gamma, beta, ch, a.has_bn);
-            const float2 q1 = bn_ab(mean, invstd, gamma, beta, ch1, a.has_bn);
-            g.al0 = q0.x;
-            g.bp0 = q0.y;
-            g.al1 = q1.x;
-            g.bp1 = q1.y;
-        }
-    };
-    Grp g[U];
-    if (EARLY) {
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (base + u * kBlock + tid < nvec) fetch(base + u * kBlock + tid, g[u]);
-    }
+    const int step = gridDim.x * kBlock;
+    int base = blockIdx.x * kBlock;
+    AffineGrp g;
+    if (base + tid < nvec) affine_fetch(g, xv, rv, base + tid, mean, invstd, gamma, beta, a.has_bn, a);
     // The quantizer's channel constants and {s, 1/s} table: rebuilt from maxval (a load, ~50 dependent double-precision
     // operations, the table entries) -- or, with fixed ranges, copied from the block fp8q_quantizer_prepare_f32 wrote once:
     // the same numbers, one 8-byte load per entry, 0.5-1 us less on the critical path of a 4-10 us launch.
@@ -231,35 +165,16 @@ k_affine_act_small(const float *__restrict__ x, const float *__restrict__ res, f
     }
     const float pmaxf = (float)f.pmax;
     __syncthreads();
-    bool first = true;
+    bool first = true;   // its group is already here
     for (; base < nvec; base += step) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = base + u * kBlock + tid;
-            if (j < nvec && !(EARLY && first)) fetch(j, g[u]);
-        }
+        const int j = base + tid;
+        if (j < nvec && !first) affine_fetch(g, xv, rv, j, mean, invstd, gamma, beta, a.has_bn, a);
         first = false;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = base + u * kBlock + tid;
-            if (j >= nvec) break;
-            float e[4] = {g[u].v.x, g[u].v.y, g[u].v.z, g[u].v.w};
-            const float rr[4] = {g[u].r.x, g[u].r.y, g[u].r.z, g[u].r.w};
-            if (a.has_bn) {
-                // elements at group-local index >= cross belong to the next plane (HW >= 4: at most one crossing)
-                const uint32_t cross = HW - g[u].off;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const bool nxt = (uint32_t)k >= cross;
-                    e[k] = res_act(fmaf(e[k], nxt ? g[u].al1 : g[u].al0, nxt ? g[u].bp1 : g[u].bp0), rr[k], a);
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) e[k] = res_act(e[k], rr[k], a);
-            }
-            if (!a.passthrough) quant_group<4>(e, c, lut, pmaxf, f.qthr);
-            st16<NT>(yv + j, vf4{e[0], e[1], e[2], e[3]});
-        }
+        if (j >= nvec) break;
+        float e[4];
+        affine_apply(g, e, a);
+        if (!a.passthrough) quant_group<4>(e, c, lut, pmaxf, f.qthr);
+        yv[j] = vf4{e[0], e[1], e[2], e[3]};
     }
 }
 
@@ -301,20 +216,10 @@ k_affine_minmax(const float *__restrict__ x, const float *__restrict__ res, cons
         if (a.has_bn) {
             const uint32_t i0 = (uint32_t)j * 4u;
             uint32_t ch = (uint32_t)(((uint64_t)i0 * a.magic48) >> 48);      // plane == channel
-            uint32_t off = i0 - ch * HW;
-            float2 p = bn_ab(mean, invstd, gamma, beta, ch, a.has_bn);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                e[q] = res_act(fmaf(e[q], p.x, p.y), rr[q], a);
-                if (++off == HW && q < 3) {      // the group crosses into the next plane
-                    off = 0;
-                    ++ch;                         // still < C: the group ends inside the image
-                    p = bn_ab(mean, invstd, gamma, beta, ch, a.has_bn);
-                }
-            }
+            affine_walk(e, rr, i0 - ch * HW, HW, bn_ab(mean, invstd, gamma, beta, ch, a.has_bn), a,
+                        [&] { return bn_ab(mean, invstd, gamma, beta, ++ch, a.has_bn); });
         } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) e[q] = res_act(e[q], rr[q], a);
+            affine_plain(e, rr, a);
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) mm_acc(mm, e[q]);
@@ -345,13 +250,6 @@ static void affine_grid_store(int64_t N, const AffineArgs &a, int64_t *bx, int64
     const int64_t nvec = a.image >> 2;
     const int64_t pieces = cdiv(nvec, kBlock);
     *bx = balanced_blocks(pieces, cap_env / *by > 0 ? cap_env / *by : 1);
-}
-
-// FP8Q_EPI_SMALL_KIND: 0 = the staged kernel for small tensors too (round 3), 1 = k_affine_act_small, 2 = with early loads
-static int small_kind()
-{
-    static const int v = env_int("FP8Q_EPI_SMALL_KIND", 2);
-    return v;
 }
 
 int fp8q_bn_fold_f32(const float *mean, const float *invstd, const float *gamma, const float *beta, int64_t C,
@@ -420,30 +318,18 @@ static int affine_quantize_impl(const float *x, const float *residual, float *y,
     if (N == 0) return FP8Q_OK;
     if (!x || !y || (!maxval && !passthrough)) return FP8Q_EINVAL;
     if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)residual) & 15) return FP8Q_EINVAL;
-    const bool small = N * a.image < affine_small_elems();
-    for (int64_t n0 = 0; n0 < N; n0 += 65535) {
-        int64_t bx, by;
-        affine_grid(N - n0, a, true, &bx, &by, small ? 1 : 4);
-        const size_t shm = has_bn ? (size_t)a.cpp * sizeof(float2) : 0;
-        const dim3 g((unsigned)bx, (unsigned)by), b(kBlock);
-        const float *rp = residual ? residual + n0 * a.image : nullptr;
-        if (N * a.image * 4 >= kNtBytes)
-            hipLaunchKernelGGL((k_affine_act<true, 4>), g, b, shm, (hipStream_t)stream, x + n0 * a.image, rp, y + n0 * a.image,
-                               mean, invstd, gamma, beta, maxval, f, a);
-        else if (small && (a.HW >= 4 || !has_bn) && small_kind() != 0) {
-            if (small_kind() == 2)
-                hipLaunchKernelGGL((k_affine_act_small<true, false, 1>), g, b, 0, (hipStream_t)stream, x + n0 * a.image, rp, y + n0 * a.image,
-                                   mean, invstd, gamma, beta, maxval, f, a, reinterpret_cast<const float4 *>(prep));
-            else
-                hipLaunchKernelGGL((k_affine_act_small<false, false, 1>), g, b, 0, (hipStream_t)stream, x + n0 * a.image, rp, y + n0 * a.image,
-                                   mean, invstd, gamma, beta, maxval, f, a, reinterpret_cast<const float4 *>(prep));
-        } else if (small)
-            hipLaunchKernelGGL((k_affine_act<false, 1>), g, b, shm, (hipStream_t)stream, x + n0 * a.image, rp, y + n0 * a.image,
-                               mean, invstd, gamma, beta, maxval, f, a);
+    affine_dispatch(N, a, true, [&](AffineKernel kind, dim3 g, size_t shm, int64_t n0) {
+        const float *xp = x + n0 * a.image, *rp = residual ? residual + n0 * a.image : nullptr;
+        float *yp = y + n0 * a.image;
+        const hipStream_t st = (hipStream_t)stream;
+        if (kind == AffineKernel::Small)
+            hipLaunchKernelGGL(k_affine_act_small, g, dim3(kBlock), 0, st, xp, rp, yp, mean, invstd, gamma, beta, maxval, f, a,
+                               reinterpret_cast<const float4 *>(prep));
         else
-            hipLaunchKernelGGL((k_affine_act<false, 4>), g, b, shm, (hipStream_t)stream, x + n0 * a.image, rp, y + n0 * a.image,
-                               mean, invstd, gamma, beta, maxval, f, a);
-    }
+            hipLaunchKernelGGL((kind == AffineKernel::StagedNt  ? k_affine_act<true, 4>
+                                : kind == AffineKernel::Staged1 ? k_affine_act<false, 1> : k_affine_act<false, 4>),
+                               g, dim3(kBlock), shm, st, xp, rp, yp, mean, invstd, gamma, beta, maxval, f, a);
+    });
     return launch_rc();
 }
 

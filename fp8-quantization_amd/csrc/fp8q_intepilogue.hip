@@ -6,8 +6,9 @@
 //   y = scale * (clamp(rint(t / scale) + zp, int_min, int_max) - zp)      -- int_one
 // bit for bit fp8q_int_quantize_f32 applied to the output of fp8q_affine_act_f32, in one pass: 8 B / element (12 with a
 // residual) instead of 24 (28) for batch_norm, activation and quantizer as three launches.
-// The two skeletons and their dispatch are fp8q_epilogue.hip's (k_affine_act, k_affine_act_small; the reasons and the
-// measurements are written there).  The uniform quantizer has no {s, 1/s} table: its constants {scale, 1/scale, zp} are
+// Two kernels, a staged one and a one-group-per-lane one, as for the FP8 quantizer: the plane walk, the staged kernels' plane
+// constants and the choice between the kernels are fp8q_affine.h's, shared with fp8q_epilogue.hip (whose kernels carry the
+// measurements behind that geometry).  The uniform quantizer has no {s, 1/s} table: its constants {scale, 1/scale, zp} are
 // consts_of() of two uniform-address loads and one division per thread, so there is no LDS table, no table barrier and no
 // prepared block.  RANGE: (delta, zero_float, sign) come from (x_min[0], x_max[0]) by range_of() in every block, and block
 // (0, 0) of the first launch reports them -- set_quant_range and the quantizer in one launch.
@@ -89,24 +90,11 @@ k_int_affine_act(const float *x, const float *res, float *y, const float *__rest
     vf4 *yv = reinterpret_cast<vf4 *>(y + base0);
     const uint32_t HW = (uint32_t)a.HW;
     const bool direct = a.has_bn && a.cpp <= 2;
-    auto plane = [&](uint32_t ch) { return bn_ab(ab, nullptr, nullptr, nullptr, ch, 2); };
     for (int base = blockIdx.x * (kBlock * U); base < nvec; base += gridDim.x * (kBlock * U)) {
-        uint32_t phase = 0;
-        float2 p0 = make_float2(1.0f, 0.0f), p1 = p0;
-        if (a.has_bn) {
-            const uint32_t e0 = (uint32_t)base * 4u;
-            const uint32_t ch_lo = e0 / HW;
-            phase = e0 - ch_lo * HW;
-            if (direct) {
-                p0 = plane(ch_lo);
-                p1 = plane(ch_lo + 1u < (uint32_t)a.C ? ch_lo + 1u : ch_lo);
-            } else {
-                __syncthreads();   // the previous step's constants are no longer read
-                for (int i = tid; i < a.cpp; i += kBlock)
-                    if (ch_lo + (uint32_t)i < (uint32_t)a.C) cst[i] = plane(ch_lo + (uint32_t)i);
-                __syncthreads();
-            }
-        }
+        float2 p0, p1;
+        const uint32_t phase = affine_step_planes(base, direct, a, p0, p1, cst, [&](uint32_t ch) {
+            return bn_ab(ab, nullptr, nullptr, nullptr, ch, 2);
+        });
         // the epilogue and the quantizer of one 16-byte group; g: piece-local group index
         auto finish = [&](int g, const vf4 &v, const vf4 &r) -> vf4 {
             float e[4] = {v.x, v.y, v.z, v.w};
@@ -114,33 +102,13 @@ k_int_affine_act(const float *x, const float *res, float *y, const float *__rest
             if (direct) {
                 const uint32_t o = phase + 4u * (uint32_t)g;
                 const bool up = o >= HW;                    // second plane of the piece
-                uint32_t off = up ? o - HW : o;
-                float2 p = up ? p1 : p0;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    e[i] = res_act(fmaf(e[i], p.x, p.y), rr[i], a);
-                    if (++off == HW && i < 3) {
-                        off = 0;
-                        p = p1;
-                    }
-                }
+                affine_walk(e, rr, up ? o - HW : o, HW, up ? p1 : p0, a, [&] { return p1; });
             } else if (a.has_bn) {
-                // (HW > kAffineMagicMaxHW never comes here: such a piece overlaps two planes and is `direct`)
                 const uint32_t o = phase + 4u * (uint32_t)g;
-                uint32_t lch = (uint32_t)div_small(o, a.magic);
-                uint32_t off = o - lch * HW;
-                float2 p = cst[lch];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    e[i] = res_act(fmaf(e[i], p.x, p.y), rr[i], a);
-                    if (++off == HW && i < 3) {      // the group crosses into the next plane (still inside the image)
-                        off = 0;
-                        p = cst[++lch];
-                    }
-                }
+                uint32_t lch = affine_local_plane(o, a);
+                affine_walk(e, rr, o - lch * HW, HW, cst[lch], a, [&] { return cst[++lch]; });
             } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) e[i] = res_act(e[i], rr[i], a);
+                affine_plain(e, rr, a);
             }
             return vf4{int_one(e[0], k, lo, hi), int_one(e[1], k, lo, hi), int_one(e[2], k, lo, hi), int_one(e[3], k, lo, hi)};
         };
@@ -183,59 +151,25 @@ k_int_affine_act_small(const float *x, const float *res, float *y, const float *
     const vf4 *xv = reinterpret_cast<const vf4 *>(x + base0);
     const vf4 *rv = reinterpret_cast<const vf4 *>(res + (a.has_res ? base0 : 0));
     vf4 *yv = reinterpret_cast<vf4 *>(y + base0);
-    const uint32_t HW = (uint32_t)a.HW;
     const int step = gridDim.x * kBlock;
     int j = blockIdx.x * kBlock + tid;
-
-    struct Grp {
-        vf4 v, r;
-        float2 q0, q1;    // {alpha, beta'} of the group's plane and of the next one
-        uint32_t off;     // offset of the group's first element inside its plane
-    };
-    auto fetch = [&](int jj, Grp &g) {
-        g.v = xv[jj];
-        g.r = a.has_res ? rv[jj] : vf4{0.0f, 0.0f, 0.0f, 0.0f};
-        g.off = 0;
-        g.q0 = g.q1 = make_float2(1.0f, 0.0f);
-        if (a.has_bn) {
-            const uint32_t i0 = (uint32_t)jj * 4u;
-            const uint32_t ch = (uint32_t)(((uint64_t)i0 * a.magic48) >> 48);      // plane == channel
-            g.off = i0 - ch * HW;
-            g.q0 = bn_ab(ab, nullptr, nullptr, nullptr, ch, 2);
-            g.q1 = bn_ab(ab, nullptr, nullptr, nullptr, ch + 1u < (uint32_t)a.C ? ch + 1u : ch, 2);
-        }
-    };
     const EpiRaw raw = epi_load(q);
-    Grp g;
-    if (j < nvec) fetch(j, g);
+    AffineGrp g;
+    if (j < nvec) affine_fetch(g, xv, rv, j, ab, nullptr, nullptr, nullptr, 2, a);
     const unsigned char flag = RANGE ? (unsigned char)0 : q.sflag[0];     // requested last: waiting for it waits for all
     const float4 k = epi_consts<RANGE>(q, raw);       // (used in the loop only, defined in front of it: stays in front of the wait)
     while (j < nvec) {
-        float e[4] = {g.v.x, g.v.y, g.v.z, g.v.w};
-        const float rr[4] = {g.r.x, g.r.y, g.r.z, g.r.w};
-        if (a.has_bn) {
-            // elements at group-local index >= cross belong to the next plane (HW >= 4: at most one crossing)
-            const uint32_t cross = HW - g.off;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float2 p = (uint32_t)i >= cross ? g.q1 : g.q0;
-                e[i] = res_act(fmaf(e[i], p.x, p.y), rr[i], a);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) e[i] = res_act(e[i], rr[i], a);
-        }
+        float e[4];
+        affine_apply(g, e, a);
         const bool sgn = epi_sign<RANGE>(q, raw, flag);
         const float lo = q.grid.lo(sgn), hi = q.grid.hi(sgn);
         yv[j] = vf4{int_one(e[0], k, lo, hi), int_one(e[1], k, lo, hi), int_one(e[2], k, lo, hi), int_one(e[3], k, lo, hi)};
         j += step;
-        if (j < nvec) fetch(j, g);
+        if (j < nvec) affine_fetch(g, xv, rv, j, ab, nullptr, nullptr, nullptr, 2, a);
     }
 }
 
-// argument checks (affine_args, make_int_grid) and fp8q_epilogue.hip's dispatch: the nontemporal staged kernel from
-// 64 MiB, the one-group-per-lane kernel below the small-tensor threshold (HW < 4 with BN: the staged kernel, a group per
-// lane), the plain staged kernel in between; more than 65535 images: one launch per 65535
+// argument checks (affine_args, make_int_grid), then affine_dispatch's kernel; the first launch reports a RANGE
 template <bool RANGE>
 int int_affine_launch(const float *x, const float *residual, float *y, int64_t N, int64_t C, int64_t HW, const float *alpha_beta,
                       int act, IntEpiArgs q, int n_bits, hipStream_t st)
@@ -251,25 +185,15 @@ int int_affine_launch(const float *x, const float *residual, float *y, int64_t N
         return FP8Q_EINVAL;
     if (!q.b) q.b = q.a;                                             // never used: read, so that no load sits behind a branch
     if (!q.sflag) q.sflag = reinterpret_cast<unsigned char *>(const_cast<float *>(q.a));
-    const bool small = N * a.image < affine_small_elems();
-    const bool nt = N * a.image * 4 >= kNtBytes;
-    for (int64_t n0 = 0; n0 < N; n0 += 65535) {
-        int64_t bx, by;
-        affine_grid(N - n0, a, true, &bx, &by, small && !nt ? 1 : 4);
-        const size_t shm = a.has_bn ? (size_t)a.cpp * sizeof(float2) : 0;
-        const dim3 g((unsigned)bx, (unsigned)by), b(kBlock);
+    affine_dispatch(N, a, false, [&](AffineKernel kind, dim3 g, size_t shm, int64_t n0) {
         const float *xp = x + n0 * a.image, *rp = residual ? residual + n0 * a.image : nullptr;
         float *yp = y + n0 * a.image;
         q.report = n0 == 0;
-        if (nt)
-            hipLaunchKernelGGL((k_int_affine_act<RANGE, true, 4>), g, b, shm, st, xp, rp, yp, alpha_beta, q, a);
-        else if (small && (a.HW >= 4 || !a.has_bn))
-            hipLaunchKernelGGL((k_int_affine_act_small<RANGE>), g, b, 0, st, xp, rp, yp, alpha_beta, q, a);
-        else if (small)
-            hipLaunchKernelGGL((k_int_affine_act<RANGE, false, 1>), g, b, shm, st, xp, rp, yp, alpha_beta, q, a);
-        else
-            hipLaunchKernelGGL((k_int_affine_act<RANGE, false, 4>), g, b, shm, st, xp, rp, yp, alpha_beta, q, a);
-    }
+        hipLaunchKernelGGL((kind == AffineKernel::StagedNt  ? k_int_affine_act<RANGE, true, 4>
+                            : kind == AffineKernel::Small   ? k_int_affine_act_small<RANGE>
+                            : kind == AffineKernel::Staged1 ? k_int_affine_act<RANGE, false, 1> : k_int_affine_act<RANGE, false, 4>),
+                           g, dim3(kBlock), shm, st, xp, rp, yp, alpha_beta, q, a);
+    });
     return launch_rc();
 }
 

@@ -185,3 +185,37 @@ def test_mse_calibration_behind_bn_takes_the_fused_path(search, monkeypatch):
     for (mv1, m1), (mv2, m2) in zip(r1, r2):
         assert mv1.shape == mv2.shape
     np.testing.assert_allclose(y1.cpu().numpy(), y2.cpu().numpy(), atol=0.15 * float(y2.abs().max()))
+
+
+@pytest.mark.parametrize("shape", [(2, 8, 5, 5),         # 16-byte groups that cross planes
+                                   (3, 12, 1, 1),        # HW < 4: a group spans several planes
+                                   (3, 40, 33, 31)])     # several steps per block, ragged end
+def test_first_mse_batch_behind_bn_writes_the_epilogue_tensor(shape):
+    """The first calibration batch of an MSE estimator behind BN + residual + ReLU (MseCalibration.step(pre=...)) forms
+    t = relu(bn(x) + residual), its range and the search grid in one launch: t is affine_act's tensor, the range is
+    affine_act_minmax's, and the search ends as it does on affine_act's output -- all bit for bit."""
+    import fp8q
+    ops = fp8q.ops
+    rng = np.random.RandomState(shape[1] + shape[2])
+    N, C = shape[0], shape[1]
+    x, res = dev(rng.randn(*shape) * 2), dev(rng.randn(*shape))
+    invstd = np.float32(1) / np.sqrt((rng.rand(C) + 0.5).astype(np.float32) + np.float32(1e-5))
+    bn = tuple(dev(b) for b in (rng.randn(C), invstd, rng.rand(C) + 0.5, rng.randn(C)))
+    ab = ops.bn_fold(bn)
+
+    def bits(t):
+        return t.cpu().numpy().view(np.int32)
+
+    t = ops.affine_act(x, ab, res, 1)
+    mn, mx, mv = ops.affine_act_minmax(x, bn=bn, residual=res, act=1)
+    fused = ops.MseCalibration(1, x.device, [3.0], 8, 1)
+    y = fused.step(x, pre=(ab, res, 1))
+    searched = ops._workspace(x.device, 4 * x.numel(), kind="pre")[:4 * x.numel()].view(torch.float32).view(shape)
+    np.testing.assert_array_equal(bits(searched), bits(t))
+    for got, want in ((fused.cur_min, mn), (fused.cur_max, mx), (fused.absmax, mv)):
+        np.testing.assert_array_equal(bits(got), bits(want))
+    plain = ops.MseCalibration(1, x.device, [3.0], 8, 1)
+    y0 = plain.step(t)
+    np.testing.assert_array_equal(bits(y), bits(y0))
+    for name in ("cur_min", "cur_max", "absmax", "maxval", "grid", "mses"):
+        np.testing.assert_array_equal(bits(getattr(fused, name)), bits(getattr(plain, name)), err_msg=name)
