@@ -1,0 +1,439 @@
+// fp8q_mx.hip -- the microscaling (MX) lane (gfx950 only): blocks of 32 elements along the last dimension under ONE E8M0
+// power-of-two scale byte each, elements in OCP E4M3FN, E5M2 or the 4-bit E2M1 -- the operand form of gfx950's scaled matrix
+// instructions (v_mfma_scale_f32_*_f8f6f4) and of torch.float8_e8m0fnu / torch.float4_e2m1fn_x2.  Nothing here multiplies
+// matrices; the lane makes, reads and fake-quantizes the operands.
+//
+// Arithmetic contract (include/fp8q.h states it for callers).  The tensor is [R, K], K contiguous; row r is cut into the
+// blocks [32j, min(32j + 32, K)): the last block of a row may be short, no block crosses a row.
+//   format   emax   fmax    mantissa field of fmax
+//   E4M3FN     8     448    0x600000
+//   E5M2      15   57344    0x600000
+//   E2M1       2       6    0x400000
+//   m    = the largest bits(|x|) of the block, compared as unsigned integers (so NaN and inf patterns are the largest)
+//   E    = m >> 23, man = m & 0x7fffff
+//   code = max(E - emax + bump, 0)           bump = 0 (floor, the OCP MX v1.0 rule X = 2^(floor(log2 amax) - emax)) or
+//                                            man > man_fmax (ceil: the smallest power of two under which nothing saturates)
+//          0xFF when E == 255 (a NaN or an infinity anywhere in the block); a zero or subnormal-only block gives 0
+//   X    = 2^(code - 127) as fp32            code 0 is the subnormal 0x00400000, 0xFF is NaN
+//   q    = clamp(x * 2^(127 - code), -fmax, fmax)   ONE fp32 multiplication by an exactly representable power of two: exact
+//                                            unless it lands in fp32's subnormal range, far below every format's smallest
+//                                            midpoint, where the element is a zero of x's sign either way
+//   elem = RNE(q) in the element format      subnormals included, -0 keeps its sign (0x80 / 0x8); a 0xFF block stores 0x7F
+//                                            (FP8) / 0x0 (FP4) everywhere
+//   E2M1: the codes 0..7 are {0, .5, 1, 1.5, 2, 3, 4, 6}, the sign in bit 3, a tie goes to the even code; two elements
+//   share a byte, the even-indexed one in the low nibble (K must be even)
+//   decode(elem) = value(elem) * X           ONE fp32 multiplication, subnormal products kept; every element of a 0xFF block
+//                                            is NaN; a half output rounds that product once
+//   quantize(x)  = decode(encode(x))         the same device functions in one pass
+//
+// What does the conversions.  FP8: v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32 on the clamped q and v_cvt_f32_fp8 / v_cvt_f32_bf8,
+// exactly as fp8q_ocp.hip uses them (RNE, subnormals, -0, E5M2's infinities on decode).  FP4: integer arithmetic -- seven
+// comparisons against the midpoints {.25, .75, 1.25, 1.75, 2.5, 3.5, 5}, `>=` at those whose upper neighbour is the even
+// code -- and the value's bits built from the code.  gfx950's scaled conversions (v_cvt_scalef32_pk_fp4_f32 and kin) are
+// NOT used: nothing has shown yet that they reproduce this contract on subnormal inputs and ties.
+//
+// Kernels.  k_mx<MODE, F, IN, OUT, NT>, the fast route: K % 32 == 0 and x / y / codes 16-byte aligned.  Then blocks tile the
+// flat tensor, block b covers elements [32b, 32b + 32) and owns scale byte b, and a workgroup takes 4096 consecutive elements.
+//   encode: a lane owns 16 consecutive elements, its 16-byte loads (four of fp32, two of half) issued before any arithmetic;
+//           the two lanes of a block exchange their integer maxima in one DPP step; 16 FP8 codes leave as ONE
+//           16-byte word, 16 FP4 codes as one 8-byte word; the even lane stores the block's scale byte (a plain 1-byte store)
+//   decode, quantize: lane <-> group of 4 elements, four groups per lane 1024 elements apart, so that every store instruction
+//           of a wave writes whole lines; quantize folds the maxima of a block's 8 lanes in three DPP steps; decode reads the
+//           block's scale byte in each of its 8 lanes (one byte, broadcast by the cache)
+// Every element is read exactly once.  NT: nontemporal loads and stores from 64 MiB (kNtBytes), the rule of the INT kernels.
+// k_mx_plain<MODE, F, IN, OUT>, the general route (ragged K, misaligned views): one lane per block, element by element, the
+// block read twice by encode and quantize.  A correctness path; no rate is claimed for it.
+// One launch per call, nothing read back, no allocation, no workspace.
+// HBM traffic per element, fast route: FP8 encode 4 + 1 + 1/32 B (2 + 1 + 1/32 from half), FP4 encode 4 + 1/2 + 1/32.
+#include "fp8q_common.h"
+#include "fp8q_half.h"
+#include "fp8q_io.h"
+
+namespace {
+
+enum { kEncode, kDecode, kQuant };
+
+constexpr int kMxBlock = 32;          // elements under one scale byte
+constexpr int kMxChunk = 4096;        // elements per workgroup: 16 per lane (encode), 4 x 4 per lane (decode, quantize)
+
+template <int F>
+struct MxFmt;
+template <>
+struct MxFmt<FP8Q_MX_E4M3FN> {
+    static constexpr int emax = 8;
+    static constexpr float fmax = 448.0f;
+    static constexpr uint32_t man_fmax = 0x600000u;
+};
+template <>
+struct MxFmt<FP8Q_MX_E5M2> {
+    static constexpr int emax = 15;
+    static constexpr float fmax = 57344.0f;
+    static constexpr uint32_t man_fmax = 0x600000u;
+};
+template <>
+struct MxFmt<FP8Q_MX_E2M1> {
+    static constexpr int emax = 2;
+    static constexpr float fmax = 6.0f;
+    static constexpr uint32_t man_fmax = 0x400000u;
+};
+
+__device__ __forceinline__ uint32_t abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+
+// the scale byte of a block whose largest |x| has the bits m
+template <int F>
+__device__ __forceinline__ uint32_t scale_code(uint32_t m, int ceil_rule)
+{
+    const int E = (int)(m >> 23);
+    const int bump = (ceil_rule && (m & 0x7fffffu) > MxFmt<F>::man_fmax) ? 1 : 0;
+    const int c = E - MxFmt<F>::emax + bump;
+    return E == 255 ? 0xffu : (uint32_t)(c < 0 ? 0 : c);
+}
+
+// 2^(127 - code), the factor of the encoding side; code <= 253 here (E <= 254, emax >= 2), so the field is never 0
+__device__ __forceinline__ float scale_inv(uint32_t code) { return __uint_as_float((254u - code) << 23); }
+
+// X = 2^(code - 127)
+__device__ __forceinline__ float scale_value(uint32_t code)
+{
+    return __uint_as_float(code == 0u ? 0x00400000u : (code == 0xffu ? 0x7fc00000u : code << 23));
+}
+
+template <int F>
+__device__ __forceinline__ float mx_q(float v, float inv)
+{
+    return fminf(fmaxf(v * inv, -MxFmt<F>::fmax), MxFmt<F>::fmax);
+}
+
+// E2M1 code of a finite q within +-6: the midpoints below |q|, a tie to the even code, the sign in bit 3
+__device__ __forceinline__ uint32_t fp4_code(float q)
+{
+    const float a = fabsf(q);
+    const uint32_t c = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) +
+                       (uint32_t)(a > 2.5f) + (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);
+    return c | ((__float_as_uint(q) >> 28) & 8u);
+}
+
+// the value of an E2M1 code
+__device__ __forceinline__ float fp4_value(uint32_t code)
+{
+    const uint32_t e = (code >> 1) & 3u, m = code & 1u;
+    const uint32_t mag = e == 0u ? (m ? 0x3f000000u : 0u) : (((e + 126u) << 23) | (m << 22));
+    return __uint_as_float(mag | ((code & 8u) << 28));
+}
+
+// four values (finite, within +-fmax) -> four FP8 codes in a dword, the first in the low byte
+template <int F>
+__device__ __forceinline__ uint32_t fp8_cvt4(float a, float b, float c, float d)
+{
+    int w = 0;
+    if constexpr (F == FP8Q_MX_E4M3FN) {
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+    } else {
+        w = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, w, false);
+        w = __builtin_amdgcn_cvt_pk_bf8_f32(c, d, w, true);
+    }
+    return (uint32_t)w;
+}
+
+// The codes of four elements under the scale byte sc: FP8 a dword, FP4 the low 16 bits (element 0 in the low nibble)
+template <int F>
+__device__ __forceinline__ uint32_t mx_code4(const float *v, uint32_t sc)
+{
+    if (sc == 0xffu) return F == FP8Q_MX_E2M1 ? 0u : 0x7f7f7f7fu;
+    const float inv = scale_inv(sc);
+    const float q0 = mx_q<F>(v[0], inv), q1 = mx_q<F>(v[1], inv), q2 = mx_q<F>(v[2], inv), q3 = mx_q<F>(v[3], inv);
+    if constexpr (F == FP8Q_MX_E2M1) return fp4_code(q0) | (fp4_code(q1) << 4) | (fp4_code(q2) << 8) | (fp4_code(q3) << 12);
+    else return fp8_cvt4<F>(q0, q1, q2, q3);
+}
+
+// value(elem) * X of element B of mx_code4()'s word; a NaN (a NaN code, a NaN scale) is the one quiet NaN
+template <int F, int B>
+__device__ __forceinline__ float mx_value_at(uint32_t w, float X)
+{
+    float v;
+    if constexpr (F == FP8Q_MX_E2M1) v = fp4_value((w >> (4 * B)) & 0xfu);
+    else if constexpr (F == FP8Q_MX_E4M3FN) v = __builtin_amdgcn_cvt_f32_fp8((int)w, B);
+    else v = __builtin_amdgcn_cvt_f32_bf8((int)w, B);
+    const float y = v * X;
+    return (y != y) ? __uint_as_float(0x7fc00000u) : y;
+}
+
+template <int F>
+__device__ __forceinline__ void mx_value4(uint32_t w, uint32_t sc, float *y)
+{
+    const float X = scale_value(sc);
+    y[0] = mx_value_at<F, 0>(w, X);
+    y[1] = mx_value_at<F, 1>(w, X);
+    y[2] = mx_value_at<F, 2>(w, X);
+    y[3] = mx_value_at<F, 3>(w, X);
+}
+
+__device__ __forceinline__ uint32_t umax4(const float *v)
+{
+    const uint32_t a = abs_bits(v[0]), b = abs_bits(v[1]), c = abs_bits(v[2]), d = abs_bits(v[3]);
+    const uint32_t ab = a > b ? a : b, cd = c > d ? c : d;
+    return ab > cd ? ab : cd;
+}
+
+// max with the lane STEP away by xor, as one DPP move (every lane of the wave is live where this runs): quad_perm [1,0,3,2]
+// and [2,3,0,1] for 1 and 2; for 4, once a quad agrees, row_half_mirror (lane i <-> 7 - i of its 8) reaches the other quad
+template <int STEP>
+__device__ __forceinline__ uint32_t umax_xor(uint32_t m)
+{
+    constexpr int ctrl = STEP == 1 ? 0xB1 : (STEP == 2 ? 0x4E : 0x141);
+    const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, ctrl, 0xf, 0xf, false);
+    return o > m ? o : m;
+}
+
+struct MxArgs {
+    const uint8_t *scales_in;     // decode
+    uint8_t *scales_out;          // encode
+    int64_t n;                    // elements
+    int64_t K;                    // row length
+    int64_t nb;                   // blocks per row
+    int64_t blocks;               // R * nb
+    int ceil_rule;
+};
+
+// ---- the fast route: n % 32 == 0, blocks tile the flat tensor, every vector word aligned ----
+template <int MODE, int F, class IN, class OUT, bool NT>
+__global__ void __launch_bounds__(kBlock)
+k_mx(const void *__restrict__ in, void *__restrict__ out, MxArgs a)
+{
+    typedef typename IN::elem in_t;
+    typedef typename OUT::elem out_t;
+    const int tid = threadIdx.x;
+    const int64_t e0 = (int64_t)blockIdx.x * kMxChunk;
+    const int left = (int)(a.n - e0 < kMxChunk ? a.n - e0 : kMxChunk);      // a multiple of 32
+    const in_t *x = static_cast<const in_t *>(in);
+    out_t *y = static_cast<out_t *>(out);
+    if constexpr (MODE == kEncode) {
+        // lanes 2i and 2i + 1 hold block i of the chunk; `left` is a multiple of 32, so both are live or neither is, and the
+        // shuffle runs in every lane
+        const bool live = 16 * tid < left;
+        const int64_t e = e0 + 16 * tid;
+        float v[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = 0.0f;
+        if (live) IN::template load16<NT>(x + e, v);
+        uint32_t m = umax4(v);
+#pragma unroll
+        for (int g = 1; g < 4; ++g) {
+            const uint32_t t = umax4(v + 4 * g);
+            m = t > m ? t : m;
+        }
+        m = umax_xor<1>(m);
+        const uint32_t sc = scale_code<F>(m, a.ceil_rule);
+        uint32_t w[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) w[g] = mx_code4<F>(v + 4 * g, sc);
+        if (live) {
+            if constexpr (F == FP8Q_MX_E2M1)
+                stv<NT>(reinterpret_cast<vu2 *>(y + (e >> 1)), vu2{w[0] | (w[1] << 16), w[2] | (w[3] << 16)});
+            else
+                stv<NT>(reinterpret_cast<vu4 *>(y + e), vu4{w[0], w[1], w[2], w[3]});
+            if (!(tid & 1)) a.scales_out[e >> 5] = (uint8_t)sc;
+        }
+    } else {
+        // lanes 8i .. 8i + 7 hold a block; a partial chunk ends on a block, so the folds see live lanes only -- and the loop
+        // is uniform, so every lane runs them
+        auto group = [&](const float *v, uint32_t w, int off, bool live) {
+            uint32_t sc = 0u;
+            if constexpr (MODE == kQuant) {
+                uint32_t m = umax4(v);
+                m = umax_xor<1>(m);
+                m = umax_xor<2>(m);
+                m = umax_xor<4>(m);
+                sc = scale_code<F>(m, a.ceil_rule);
+                w = mx_code4<F>(v, sc);
+            } else if (live) {
+                sc = a.scales_in[(e0 + off) >> 5];
+            }
+            float r[4];
+            mx_value4<F>(w, sc, r);
+            if (live) OUT::template store4<NT>(y + e0 + off, r);
+        };
+        auto fetch = [&](float *v, uint32_t &w, int off, bool live) {
+            v[0] = v[1] = v[2] = v[3] = 0.0f;
+            w = 0u;
+            if (!live) return;
+            if constexpr (MODE == kQuant) IN::template load4<NT>(x + e0 + off, v);
+            else if constexpr (F == FP8Q_MX_E2M1) w = ldv<NT>(reinterpret_cast<const uint16_t *>(x + ((e0 + off) >> 1)));
+            else w = IoCodes::load4<NT>(x + e0 + off);
+        };
+        if (left == kMxChunk) {
+            float v[4][4];
+            uint32_t w[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) fetch(v[u], w[u], 4 * (u * kBlock + tid), true);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) group(v[u], w[u], 4 * (u * kBlock + tid), true);
+        } else {
+            for (int base = 0; base < left; base += 4 * kBlock) {
+                const int off = base + 4 * tid;
+                const bool live = off < left;
+                float v[4];
+                uint32_t w;
+                fetch(v, w, off, live);
+                group(v, w, off, live);
+            }
+        }
+    }
+}
+
+// ---- the general route: one lane per block, element by element ----
+template <int MODE, int F, class IN, class OUT>
+__global__ void __launch_bounds__(kBlock)
+k_mx_plain(const void *__restrict__ in, void *__restrict__ out, MxArgs a)
+{
+    typedef typename IN::elem in_t;
+    typedef typename OUT::elem out_t;
+    const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (b >= a.blocks) return;
+    const int64_t row = b / a.nb, j = b - row * a.nb;
+    const int64_t base = row * a.K + kMxBlock * j;
+    const int len = (int)(a.K - kMxBlock * j < kMxBlock ? a.K - kMxBlock * j : kMxBlock);
+    const in_t *x = static_cast<const in_t *>(in);
+    out_t *y = static_cast<out_t *>(out);
+    uint32_t sc;
+    if constexpr (MODE == kDecode) {
+        sc = a.scales_in[b];
+    } else {
+        uint32_t m = 0u;
+        for (int i = 0; i < len; ++i) {
+            const uint32_t t = abs_bits(IN::load1(x + base + i));
+            m = t > m ? t : m;
+        }
+        sc = scale_code<F>(m, a.ceil_rule);
+        if constexpr (MODE == kEncode) a.scales_out[b] = (uint8_t)sc;
+    }
+    // E2M1: K is even, so base and len are: the two elements of a byte lie in one block
+    constexpr int kStep = F == FP8Q_MX_E2M1 ? 2 : 1;
+    for (int i = 0; i < len; i += kStep) {
+        const int64_t e = base + i;
+        uint32_t w;
+        if constexpr (MODE == kDecode) {
+            w = x[F == FP8Q_MX_E2M1 ? e >> 1 : e];
+        } else {
+            float v[4] = {IN::load1(x + e), 0.0f, 0.0f, 0.0f};
+            if constexpr (F == FP8Q_MX_E2M1) v[1] = IN::load1(x + e + 1);
+            w = mx_code4<F>(v, sc) & 0xffu;
+        }
+        if constexpr (MODE == kEncode) {
+            y[F == FP8Q_MX_E2M1 ? e >> 1 : e] = (uint8_t)w;
+        } else {
+            const float X = scale_value(sc);
+            OUT::store1(y + e, mx_value_at<F, 0>(w, X));
+            if constexpr (F == FP8Q_MX_E2M1) OUT::store1(y + e + 1, mx_value_at<F, 1>(w, X));
+        }
+    }
+}
+
+template <int MODE, int F, class IN, class OUT>
+void launch_io(const void *in, void *out, const MxArgs &a, bool fast, hipStream_t st)
+{
+    const dim3 b(kBlock);
+    if (!fast) {
+        hipLaunchKernelGGL((k_mx_plain<MODE, F, IN, OUT>), dim3((unsigned)cdiv(a.blocks, kBlock)), b, 0, st, in, out, a);
+        return;
+    }
+    const dim3 g((unsigned)cdiv(a.n, kMxChunk));
+    if (a.n * 4 >= kNtBytes) hipLaunchKernelGGL((k_mx<MODE, F, IN, OUT, true>), g, b, 0, st, in, out, a);
+    else hipLaunchKernelGGL((k_mx<MODE, F, IN, OUT, false>), g, b, 0, st, in, out, a);
+}
+
+template <int MODE, class IN, class OUT>
+void launch_fmt(int fmt, const void *in, void *out, const MxArgs &a, bool fast, hipStream_t st)
+{
+    if (fmt == FP8Q_MX_E4M3FN) launch_io<MODE, FP8Q_MX_E4M3FN, IN, OUT>(in, out, a, fast, st);
+    else if (fmt == FP8Q_MX_E5M2) launch_io<MODE, FP8Q_MX_E5M2, IN, OUT>(in, out, a, fast, st);
+    else launch_io<MODE, FP8Q_MX_E2M1, IN, OUT>(in, out, a, fast, st);
+}
+
+// Argument checks (everything is reported before the launch) and the one launch.  in_type / out_type: FP8Q_DT_* of the value
+// side(s), -1 for the side that holds codes.  scales: written by encode, read by decode, unused (null) by quantize.
+int mx_launch(int mode, const void *in, void *out, const uint8_t *scales, int in_type, int out_type, int64_t R, int64_t K,
+              int fmt, int rounding, hipStream_t st)
+{
+    if (!in || !out || (mode != kQuant && !scales) || R <= 0 || K <= 0) return FP8Q_EINVAL;
+    if (fmt != FP8Q_MX_E4M3FN && fmt != FP8Q_MX_E5M2 && fmt != FP8Q_MX_E2M1) return FP8Q_EUNSUPPORTED;
+    if (rounding != FP8Q_MX_FLOOR && rounding != FP8Q_MX_CEIL) return FP8Q_EINVAL;
+    if (fmt == FP8Q_MX_E2M1 && (K & 1)) return FP8Q_EINVAL;
+    auto misaligned = [](const void *p, int type) {
+        return type < 0 ? false : (((uintptr_t)p) & (uintptr_t)(type == FP8Q_DT_F32 ? 3 : 1)) != 0;
+    };
+    if (misaligned(in, in_type) || misaligned(out, out_type)) return FP8Q_EINVAL;
+    const int64_t nb = cdiv(K, kMxBlock);
+    if (R > INT64_MAX / K || R > INT64_MAX / nb || cdiv(R * nb, kBlock) > (int64_t)INT32_MAX) return FP8Q_EINVAL;
+    MxArgs a = {};
+    a.scales_in = scales;
+    a.scales_out = const_cast<uint8_t *>(scales);
+    a.n = R * K;
+    a.K = K;
+    a.nb = nb;
+    a.blocks = R * nb;
+    a.ceil_rule = rounding == FP8Q_MX_CEIL;
+    const bool fast = K % kMxBlock == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
+    const bool f16 = in_type == FP8Q_DT_F16 || out_type == FP8Q_DT_F16;
+    if (mode == kEncode) {
+        if (in_type == FP8Q_DT_F32) launch_fmt<kEncode, IoF32, IoCodes>(fmt, in, out, a, fast, st);
+        else if (f16) launch_fmt<kEncode, IoH16<F16>, IoCodes>(fmt, in, out, a, fast, st);
+        else launch_fmt<kEncode, IoH16<BF16>, IoCodes>(fmt, in, out, a, fast, st);
+    } else if (mode == kDecode) {
+        if (out_type == FP8Q_DT_F32) launch_fmt<kDecode, IoCodes, IoF32>(fmt, in, out, a, fast, st);
+        else if (f16) launch_fmt<kDecode, IoCodes, IoH16<F16>>(fmt, in, out, a, fast, st);
+        else launch_fmt<kDecode, IoCodes, IoH16<BF16>>(fmt, in, out, a, fast, st);
+    } else {
+        if (in_type == FP8Q_DT_F32) launch_fmt<kQuant, IoF32, IoF32>(fmt, in, out, a, fast, st);
+        else if (f16 && out_type == FP8Q_DT_F32) launch_fmt<kQuant, IoH16<F16>, IoF32>(fmt, in, out, a, fast, st);
+        else if (f16) launch_fmt<kQuant, IoH16<F16>, IoH16<F16>>(fmt, in, out, a, fast, st);
+        else if (out_type == FP8Q_DT_F32) launch_fmt<kQuant, IoH16<BF16>, IoF32>(fmt, in, out, a, fast, st);
+        else launch_fmt<kQuant, IoH16<BF16>, IoH16<BF16>>(fmt, in, out, a, fast, st);
+    }
+    return launch_rc();
+}
+
+}  // namespace
+
+extern "C" {
+
+int fp8q_mx_encode_f32(const float *x, uint8_t *codes, uint8_t *scales, int64_t R, int64_t K, int fmt, int rounding,
+                       fp8q_stream_t stream)
+{
+    return mx_launch(kEncode, x, codes, scales, FP8Q_DT_F32, -1, R, K, fmt, rounding, (hipStream_t)stream);
+}
+
+int fp8q_mx_encode_h16(const void *x, uint8_t *codes, uint8_t *scales, int x_type, int64_t R, int64_t K, int fmt,
+                       int rounding, fp8q_stream_t stream)
+{
+    if (!half_type(x_type)) return FP8Q_EINVAL;
+    return mx_launch(kEncode, x, codes, scales, x_type, -1, R, K, fmt, rounding, (hipStream_t)stream);
+}
+
+int fp8q_mx_decode_f32(const uint8_t *codes, const uint8_t *scales, float *y, int64_t R, int64_t K, int fmt,
+                       fp8q_stream_t stream)
+{
+    return mx_launch(kDecode, codes, y, scales, -1, FP8Q_DT_F32, R, K, fmt, FP8Q_MX_FLOOR, (hipStream_t)stream);
+}
+
+int fp8q_mx_decode_h16(const uint8_t *codes, const uint8_t *scales, void *y, int y_type, int64_t R, int64_t K, int fmt,
+                       fp8q_stream_t stream)
+{
+    if (!half_type(y_type)) return FP8Q_EINVAL;
+    return mx_launch(kDecode, codes, y, scales, -1, y_type, R, K, fmt, FP8Q_MX_FLOOR, (hipStream_t)stream);
+}
+
+int fp8q_mx_quantize_f32(const float *x, float *y, int64_t R, int64_t K, int fmt, int rounding, fp8q_stream_t stream)
+{
+    return mx_launch(kQuant, x, y, nullptr, FP8Q_DT_F32, FP8Q_DT_F32, R, K, fmt, rounding, (hipStream_t)stream);
+}
+
+int fp8q_mx_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int fmt, int rounding,
+                         fp8q_stream_t stream)
+{
+    if (int rc = check_types(x_type, y_type)) return rc;
+    return mx_launch(kQuant, x, y, nullptr, x_type, y_type, R, K, fmt, rounding, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -48,6 +48,7 @@
 #include "fp8q_common.h"
 #include "fp8q_half.h"
 #include "fp8q_intq.h"
+#include "fp8q_io.h"
 
 namespace {
 
@@ -153,76 +154,6 @@ __device__ __forceinline__ void value4(uint32_t w, const float4 *k, float *y)
     y[2] = value_at<F, 2>(w, k[2].x);
     y[3] = value_at<F, 3>(w, k[3].x);
 }
-
-// ---- a lane's 16 elements on either side: fp32, half (T = F16 / BF16), codes ----
-typedef uint32_t vu4 __attribute__((ext_vector_type(4)));
-typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
-
-struct IoF32 {
-    typedef float elem;
-    template <bool NT>
-    static __device__ __forceinline__ void load16(const elem *p, float *v)
-    {
-        const vf4 *q = reinterpret_cast<const vf4 *>(p);
-        vf4 t[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) t[j] = ldv<NT>(q + j);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[4 * j] = t[j].x;
-            v[4 * j + 1] = t[j].y;
-            v[4 * j + 2] = t[j].z;
-            v[4 * j + 3] = t[j].w;
-        }
-    }
-    template <bool NT>
-    static __device__ __forceinline__ void load4(const elem *p, float *v)
-    {
-        const vf4 t = ldv<NT>(reinterpret_cast<const vf4 *>(p));
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    }
-    template <bool NT>
-    static __device__ __forceinline__ void store4(elem *p, const float *v)
-    {
-        stv<NT>(reinterpret_cast<vf4 *>(p), vf4{v[0], v[1], v[2], v[3]});
-    }
-    static __device__ __forceinline__ float load1(const elem *p) { return *p; }
-    static __device__ __forceinline__ void store1(elem *p, float v) { *p = v; }
-};
-
-template <class T>
-struct IoH16 {
-    typedef uint16_t elem;
-    template <bool NT>
-    static __device__ __forceinline__ void load16(const elem *p, float *v)
-    {
-        const vu4 *q = reinterpret_cast<const vu4 *>(p);
-        const vu4 a = ldv<NT>(q), b = ldv<NT>(q + 1);
-        const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) T::widen2(w[j], v[2 * j], v[2 * j + 1]);
-    }
-    template <bool NT>
-    static __device__ __forceinline__ void load4(const elem *p, float *v)
-    {
-        const vu2 t = ldv<NT>(reinterpret_cast<const vu2 *>(p));
-        T::widen2(t.x, v[0], v[1]);
-        T::widen2(t.y, v[2], v[3]);
-    }
-    template <bool NT>
-    static __device__ __forceinline__ void store4(elem *p, const float *v)
-    {
-        stv<NT>(reinterpret_cast<vu2 *>(p), vu2{T::narrow2(v[0], v[1]), T::narrow2(v[2], v[3])});
-    }
-    static __device__ __forceinline__ float load1(const elem *p) { return T::widen1(*p); }
-    static __device__ __forceinline__ void store1(elem *p, float v) { *p = T::narrow1(v); }
-};
-
-struct IoCodes {
-    typedef uint8_t elem;
-    template <bool NT>
-    static __device__ __forceinline__ uint32_t load4(const elem *p) { return ldv<NT>(reinterpret_cast<const uint32_t *>(p)); }
-};
 
 // the row constants {scale, 1/scale} of the encoding side: scale from (maxval, eps), reported where the row starts
 template <int F>

@@ -1595,6 +1595,153 @@ def ocp_quantize(x, maxval, fmt, eps=1e-8, out=None, out_dtype=None):
     return y
 
 
+# ---- microscaling: blocks of 32 under an E8M0 scale byte (csrc/fp8q_mx.hip; the contract is in include/fp8q.h) ----
+_MX_FMT = {torch.float8_e4m3fn: 0, torch.float8_e5m2: 1, torch.float4_e2m1fn_x2: 2}      # FP8Q_MX_* (include/fp8q.h)
+_MX_ROUNDING = {"floor": 0, "ceil": 1}
+MX_BLOCK = 32
+MX_SCALE_DTYPE = torch.float8_e8m0fnu
+
+
+def _mx_fmt(fmt):
+    if fmt not in _MX_FMT:
+        raise Fp8qError(f"fmt must be torch.float8_e4m3fn, torch.float8_e5m2 or torch.float4_e2m1fn_x2, got {fmt}")
+    return _MX_FMT[fmt]
+
+
+def _mx_rounding(rounding):
+    if rounding not in _MX_ROUNDING:
+        raise Fp8qError(f"rounding must be 'floor' or 'ceil', got {rounding!r}")
+    return _MX_ROUNDING[rounding]
+
+
+def _mx_geometry(shape, fmt):
+    """(lead, R, K, codes shape, scales shape) of values shaped `shape`: blocks run along the last dimension"""
+    if len(shape) == 0:
+        raise Fp8qError("MX blocks run along the last dimension: the tensor needs at least one")
+    lead, K = tuple(shape[:-1]), int(shape[-1])
+    R = 1
+    for s in lead:
+        R *= int(s)
+    if fmt == torch.float4_e2m1fn_x2 and K % 2:
+        raise Fp8qError(f"two E2M1 elements share a byte: the last dimension must be even, got {K}")
+    kc = K // 2 if fmt == torch.float4_e2m1fn_x2 else K
+    return R, K, lead + (kc,), lead + ((K + MX_BLOCK - 1) // MX_BLOCK,)
+
+
+def _mx_bytes(out, shape, dtype, name, like):
+    """a uint8 view of a fresh tensor of `dtype` shaped `shape`, or of the caller's (uint8 or `dtype`, contiguous, as large)"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=like.device)
+    _require(out, name, (torch.uint8, dtype), like)
+    n = 1
+    for s in shape:
+        n *= s
+    if out.numel() != n or not out.is_contiguous():
+        raise Fp8qError(f"{name} must be a contiguous tensor of {n} elements (got {tuple(out.shape)}, "
+                        f"contiguous={out.is_contiguous()})")
+    return out.view(torch.uint8)
+
+
+def mx_encode(x, fmt, rounding="floor", out=None, scales_out=None):
+    """MX operands of x: (codes, scales).  Blocks of 32 along the last dimension, one E8M0 scale byte each (include/fp8q.h
+    states the arithmetic).  fmt: torch.float8_e4m3fn / torch.float8_e5m2 (codes shaped like x) or torch.float4_e2m1fn_x2
+    (codes [..., K / 2], the even-indexed element in the low nibble; K must be even).  scales: torch.float8_e8m0fnu
+    [..., ceil(K / 32)].  rounding: "floor" (OCP MX v1.0: the largest elements of a block may saturate) or "ceil" (the smallest
+    power of two under which none does).  x float32, or float16 / bfloat16 (widened exactly).  `out` / `scales_out`: contiguous
+    tensors of the result's dtype or uint8.  One launch; the range is found in the same pass."""
+    f, r = _mx_fmt(fmt), _mx_rounding(rounding)
+    _require(x, "x", _VALUES)
+    x = x.detach().contiguous()
+    R, K, cshape, sshape = _mx_geometry(x.shape, fmt)
+    codes = _mx_bytes(out, cshape, fmt, "out", x)
+    scales = _mx_bytes(scales_out, sshape, MX_SCALE_DTYPE, "scales_out", x)
+    if x.numel():
+        with _on_device(x):
+            if x.dtype in _HALF:
+                fn = "fp8q_mx_encode_h16"
+                rc = lib().fp8q_mx_encode_h16(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), _DT[x.dtype], R, K, f, r,
+                                              _stream(x))
+            else:
+                fn = "fp8q_mx_encode_f32"
+                rc = lib().fp8q_mx_encode_f32(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), R, K, f, r, _stream(x))
+        check(rc, fn)
+    return codes.view(fmt).view(cshape), scales.view(MX_SCALE_DTYPE).view(sshape)
+
+
+def mx_decode(codes, scales, fmt=None, out_dtype=None, out=None):
+    """Values of MX operands: value(elem) * 2^(scale - 127), one float32 multiplication; every element of a 0xFF block is NaN.
+    codes: a CUDA tensor of an MX element dtype, or uint8 with `fmt` naming the format; scales: torch.float8_e8m0fnu or uint8,
+    one per block of 32 along the last dimension (mx_encode's).  float32 unless a float16 / bfloat16 `out` or out_dtype asks
+    for a half type (the float32 product rounded once).  One launch."""
+    dt = _decode_out_dtype(out, out_dtype)
+    if not isinstance(codes, torch.Tensor) or not codes.is_cuda:
+        raise Fp8qError("codes must be a CUDA(HIP) tensor: the FP8 engine has no CPU path")
+    if codes.dtype in _MX_FMT:
+        if fmt is not None and fmt != codes.dtype:
+            raise Fp8qError(f"codes are {codes.dtype} but fmt is {fmt}")
+        fmt = codes.dtype
+    elif codes.dtype != torch.uint8:
+        raise Fp8qError(f"codes must be float8_e4m3fn, float8_e5m2, float4_e2m1fn_x2 or uint8, got {codes.dtype}")
+    elif fmt is None:
+        raise Fp8qError("uint8 codes carry no format: pass fmt=")
+    f = _mx_fmt(fmt)
+    _require(scales, "scales", (MX_SCALE_DTYPE, torch.uint8), codes)
+    if codes.dim() == 0:
+        raise Fp8qError("MX blocks run along the last dimension: codes need at least one")
+    codes = codes.contiguous().view(torch.uint8)
+    vshape = tuple(codes.shape[:-1]) + (codes.shape[-1] * (2 if fmt == torch.float4_e2m1fn_x2 else 1),)
+    R, K, _, sshape = _mx_geometry(vshape, fmt)
+    scales = scales.contiguous().view(torch.uint8)
+    if tuple(scales.shape) != sshape:
+        raise Fp8qError(f"scales are {tuple(scales.shape)}, values of shape {vshape} have {sshape}")
+    if out is None:
+        y = torch.empty(vshape, dtype=dt, device=codes.device)
+    else:
+        _require(out, "out", dt, codes)
+        if out.numel() != R * K or not out.is_contiguous():
+            raise Fp8qError(f"out must be a contiguous tensor of {R * K} elements (got {tuple(out.shape)}, "
+                            f"contiguous={out.is_contiguous()})")
+        y = out
+    if R * K == 0:
+        return y
+    with _on_device(codes):
+        if dt in _HALF:
+            fn = "fp8q_mx_decode_h16"
+            rc = lib().fp8q_mx_decode_h16(codes.data_ptr(), scales.data_ptr(), y.data_ptr(), _DT[dt], R, K, f, _stream(codes))
+        else:
+            fn = "fp8q_mx_decode_f32"
+            rc = lib().fp8q_mx_decode_f32(codes.data_ptr(), scales.data_ptr(), y.data_ptr(), R, K, f, _stream(codes))
+    check(rc, fn)
+    return y
+
+
+def mx_quantize(x, fmt, rounding="floor", out_dtype=None, out=None):
+    """Fake-quantize the way an MX matrix multiplication sees x: mx_decode(*mx_encode(x, fmt, rounding)) bit for bit, in one
+    launch, the scales never leaving the registers.  x float32 gives float32; x float16 / bfloat16 gives float32 unless `out`
+    or out_dtype=x.dtype ask for x's own dtype (the float32 result rounded once)."""
+    f, r = _mx_fmt(fmt), _mx_rounding(rounding)
+    _require(x, "x", _VALUES)
+    if x.dtype in _HALF:
+        dt = _half_out_dtype(x, out, out_dtype)
+    else:
+        _check_out_dtype(x, out_dtype)
+        dt = torch.float32
+    x = x.detach().contiguous()
+    R, K, _, _ = _mx_geometry(x.shape, fmt)
+    y = _out(out, x, dt)
+    if x.numel() == 0:
+        return y
+    with _on_device(x):
+        if x.dtype in _HALF:
+            fn = "fp8q_mx_quantize_h16"
+            rc = lib().fp8q_mx_quantize_h16(x.data_ptr(), y.data_ptr(), _DT[x.dtype], _DT[dt], R, K, f, r, _stream(x))
+        else:
+            fn = "fp8q_mx_quantize_f32"
+            rc = lib().fp8q_mx_quantize_f32(x.data_ptr(), y.data_ptr(), R, K, f, r, _stream(x))
+    check(rc, fn)
+    return y
+
+
 def _nchw(x):
     """[N, C, *spatial] -> (N, C, HW)."""
     if x.dim() < 2:

@@ -110,6 +110,8 @@ class QuantizationManager(nn.Module):
 
     def forward(self, x):
         q, est = self.quantizer, self.range_estimator
+        if getattr(q, "range_free", False):
+            return q(x)                              # block-scaled (MXQuantizer): no range in any state, half tensors as they are
         half = isinstance(x, torch.Tensor) and x.dtype in (torch.float16, torch.bfloat16) and x.is_cuda
         if half and type(q) is not FPQuantizer and not (type(q) in _UNIFORM and q.keep_dtype):
             x, half = x.float(), False               # INT without keep_dtype / custom quantizers: float32-only

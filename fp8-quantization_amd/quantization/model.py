@@ -329,6 +329,41 @@ def decode_ocp_weights(exported, device="cuda", dtype=None):
             for name, e in exported.items()}
 
 
+def export_mx_weights(model):
+    """{layer name: {codes, scales, fmt, shape}} for every layer whose weights go through an MXQuantizer -- the twin of
+    export_ocp_weights for the block-scaled formats: codes is a CPU tensor of dtype torch.float8_e4m3fn / torch.float8_e5m2
+    ([..., K]) or torch.float4_e2m1fn_x2 ([..., K / 2]), scales a CPU torch.float8_e8m0fnu tensor [..., ceil(K / 32)], both
+    cut as the quantizer cuts the weight (flatten_rows: [shape[0], -1]); shape is the weight's.  An MX quantizer has no range,
+    so the manager's state does not matter.  decode(codes, scales) == the layer's quantized weight bit for bit.  float16 /
+    bfloat16 weights are encoded as they are (fp8q_mx_encode_h16: the codes of the exactly widened weight)."""
+    from .layers import QuantizationHijacker
+    from .mx import MXQuantizer
+    out = {}
+    for name, m in model.named_modules():
+        if not isinstance(m, QuantizationHijacker) or not getattr(m, "_qw", False):
+            continue
+        if type(m).quantize_weights is not QuantizationHijacker.quantize_weights:
+            continue
+        q = getattr(m.weight_quantizer, "quantizer", None)
+        if not isinstance(q, MXQuantizer):
+            continue
+        w = m.get_weight_bias()[0].detach()
+        if not w.is_cuda:
+            continue
+        codes, scales = q.encode(w)
+        out[name] = dict(codes=codes.cpu(), scales=scales.cpu(), fmt=q.fmt, shape=tuple(w.shape))
+    return out
+
+
+def decode_mx_weights(exported, device="cuda", dtype=None):
+    """{layer name: tensor} from export_mx_weights(): the values the layers compute with, shaped like the weights, float32 or
+    `dtype` (float16 / bfloat16: the float32 value rounded once)."""
+    import fp8q
+    return {name: fp8q.ops.mx_decode(e["codes"].to(device), e["scales"].to(device), fmt=e["fmt"],
+                                     out_dtype=dtype).view(e["shape"])
+            for name, e in exported.items()}
+
+
 class GraphedForward:
     """HIP graph of `model(x)` for one input shape.  With FIXED ranges nothing in a quantized forward is decided on
     the host (the engine's entry points only enqueue kernels on the current stream), so the whole forward can be

@@ -1,0 +1,91 @@
+"""Microscaling (MX) fake-quantizer: blocks of 32 elements under one E8M0 power-of-two scale byte, elements in OCP E4M3FN,
+E5M2 or the 4-bit E2M1 -- the operands of the MI355X's scaled matrix instructions, held by torch.float8_e8m0fnu and
+torch.float4_e2m1fn_x2.
+
+    forward(x) = decode(encode(x))      on the kernels of csrc/fp8q_mx.hip (include/fp8q.h states the arithmetic)
+
+The scale of a block is a function of that block's own largest element, found inside the quantizing pass: there is no range
+to estimate, calibrate, fix or learn.  `range_free = True` tells QuantizationManager so -- it calls the quantizer directly in
+every state and never runs its estimator.  Blocks run along the last dimension, the reduction dimension of a Linear weight
+[out, in] and of its input; flatten_rows=True views a tensor of more than two dimensions as [shape[0], -1] first, which is
+what a convolution weight [out, in, kh, kw] wants.
+
+It follows the quantizer protocol (QuantizerBase) and the model zoo takes it as `method=MXQuantizer`; it is deliberately NOT a
+member of QMethods (the CLI's choices).  Forward only: there is no backward kernel, and a call that would need a gradient
+raises NotImplementedError.  There is no CPU path.
+"""
+import torch
+
+from fp8q import ops as _ops
+from .fp8 import QuantizerBase
+
+_HALF = (torch.float16, torch.bfloat16)
+_BITS = {torch.float8_e4m3fn: 8, torch.float8_e5m2: 8, torch.float4_e2m1fn_x2: 4}
+_NAME = {torch.float8_e4m3fn: "E4M3FN", torch.float8_e5m2: "E5M2", torch.float4_e2m1fn_x2: "E2M1"}
+
+
+class MXQuantizer(QuantizerBase):
+    range_free = True
+
+    def __init__(self, n_bits=None, fmt=torch.float8_e4m3fn, rounding="floor", keep_dtype=False, flatten_rows=False,
+                 per_channel=False, scale_domain=None, **kwargs):
+        if fmt not in _BITS:
+            raise ValueError(f"fmt must be torch.float8_e4m3fn, torch.float8_e5m2 or torch.float4_e2m1fn_x2, got {fmt}")
+        if n_bits is not None and n_bits != _BITS[fmt]:
+            raise ValueError(f"{_NAME[fmt]} elements have {_BITS[fmt]} bits, got n_bits={n_bits}")
+        if rounding not in ("floor", "ceil"):
+            raise ValueError(f"rounding must be 'floor' or 'ceil', got {rounding!r}")
+        # per_channel is the protocol's argument; the scales are per block either way
+        super().__init__(n_bits=_BITS[fmt], per_channel=per_channel, **kwargs)
+        self.fmt = fmt
+        self.rounding = rounding
+        # float16 / bfloat16 inputs: False returns float32, True the input's dtype (the float32 value rounded once)
+        self.keep_dtype = keep_dtype
+        self.flatten_rows = flatten_rows
+
+    @property
+    def is_initialized(self):
+        return True
+
+    @property
+    def symmetric(self):
+        return True
+
+    def reset(self):
+        pass
+
+    def set_quant_range(self, x_min, x_max):
+        pass
+
+    def fix_ranges(self):
+        pass
+
+    def make_range_trainable(self):
+        raise NotImplementedError("MXQuantizer is forward-only and has no range: nothing can be learned")
+
+    def _rows(self, t):
+        """t as the kernels cut it into blocks: along the last dimension, of [shape[0], -1] with flatten_rows"""
+        if self.flatten_rows and t.dim() > 2:
+            return t.contiguous().view(t.shape[0], -1)
+        return t
+
+    def forward(self, x_float):
+        if torch.is_grad_enabled() and x_float.requires_grad:
+            raise NotImplementedError("MXQuantizer is forward-only: there is no backward kernel for the MX lane (call it "
+                                      "under torch.no_grad(), or on a detached tensor)")
+        out_dtype = x_float.dtype if (self.keep_dtype and x_float.dtype in _HALF) else None
+        y = _ops.mx_quantize(self._rows(x_float), self.fmt, self.rounding, out_dtype=out_dtype)
+        return y.view(x_float.shape)
+
+    def encode(self, x_float):
+        """(codes, scales) of forward(x): codes of dtype `fmt` ([..., K] for FP8, [..., K / 2] for E2M1), scales
+        torch.float8_e8m0fnu [..., ceil(K / 32)]; with flatten_rows, of the [shape[0], -1] view."""
+        return _ops.mx_encode(self._rows(x_float.detach()), self.fmt, self.rounding)
+
+    def decode(self, codes, scales, out_dtype=None):
+        """Values of encode()'s operands, float32 or out_dtype (float16 / bfloat16: the float32 value rounded once), shaped as
+        encode() saw them: decode(*encode(x)) == forward(x) bit for bit (after .view(x.shape) with flatten_rows)."""
+        return _ops.mx_decode(codes, scales, fmt=self.fmt, out_dtype=out_dtype)
+
+    def extra_repr(self):
+        return f"{super().extra_repr()}, fmt={_NAME[self.fmt]}, rounding={self.rounding}, flatten_rows={self.flatten_rows}"

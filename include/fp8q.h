@@ -834,6 +834,61 @@ int fp8q_ocp_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_
                           int64_t n_maxval, int fmt, float eps, fp8q_stream_t stream);
 int fp8q_ocp_scale_f32(const float *maxval, int64_t n, int fmt, float eps, float *scale, fp8q_stream_t stream);
 
+/* ---- microscaling (MX): blocks of 32 under an E8M0 scale byte, elements in E4M3FN / E5M2 / E2M1 (csrc/fp8q_mx.hip) ---------
+ * The operand form of gfx950's scaled matrix instructions (v_mfma_scale_f32_*_f8f6f4), carried by torch.float8_e8m0fnu and
+ * torch.float4_e2m1fn_x2.  These entries make, read and fake-quantize such operands; nothing here performs the multiplication,
+ * and the scale bytes are in plain [R, ceil(K / 32)] order, not in any library's pre-swizzled layout.
+ * Arithmetic contract.  The tensor is [R, K], K contiguous.  Row r is cut into the blocks [32j, min(32j + 32, K)): the last
+ * block of a row may be short, and no block crosses a row.
+ *   fmt              emax    fmax    mantissa field of fmax (man_fmax)
+ *   FP8Q_MX_E4M3FN     8      448    0x600000
+ *   FP8Q_MX_E5M2      15    57344    0x600000
+ *   FP8Q_MX_E2M1       2        6    0x400000
+ * The scale byte of a block, in integer arithmetic only:
+ *   m    = the largest of the block's bits(|x|), compared as unsigned integers (NaN and inf patterns are the largest)
+ *   E    = m >> 23, man = m & 0x7fffff
+ *   code = max(E - emax + bump, 0);  0xFF when E == 255 (a NaN or an infinity anywhere in the block); a zero or
+ *          subnormal-only block gives 0
+ *   bump = 0 for FP8Q_MX_FLOOR, the OCP MX v1.0 rule X = 2^(floor(log2 amax) - emax): elements above fmax * X saturate;
+ *          (man > man_fmax) for FP8Q_MX_CEIL: the smallest power of two under which no element saturates
+ *   X    = 2^(code - 127) as float32: code 0 is the subnormal 0x00400000, 0xFF is NaN
+ * Elements:
+ *   q    = clamp(x * 2^(127 - code), -fmax, fmax)   ONE float32 multiplication by an exactly representable power of two.  It
+ *          is exact except where it lands in float32's subnormal range, which is far below every format's smallest
+ *          midpoint: those elements are a zero of x's sign either way
+ *   elem = RNE(q) in the element format, subnormals included; -0 keeps its sign (0x80 in FP8, 0x8 in FP4)
+ *   a 0xFF block stores 0x7F (FP8) / 0x0 (FP4) in every element
+ *   E2M1: the codes 0..7 are the values {0, .5, 1, 1.5, 2, 3, 4, 6}, the sign is bit 3, a tie goes to the even code; two
+ *   elements share a byte, the even-indexed one in the low nibble, so codes holds R * K / 2 bytes and K must be even
+ * decode(elem) = value(elem) * X, ONE float32 multiplication; subnormal products are kept; every element of a 0xFF block
+ * decodes to NaN, as does a NaN element code; a half output rounds the float32 product once (round to nearest even).
+ * quantize(x) = decode(encode(x)) bit for bit, in one launch.  Half inputs are widened exactly; fp8q_mx_quantize_h16's y_type
+ * is FP8Q_DT_F32 or x_type.
+ * scales holds R * ceil(K / 32) bytes in row-major order; encode writes it, decode reads it, quantize keeps it in registers.
+ * K % 32 == 0 with x / y / codes 16-byte aligned takes the vector route (the range is found in the wave, every element is
+ * read once); anything else goes block by block, one lane each, with the same results.
+ * Errors, all reported before the launch: FP8Q_EINVAL for null pointers, empty shapes (R or K <= 0), an fp32 pointer off its
+ * 4-byte / a half pointer off its 2-byte alignment, an odd K with FP8Q_MX_E2M1, an unknown rounding, a type that is not a
+ * half type (y_type: nor FP8Q_DT_F32) or two different half types; FP8Q_EUNSUPPORTED for any other fmt.  One launch per call,
+ * enqueue-only, no workspace.  FP8Q_VERSION is unchanged: the entries are additive.
+ */
+#define FP8Q_MX_E4M3FN 0
+#define FP8Q_MX_E5M2 1
+#define FP8Q_MX_E2M1 2
+#define FP8Q_MX_FLOOR 0
+#define FP8Q_MX_CEIL 1
+int fp8q_mx_encode_f32(const float *x, uint8_t *codes, uint8_t *scales, int64_t R, int64_t K, int fmt, int rounding,
+                       fp8q_stream_t stream);
+int fp8q_mx_encode_h16(const void *x, uint8_t *codes, uint8_t *scales, int x_type, int64_t R, int64_t K, int fmt,
+                       int rounding, fp8q_stream_t stream);
+int fp8q_mx_decode_f32(const uint8_t *codes, const uint8_t *scales, float *y, int64_t R, int64_t K, int fmt,
+                       fp8q_stream_t stream);
+int fp8q_mx_decode_h16(const uint8_t *codes, const uint8_t *scales, void *y, int y_type, int64_t R, int64_t K, int fmt,
+                       fp8q_stream_t stream);
+int fp8q_mx_quantize_f32(const float *x, float *y, int64_t R, int64_t K, int fmt, int rounding, fp8q_stream_t stream);
+int fp8q_mx_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int fmt, int rounding,
+                         fp8q_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
