@@ -49,25 +49,8 @@
 namespace {
 
 // ---------------------------------------------------------------------------------------------
-// what the kernels share: widening a 16-byte word, the narrow side's stores
+// what the kernels share (widen8, store_half8, scalar_of: fp8q_half.h): the store of a lane's 16 one-byte codes
 // ---------------------------------------------------------------------------------------------
-template <class T>
-__device__ __forceinline__ void widen8(const u4v w, float (&e)[8])
-{
-    T::widen2(w.x, e[0], e[1]);
-    T::widen2(w.y, e[2], e[3]);
-    T::widen2(w.z, e[4], e[5]);
-    T::widen2(w.w, e[6], e[7]);
-}
-
-// 8 values, each rounded once to T, as 16 bytes at whatever 2-byte phase y has
-template <class T>
-__device__ __forceinline__ void store_half8(uint16_t *y, const float *e)
-{
-    const u4v2 w = {T::narrow2(e[0], e[1]), T::narrow2(e[2], e[3]), T::narrow2(e[4], e[5]), T::narrow2(e[6], e[7])};
-    *reinterpret_cast<u4v2 *>(y) = w;
-}
-
 // how the 16 one-byte codes of a lane go out (decided on the host from the address of the first group)
 enum { kStore16 = 0, kStore4 = 1, kStore1 = 2 };
 
@@ -89,14 +72,6 @@ __device__ __forceinline__ void store_codes16(uint8_t *p, const uint32_t (&w)[4]
 #pragma unroll
         for (int j = 0; j < 16; ++j) p[j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
     }
-}
-
-// the element in front of the body (tid < head) or behind it (lanes 32 ..) that this lane of block 0 takes, or -1
-__device__ __forceinline__ int64_t scalar_of(int tid, int64_t head, int64_t tail0, int64_t n)
-{
-    if (tid < head) return tid;
-    if (tid >= 32 && tail0 + (tid - 32) < n) return tail0 + (tid - 32);
-    return -1;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -426,15 +401,15 @@ k_h16_int_encode(const uint16_t *__restrict__ x, void *__restrict__ codes, IntAr
     if (W == 1) {
         uint32_t w[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) w[j] = q[4 * j] | (q[4 * j + 1] << 8) | (q[4 * j + 2] << 16) | (q[4 * j + 3] << 24);
+        for (int j = 0; j < 4; ++j) w[j] = pack_codes<1>(q + 4 * j);
         store_codes16(static_cast<uint8_t *>(codes) + c.e0 + off, w, cs);
     } else {
         // 2-byte codes: 2 x 16 bytes at whatever 2-byte phase the codes have
         u4v2 *co = reinterpret_cast<u4v2 *>(static_cast<uint16_t *>(codes) + c.e0 + off);
 #pragma unroll
         for (int k = 0; k < 2; ++k)
-            co[k] = u4v2{q[8 * k] | (q[8 * k + 1] << 16), q[8 * k + 2] | (q[8 * k + 3] << 16), q[8 * k + 4] | (q[8 * k + 5] << 16),
-                         q[8 * k + 6] | (q[8 * k + 7] << 16)};
+            co[k] = u4v2{pack_codes<2>(q + 8 * k), pack_codes<2>(q + 8 * k + 2), pack_codes<2>(q + 8 * k + 4),
+                         pack_codes<2>(q + 8 * k + 6)};
     }
 }
 
@@ -468,16 +443,10 @@ k_h16_int_decode(const void *__restrict__ codes, uint16_t *__restrict__ y, IntAr
     float e[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
-        uint32_t q;
-        if (W == 1) {
-            const uint32_t w[4] = {v[0].x, v[0].y, v[0].z, v[0].w};
-            q = (w[j >> 2] >> (8 * (j & 3))) & 255u;
-        } else {
-            const u4v vv = v[(W - 1) * (j >> 3)];
-            const uint32_t w[4] = {vv.x, vv.y, vv.z, vv.w};
-            q = (w[(j & 7) >> 1] >> (16 * (j & 1))) & 65535u;
-        }
-        e[j] = value_of<W>(q, c.sgn, c.at<PC>(off + j));
+        constexpr int CPW = 4 / W;     // codes per dword, 4 dwords per 16-byte word
+        const u4v vv = v[j / (4 * CPW)];
+        const uint32_t w[4] = {vv.x, vv.y, vv.z, vv.w};
+        e[j] = value_of<W>(code_at<W>(w[(j / CPW) & 3], j % CPW), c.sgn, c.at<PC>(off + j));
     }
     uint16_t *yo = y + c.e0 + off;
     store_half8<T>(yo, e);
@@ -517,18 +486,12 @@ int int_codec_launch(bool encode, const void *in, void *out, int type, int64_t C
 {
     if (!half_type(type)) return FP8Q_EINVAL;
     if (int rc = int_check_x(in, out, C, inner, n_delta)) return rc;
-    if (!delta || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
     IntArgs a = {};
-    if (int rc = make_int_grid(n_bits, a.grid)) return rc;
+    if (int rc = int_fixed_args(a, delta, zero_float, n_delta, signed_flag, n_bits, symmetric, eps)) return rc;
     const int W = n_bits <= 8 ? 1 : 2;
     const uintptr_t phalf = (uintptr_t)(encode ? in : out), pcodes = (uintptr_t)(encode ? out : in);
     if ((phalf & 1) || (pcodes & (uintptr_t)(W - 1))) return FP8Q_EINVAL;
     const bool pc = n_delta > 1;
-    a.a = delta;
-    a.b = zero_float;
-    a.sflag = const_cast<unsigned char *>(signed_flag);   // read only
-    a.symmetric = symmetric != 0;
-    a.eps = eps;
     int_geometry(a, C, inner, pc);
     if (type == FP8Q_DT_F16) int_launch_t<F16>(encode, W, pc, in, out, a, st);
     else int_launch_t<BF16>(encode, W, pc, in, out, a, st);

@@ -280,15 +280,8 @@ int fp8q_int_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, co
                           int symmetric, float eps, fp8q_stream_t stream)
 {
     if (int rc = int_check_x(x, y, C, inner, n_delta)) return rc;
-    if (!delta || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
     IntArgs a = {};
-    if (int rc = make_int_grid(n_bits, a.grid)) return rc;
-    a.a = delta;
-    a.b = zero_float;
-    a.sflag = const_cast<unsigned char *>(signed_flag);   // read only (RANGE == false)
-    a.C = n_delta;
-    a.symmetric = symmetric != 0;
-    a.eps = eps;
+    if (int rc = int_fixed_args(a, delta, zero_float, n_delta, signed_flag, n_bits, symmetric, eps)) return rc;
     return int_quant_launch(false, x, y, C, inner, a, (hipStream_t)stream);
 }
 

@@ -23,7 +23,8 @@
 // Kernels -- k_int_quant's geometry: one aligned 4096-element chunk per block, the channel constants {scale, 1/scale, zp}
 // of the rows overlapping the chunk built once per block in LDS, the channel of an element from the magic division.  The
 // argument block, that prologue (chunk_setup), k_int_level's streaming loop (chunk_walk) and the host side of the launch
-// are fp8q_intq.h's, shared with fp8q_int.hip; encode and decode keep their own group shapes:
+// are fp8q_intq.h's, shared with fp8q_int.hip, as are int_fixed_args() and the code dwords (pack_codes / code_at, also used
+// by fp8q_codec_h16.hip); encode and decode keep their own group shapes:
 //   k_int_encode<W, PC, VEC, NT>  the wide side is the LOAD: a lane owns 16 (W = 1) or 8 (W = 2) consecutive elements,
 //                 issues its four 16-byte loads before any arithmetic and stores the codes as ONE 16-byte word.
 //   k_int_decode<W, PC, VEC, NT>  the wide side is the STORE (the FP8 decoder's mapping): lane <-> 4-element group, one
@@ -33,14 +34,12 @@
 // goes element by element.  One launch per call, no workspace, nothing read back.
 // HBM traffic: encode / decode 5 B per element (6 B with 2-byte codes), to_integer 8 B.
 #include "fp8q_common.h"
+#include "fp8q_half.h"
 #include "fp8q_intq.h"
 
 namespace {
 
-typedef uint32_t vu4 __attribute__((ext_vector_type(4)));
-typedef uint32_t vu2 __attribute__((ext_vector_type(2)));
-
-// a code, and the word of a 4-element group's codes
+// a code, and the word of a 4-element group's codes (u2v / u4v: fp8q_half.h)
 template <int W>
 struct CodeType {
     typedef uint8_t type;
@@ -49,7 +48,7 @@ struct CodeType {
 template <>
 struct CodeType<2> {
     typedef uint16_t type;
-    typedef vu2 word;
+    typedef u2v word;
 };
 
 template <int W, bool PC, bool VEC, bool NT>
@@ -70,8 +69,8 @@ k_int_encode(const void *__restrict__ in, void *__restrict__ codes, IntArgs a)
         constexpr int EPG = 16 / W, LPG = EPG / 4, GPL = kIntChunk / EPG / kBlock;
         const int ngroups = (int)((e1 - e0) / EPG);
         const vf4 *xv = reinterpret_cast<const vf4 *>(x + e0);
-        vu4 *cv = reinterpret_cast<vu4 *>(out + e0);
-        auto pack = [&](const vf4 *v, int off) -> vu4 {
+        u4v *cv = reinterpret_cast<u4v *>(out + e0);
+        auto pack = [&](const vf4 *v, int off) -> u4v {
             uint32_t q[EPG];
 #pragma unroll
             for (int j = 0; j < LPG; ++j) {
@@ -80,15 +79,7 @@ k_int_encode(const void *__restrict__ in, void *__restrict__ codes, IntArgs a)
                 q[4 * j + 2] = code_of(v[j].z, c.at<PC>(off + 4 * j + 2), c.lo, c.hi) & kMask;
                 q[4 * j + 3] = code_of(v[j].w, c.at<PC>(off + 4 * j + 3), c.lo, c.hi) & kMask;
             }
-            uint32_t w[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if constexpr (W == 1)
-                    w[j] = q[4 * j] | (q[4 * j + 1] << 8) | (q[4 * j + 2] << 16) | (q[4 * j + 3] << 24);
-                else
-                    w[j] = q[2 * j] | (q[2 * j + 1] << 16);
-            }
-            return vu4{w[0], w[1], w[2], w[3]};
+            return u4v{pack_codes<W>(q), pack_codes<W>(q + 4 / W), pack_codes<W>(q + 8 / W), pack_codes<W>(q + 12 / W)};
         };
         if (ngroups == kIntChunk / EPG) {
             vf4 v[GPL * LPG];
@@ -133,15 +124,9 @@ k_int_decode(const void *__restrict__ codes, void *__restrict__ out, IntArgs a)
         auto unpack = [&](const word_t w, int off) -> vf4 {
             uint32_t q[4];
             if constexpr (W == 1) {
-                q[0] = w & 255u;
-                q[1] = (w >> 8) & 255u;
-                q[2] = (w >> 16) & 255u;
-                q[3] = w >> 24;
+                q[0] = code_at<1>(w, 0), q[1] = code_at<1>(w, 1), q[2] = code_at<1>(w, 2), q[3] = code_at<1>(w, 3);
             } else {
-                q[0] = w.x & 65535u;
-                q[1] = w.x >> 16;
-                q[2] = w.y & 65535u;
-                q[3] = w.y >> 16;
+                q[0] = code_at<2>(w.x, 0), q[1] = code_at<2>(w.x, 1), q[2] = code_at<2>(w.y, 0), q[3] = code_at<2>(w.y, 1);
             }
             return vf4{value_of<W>(q[0], c.sgn, c.at<PC>(off)), value_of<W>(q[1], c.sgn, c.at<PC>(off + 1)),
                        value_of<W>(q[2], c.sgn, c.at<PC>(off + 2)), value_of<W>(q[3], c.sgn, c.at<PC>(off + 3))};
@@ -183,19 +168,13 @@ int codec_launch(int mode, const void *in, void *out, int64_t C, int64_t inner, 
                  float eps, hipStream_t st)
 {
     if (int rc = int_check_x(in, out, C, inner, n_delta)) return rc;
-    if (!delta || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
     IntArgs a = {};
-    if (int rc = make_int_grid(n_bits, a.grid)) return rc;
+    if (int rc = int_fixed_args(a, delta, zero_float, n_delta, signed_flag, n_bits, symmetric, eps)) return rc;
     const int W = n_bits <= 8 ? 1 : 2;
     const uintptr_t pin = (uintptr_t)in, pout = (uintptr_t)out;
     if (((mode == kDecode ? pout : pin) & 3) || (mode == kLevel && (pout & 3))) return FP8Q_EINVAL;   // fp32 sides
     if (mode != kLevel && ((mode == kEncode ? pout : pin) & (uintptr_t)(W - 1))) return FP8Q_EINVAL;   // codes
     const bool pc = n_delta > 1;
-    a.a = delta;
-    a.b = zero_float;
-    a.sflag = const_cast<unsigned char *>(signed_flag);   // read only
-    a.symmetric = symmetric != 0;
-    a.eps = eps;
     int_geometry(a, C, inner, pc);
     // both sides on their vector word: 16 bytes, or (decode) a group's 4 W bytes of codes
     const bool vec = mode == kDecode ? ((pout & 15) == 0 && (pin & (uintptr_t)(4 * W - 1)) == 0) : ((pin | pout) & 15) == 0;

@@ -28,6 +28,7 @@
 //                 group included -- need no second path.  The output goes out as 16 bytes (half) or 2 x 16 bytes (fp32) per
 //                 group at the alignment y happens to have: y need not share x's phase, and y == x (same type) is safe
 //                 because a lane writes only what it has read.
+// widen8 / store_half8 are fp8q_half.h's, the fixed-range argument block is int_fixed_args() of fp8q_intq.h.
 // The per-channel current_minmax entry runs fp8q_minmax_h16's row scan (fp8q_h16.hip), then the RANGE launch.
 // HBM traffic per element: 4 B (half out) or 6 B (fp32 out); with the min/max scan 2 B more.
 #include "fp8q_common.h"
@@ -66,10 +67,7 @@ __device__ __forceinline__ void chunk_walk_h16(const uint16_t *x, void *y, const
         if (g >= ng) break;
         const int off = h + 8 * g;
         float e[8];
-        T::widen2(v[u].x, e[0], e[1]);
-        T::widen2(v[u].y, e[2], e[3]);
-        T::widen2(v[u].z, e[4], e[5]);
-        T::widen2(v[u].w, e[6], e[7]);
+        widen8<T>(v[u], e);
 #pragma unroll
         for (int j = 0; j < 8; ++j) e[j] = int_one(e[j], c.at<PC>(off + j), c.lo, c.hi);
         if (YF32) {
@@ -77,12 +75,7 @@ __device__ __forceinline__ void chunk_walk_h16(const uint16_t *x, void *y, const
             st16u<NT>(yo, vf4{e[0], e[1], e[2], e[3]});
             st16u<NT>(yo + 4, vf4{e[4], e[5], e[6], e[7]});
         } else {
-            u4v2 *yo = reinterpret_cast<u4v2 *>(reinterpret_cast<uint16_t *>(y) + c.e0 + off);
-            const u4v2 w = {T::narrow2(e[0], e[1]), T::narrow2(e[2], e[3]), T::narrow2(e[4], e[5]), T::narrow2(e[6], e[7])};
-            if (NT)
-                __builtin_nontemporal_store(w, yo);
-            else
-                *yo = w;
+            store_half8<T, NT>(reinterpret_cast<uint16_t *>(y) + c.e0 + off, e);
         }
     }
 }
@@ -152,15 +145,8 @@ int fp8q_int_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_
                           int symmetric, float eps, fp8q_stream_t stream)
 {
     if (int rc = check_xy(x, y, x_type, y_type, C, inner, n_delta)) return rc;
-    if (!delta || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
     IntArgs a = {};
-    if (int rc = make_int_grid(n_bits, a.grid)) return rc;
-    a.a = delta;
-    a.b = zero_float;
-    a.sflag = const_cast<unsigned char *>(signed_flag);   // read only (RANGE == false)
-    a.C = n_delta;
-    a.symmetric = symmetric != 0;
-    a.eps = eps;
+    if (int rc = int_fixed_args(a, delta, zero_float, n_delta, signed_flag, n_bits, symmetric, eps)) return rc;
     return quant_dispatch(false, x, y, x_type, y_type, C, inner, a, (hipStream_t)stream);
 }
 

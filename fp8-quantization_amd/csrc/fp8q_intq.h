@@ -4,7 +4,8 @@
 // element, the code of an element and the value of a code, a row's range from (x_min, x_max), and the geometry of the
 // chunked kernels (k_int_quant, k_inth16_quant, k_int_level, k_int_encode, k_int_decode): one aligned 4096-element chunk
 // per block, its prologue (sign, grid ends, the channel constants in LDS, the channel of an element by magic division),
-// the fp32 -> fp32 streaming loop, and the host side of their launch.  Internal linkage, as fp8q_common.h.
+// the fp32 -> fp32 streaming loop, and the host side of their launch -- int_fixed_args(): the argument block of every
+// fixed-range entry point -- and pack_codes / code_at, the dwords of 1- and 2-byte codes.  Internal linkage, as fp8q_common.h.
 #pragma once
 #include "fp8q_common.h"
 
@@ -94,6 +95,20 @@ __device__ __forceinline__ float value_of(uint32_t code, bool sgn, const float4 
 {
     const int iv = sgn ? (W == 1 ? (int)(int8_t)code : (int)(int16_t)code) : (int)code;
     return k.x * ((float)iv - k.z);
+}
+
+// 4 / W codes of W bytes (each masked to its width) as a dword, the first in the low bits -- and code j of such a dword
+template <int W>
+__device__ __forceinline__ uint32_t pack_codes(const uint32_t *q)
+{
+    if constexpr (W == 1) return q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+    else return q[0] | (q[1] << 16);
+}
+template <int W>
+__device__ __forceinline__ uint32_t code_at(uint32_t w, int j)
+{
+    const uint32_t s = w >> (8 * W * j);
+    return j == 4 / W - 1 ? s : s & (W == 1 ? 255u : 65535u);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -305,6 +320,22 @@ inline int int_check_x(const void *x, const void *y, int64_t C, int64_t inner, i
     if (!x || !y || C <= 0 || inner <= 0 || (n_range != 1 && n_range != C)) return FP8Q_EINVAL;
     if ((n_range > 1 && inner > INT32_MAX) || C > INT64_MAX / inner || cdiv(C * inner, kIntChunk) > (int64_t)UINT32_MAX)
         return FP8Q_EINVAL;
+    return FP8Q_OK;
+}
+
+// the argument block of a fixed-range launch: the range buffers are there, the grid of n_bits, the range as the kernels read
+// it (ReadRange); the sign byte is only read
+inline int int_fixed_args(IntArgs &a, const float *delta, const float *zero_float, int64_t n_delta,
+                          const unsigned char *signed_flag, int n_bits, int symmetric, float eps)
+{
+    if (!delta || (symmetric ? !signed_flag : !zero_float)) return FP8Q_EINVAL;
+    if (int rc = make_int_grid(n_bits, a.grid)) return rc;
+    a.a = delta;
+    a.b = zero_float;
+    a.sflag = const_cast<unsigned char *>(signed_flag);
+    a.C = n_delta;
+    a.symmetric = symmetric != 0;
+    a.eps = eps;
     return FP8Q_OK;
 }
 

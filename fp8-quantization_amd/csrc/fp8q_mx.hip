@@ -45,29 +45,27 @@
 // block read twice by encode and quantize.  A correctness path; no rate is claimed for it.
 // One launch per call, nothing read back, no allocation, no workspace.
 // HBM traffic per element, fast route: FP8 encode 4 + 1 + 1/32 B (2 + 1 + 1/32 from half), FP4 encode 4 + 1/2 + 1/32.
+// Shared with fp8q_ocp.hip through fp8q_io.h: the launch modes, the Io* element policies, Fp8Fmt (the conversion instructions)
+// and io_dispatch(), the (mode, in_type, out_type) ladder that mx_launch ends in.
 #include "fp8q_common.h"
-#include "fp8q_half.h"
 #include "fp8q_io.h"
 
 namespace {
 
-enum { kEncode, kDecode, kQuant };
-
 constexpr int kMxBlock = 32;          // elements under one scale byte
 constexpr int kMxChunk = 4096;        // elements per workgroup: 16 per lane (encode), 4 x 4 per lane (decode, quantize)
 
+// the FP8 formats: Fp8Fmt (fp8q_io.h: fmax, cvt4, value<B>) and what the scale byte needs; E2M1 converts in integer code below
 template <int F>
 struct MxFmt;
 template <>
-struct MxFmt<FP8Q_MX_E4M3FN> {
+struct MxFmt<FP8Q_MX_E4M3FN> : Fp8Fmt<FP8Q_MX_E4M3FN> {
     static constexpr int emax = 8;
-    static constexpr float fmax = 448.0f;
     static constexpr uint32_t man_fmax = 0x600000u;
 };
 template <>
-struct MxFmt<FP8Q_MX_E5M2> {
+struct MxFmt<FP8Q_MX_E5M2> : Fp8Fmt<FP8Q_MX_E5M2> {
     static constexpr int emax = 15;
-    static constexpr float fmax = 57344.0f;
     static constexpr uint32_t man_fmax = 0x600000u;
 };
 template <>
@@ -121,21 +119,6 @@ __device__ __forceinline__ float fp4_value(uint32_t code)
     return __uint_as_float(mag | ((code & 8u) << 28));
 }
 
-// four values (finite, within +-fmax) -> four FP8 codes in a dword, the first in the low byte
-template <int F>
-__device__ __forceinline__ uint32_t fp8_cvt4(float a, float b, float c, float d)
-{
-    int w = 0;
-    if constexpr (F == FP8Q_MX_E4M3FN) {
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-    } else {
-        w = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, w, false);
-        w = __builtin_amdgcn_cvt_pk_bf8_f32(c, d, w, true);
-    }
-    return (uint32_t)w;
-}
-
 // The codes of four elements under the scale byte sc: FP8 a dword, FP4 the low 16 bits (element 0 in the low nibble)
 template <int F>
 __device__ __forceinline__ uint32_t mx_code4(const float *v, uint32_t sc)
@@ -144,7 +127,7 @@ __device__ __forceinline__ uint32_t mx_code4(const float *v, uint32_t sc)
     const float inv = scale_inv(sc);
     const float q0 = mx_q<F>(v[0], inv), q1 = mx_q<F>(v[1], inv), q2 = mx_q<F>(v[2], inv), q3 = mx_q<F>(v[3], inv);
     if constexpr (F == FP8Q_MX_E2M1) return fp4_code(q0) | (fp4_code(q1) << 4) | (fp4_code(q2) << 8) | (fp4_code(q3) << 12);
-    else return fp8_cvt4<F>(q0, q1, q2, q3);
+    else return MxFmt<F>::cvt4(q0, q1, q2, q3);
 }
 
 // value(elem) * X of element B of mx_code4()'s word; a NaN (a NaN code, a NaN scale) is the one quiet NaN
@@ -153,8 +136,7 @@ __device__ __forceinline__ float mx_value_at(uint32_t w, float X)
 {
     float v;
     if constexpr (F == FP8Q_MX_E2M1) v = fp4_value((w >> (4 * B)) & 0xfu);
-    else if constexpr (F == FP8Q_MX_E4M3FN) v = __builtin_amdgcn_cvt_f32_fp8((int)w, B);
-    else v = __builtin_amdgcn_cvt_f32_bf8((int)w, B);
+    else v = MxFmt<F>::template value<B>(w);
     const float y = v * X;
     return (y != y) ? __uint_as_float(0x7fc00000u) : y;
 }
@@ -230,9 +212,9 @@ k_mx(const void *__restrict__ in, void *__restrict__ out, MxArgs a)
         for (int g = 0; g < 4; ++g) w[g] = mx_code4<F>(v + 4 * g, sc);
         if (live) {
             if constexpr (F == FP8Q_MX_E2M1)
-                stv<NT>(reinterpret_cast<vu2 *>(y + (e >> 1)), vu2{w[0] | (w[1] << 16), w[2] | (w[3] << 16)});
+                stv<NT>(reinterpret_cast<u2v *>(y + (e >> 1)), u2v{w[0] | (w[1] << 16), w[2] | (w[3] << 16)});
             else
-                stv<NT>(reinterpret_cast<vu4 *>(y + e), vu4{w[0], w[1], w[2], w[3]});
+                stv<NT>(reinterpret_cast<u4v *>(y + e), u4v{w[0], w[1], w[2], w[3]});
             if (!(tid & 1)) a.scales_out[e >> 5] = (uint8_t)sc;
         }
     } else {
@@ -343,14 +325,6 @@ void launch_io(const void *in, void *out, const MxArgs &a, bool fast, hipStream_
     else hipLaunchKernelGGL((k_mx<MODE, F, IN, OUT, false>), g, b, 0, st, in, out, a);
 }
 
-template <int MODE, class IN, class OUT>
-void launch_fmt(int fmt, const void *in, void *out, const MxArgs &a, bool fast, hipStream_t st)
-{
-    if (fmt == FP8Q_MX_E4M3FN) launch_io<MODE, FP8Q_MX_E4M3FN, IN, OUT>(in, out, a, fast, st);
-    else if (fmt == FP8Q_MX_E5M2) launch_io<MODE, FP8Q_MX_E5M2, IN, OUT>(in, out, a, fast, st);
-    else launch_io<MODE, FP8Q_MX_E2M1, IN, OUT>(in, out, a, fast, st);
-}
-
 // Argument checks (everything is reported before the launch) and the one launch.  in_type / out_type: FP8Q_DT_* of the value
 // side(s), -1 for the side that holds codes.  scales: written by encode, read by decode, unused (null) by quantize.
 int mx_launch(int mode, const void *in, void *out, const uint8_t *scales, int in_type, int out_type, int64_t R, int64_t K,
@@ -360,10 +334,7 @@ int mx_launch(int mode, const void *in, void *out, const uint8_t *scales, int in
     if (fmt != FP8Q_MX_E4M3FN && fmt != FP8Q_MX_E5M2 && fmt != FP8Q_MX_E2M1) return FP8Q_EUNSUPPORTED;
     if (rounding != FP8Q_MX_FLOOR && rounding != FP8Q_MX_CEIL) return FP8Q_EINVAL;
     if (fmt == FP8Q_MX_E2M1 && (K & 1)) return FP8Q_EINVAL;
-    auto misaligned = [](const void *p, int type) {
-        return type < 0 ? false : (((uintptr_t)p) & (uintptr_t)(type == FP8Q_DT_F32 ? 3 : 1)) != 0;
-    };
-    if (misaligned(in, in_type) || misaligned(out, out_type)) return FP8Q_EINVAL;
+    if (value_side_misaligned(in, in_type) || value_side_misaligned(out, out_type)) return FP8Q_EINVAL;
     const int64_t nb = cdiv(K, kMxBlock);
     if (R > INT64_MAX / K || R > INT64_MAX / nb || cdiv(R * nb, kBlock) > (int64_t)INT32_MAX) return FP8Q_EINVAL;
     MxArgs a = {};
@@ -375,22 +346,14 @@ int mx_launch(int mode, const void *in, void *out, const uint8_t *scales, int in
     a.blocks = R * nb;
     a.ceil_rule = rounding == FP8Q_MX_CEIL;
     const bool fast = K % kMxBlock == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
-    const bool f16 = in_type == FP8Q_DT_F16 || out_type == FP8Q_DT_F16;
-    if (mode == kEncode) {
-        if (in_type == FP8Q_DT_F32) launch_fmt<kEncode, IoF32, IoCodes>(fmt, in, out, a, fast, st);
-        else if (f16) launch_fmt<kEncode, IoH16<F16>, IoCodes>(fmt, in, out, a, fast, st);
-        else launch_fmt<kEncode, IoH16<BF16>, IoCodes>(fmt, in, out, a, fast, st);
-    } else if (mode == kDecode) {
-        if (out_type == FP8Q_DT_F32) launch_fmt<kDecode, IoCodes, IoF32>(fmt, in, out, a, fast, st);
-        else if (f16) launch_fmt<kDecode, IoCodes, IoH16<F16>>(fmt, in, out, a, fast, st);
-        else launch_fmt<kDecode, IoCodes, IoH16<BF16>>(fmt, in, out, a, fast, st);
-    } else {
-        if (in_type == FP8Q_DT_F32) launch_fmt<kQuant, IoF32, IoF32>(fmt, in, out, a, fast, st);
-        else if (f16 && out_type == FP8Q_DT_F32) launch_fmt<kQuant, IoH16<F16>, IoF32>(fmt, in, out, a, fast, st);
-        else if (f16) launch_fmt<kQuant, IoH16<F16>, IoH16<F16>>(fmt, in, out, a, fast, st);
-        else if (out_type == FP8Q_DT_F32) launch_fmt<kQuant, IoH16<BF16>, IoF32>(fmt, in, out, a, fast, st);
-        else launch_fmt<kQuant, IoH16<BF16>, IoH16<BF16>>(fmt, in, out, a, fast, st);
-    }
+    io_dispatch(mode, in_type, out_type, [&](auto m, auto ti, auto to) {
+        constexpr int MODE = decltype(m)::value;
+        typedef decltype(ti) IN;
+        typedef decltype(to) OUT;
+        if (fmt == FP8Q_MX_E4M3FN) launch_io<MODE, FP8Q_MX_E4M3FN, IN, OUT>(in, out, a, fast, st);
+        else if (fmt == FP8Q_MX_E5M2) launch_io<MODE, FP8Q_MX_E5M2, IN, OUT>(in, out, a, fast, st);
+        else launch_io<MODE, FP8Q_MX_E2M1, IN, OUT>(in, out, a, fast, st);
+    });
     return launch_rc();
 }
 

@@ -45,53 +45,34 @@
 // (host check); anything else, and the elements behind the last group of the last chunk, go element by element.  NT:
 // nontemporal loads and stores from 64 MiB (kNtBytes).  The block in whose chunk a row starts writes scale_out[row].  One launch per call, nothing read back.
 // HBM traffic per element: encode / decode 5 B (3 B on half tensors), quantize 8 B (4 B half to half).
+// Shared with fp8q_mx.hip through fp8q_io.h: the launch modes, the Io* element policies, Fp8Fmt (the conversion instructions)
+// and io_dispatch(), the (mode, in_type, out_type) ladder that ocp_launch ends in.
 #include "fp8q_common.h"
-#include "fp8q_half.h"
 #include "fp8q_intq.h"
 #include "fp8q_io.h"
 
 namespace {
 
-enum { kEncode, kDecode, kQuant };
-
+// Fp8Fmt (fp8q_io.h: fmax, M, cvt4, value<B>) and the NaN codes, which decode does not leave to the instruction
 template <int F>
 struct OcpFmt;
 template <>
-struct OcpFmt<FP8Q_OCP_E4M3FN> {
-    static constexpr float fmax = 448.0f;
-    static constexpr int M = 3;
+struct OcpFmt<FP8Q_OCP_E4M3FN> : Fp8Fmt<FP8Q_OCP_E4M3FN> {
     static __device__ __forceinline__ bool is_nan(uint32_t code) { return (code & 0x7fu) == 0x7fu; }
 };
 template <>
-struct OcpFmt<FP8Q_OCP_E5M2> {
-    static constexpr float fmax = 57344.0f;
-    static constexpr int M = 2;
+struct OcpFmt<FP8Q_OCP_E5M2> : Fp8Fmt<FP8Q_OCP_E5M2> {
     static __device__ __forceinline__ bool is_nan(uint32_t code) { return (code & 0x7fu) > 0x7cu; }
 };
 
 constexpr float kOcpLo = 1.0f - 0x1p-21f, kOcpHi = 1.0f + 0x1p-21f;   // the interval around x * (1 / scale), see the top
-
-// four values -> four codes in a dword, the first in the low byte; the values are finite and within +-fmax
-template <int F>
-__device__ __forceinline__ uint32_t cvt4(float a, float b, float c, float d)
-{
-    int w = 0;
-    if constexpr (F == FP8Q_OCP_E4M3FN) {
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-    } else {
-        w = __builtin_amdgcn_cvt_pk_bf8_f32(a, b, w, false);
-        w = __builtin_amdgcn_cvt_pk_bf8_f32(c, d, w, true);
-    }
-    return (uint32_t)w;
-}
 
 // the contract's code of one element, by the IEEE division
 template <int F>
 __device__ __forceinline__ uint32_t code_exact(float v, float s)
 {
     const float q = t_clamp(v / s, -OcpFmt<F>::fmax, OcpFmt<F>::fmax);
-    return (q != q) ? 0x7fu : (cvt4<F>(q, 0.0f, 0.0f, 0.0f) & 0xffu);
+    return (q != q) ? 0x7fu : (OcpFmt<F>::cvt4(q, 0.0f, 0.0f, 0.0f) & 0xffu);
 }
 
 // a value's end of the interval, clamped (a NaN does not come out as one: its dword is redone)
@@ -114,8 +95,8 @@ __device__ __forceinline__ uint32_t code4(const float *v, const float4 *k)
         lo[j] = clamp_end<F>(q0, kOcpLo);
         hi[j] = clamp_end<F>(q0, kOcpHi);
     }
-    uint32_t w = cvt4<F>(lo[0], lo[1], lo[2], lo[3]);
-    if (w != cvt4<F>(hi[0], hi[1], hi[2], hi[3]) || nan) {
+    uint32_t w = OcpFmt<F>::cvt4(lo[0], lo[1], lo[2], lo[3]);
+    if (w != OcpFmt<F>::cvt4(hi[0], hi[1], hi[2], hi[3]) || nan) {
         w = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) w |= code_exact<F>(v[j], k[j].x) << (8 * j);
@@ -127,8 +108,8 @@ template <int F>
 __device__ __forceinline__ uint32_t code1(float v, const float4 k)
 {
     const float q0 = v * k.y;
-    const uint32_t w = cvt4<F>(clamp_end<F>(q0, kOcpLo), 0.0f, 0.0f, 0.0f) & 0xffu;
-    if (w != (cvt4<F>(clamp_end<F>(q0, kOcpHi), 0.0f, 0.0f, 0.0f) & 0xffu) || q0 != q0) return code_exact<F>(v, k.x);
+    const uint32_t w = OcpFmt<F>::cvt4(clamp_end<F>(q0, kOcpLo), 0.0f, 0.0f, 0.0f) & 0xffu;
+    if (w != (OcpFmt<F>::cvt4(clamp_end<F>(q0, kOcpHi), 0.0f, 0.0f, 0.0f) & 0xffu) || q0 != q0) return code_exact<F>(v, k.x);
     return w;
 }
 
@@ -137,10 +118,7 @@ template <int F, int B>
 __device__ __forceinline__ float value_at(uint32_t w, float s)
 {
     const uint32_t code = (w >> (8 * B)) & 0xffu;
-    float v;
-    if constexpr (F == FP8Q_OCP_E4M3FN) v = __builtin_amdgcn_cvt_f32_fp8((int)w, B);
-    else v = __builtin_amdgcn_cvt_f32_bf8((int)w, B);
-    const float y = v * s;
+    const float y = OcpFmt<F>::template value<B>(w) * s;
     constexpr int M = OcpFmt<F>::M;
     const uint32_t nan = ((code & 0x80u) << 24) | 0x7fc00000u | ((code & ((1u << M) - 1u)) << (23 - M));
     return OcpFmt<F>::is_nan(code) ? __uint_as_float(nan) : y;
@@ -205,7 +183,7 @@ k_ocp(const void *__restrict__ in, void *__restrict__ out, IntArgs a)
                                      c.at<PC>(off + 4 * g + 3)};
                 w[g] = code4<F>(v + 4 * g, k);
             }
-            stv<NT>(reinterpret_cast<vu4 *>(y + c.e0 + off), vu4{w[0], w[1], w[2], w[3]});
+            stv<NT>(reinterpret_cast<u4v *>(y + c.e0 + off), u4v{w[0], w[1], w[2], w[3]});
         }
         tail = c.e0 + 16 * (int64_t)ng;
     } else if constexpr (VEC) {
@@ -270,14 +248,6 @@ void launch_io(const void *in, void *out, const IntArgs &a, bool pc, hipStream_t
     else FP8Q_INT_LAUNCH(vec, in, out, a, st, k_ocp, MODE, F, IN, OUT, false);
 }
 
-// VT: the side that holds values (x of encode, y of decode; quantize: IN and OUT given)
-template <int MODE, class IN, class OUT>
-void launch_fmt(int fmt, const void *in, void *out, const IntArgs &a, bool pc, hipStream_t st)
-{
-    if (fmt == FP8Q_OCP_E4M3FN) launch_io<MODE, FP8Q_OCP_E4M3FN, IN, OUT>(in, out, a, pc, st);
-    else launch_io<MODE, FP8Q_OCP_E5M2, IN, OUT>(in, out, a, pc, st);
-}
-
 // Argument checks (everything is reported before the launch) and the one launch.  in_type / out_type: FP8Q_DT_* of the value
 // side(s), -1 for the side that holds codes.  range: maxval, or decode's scale.
 int ocp_launch(int mode, const void *in, void *out, int in_type, int out_type, int64_t C, int64_t inner, const float *range,
@@ -286,10 +256,8 @@ int ocp_launch(int mode, const void *in, void *out, int in_type, int out_type, i
     if (int rc = int_check_x(in, out, C, inner, n_range)) return rc;
     if (!range) return FP8Q_EINVAL;
     if (fmt != FP8Q_OCP_E4M3FN && fmt != FP8Q_OCP_E5M2) return FP8Q_EUNSUPPORTED;
-    auto misaligned = [](const void *p, int type) {
-        return type < 0 ? false : (((uintptr_t)p) & (uintptr_t)(type == FP8Q_DT_F32 ? 3 : 1)) != 0;
-    };
-    if (misaligned(in, in_type) || misaligned(out, out_type) || ((uintptr_t)range & 3) || ((uintptr_t)scale_out & 3))
+    if (value_side_misaligned(in, in_type) || value_side_misaligned(out, out_type) || ((uintptr_t)range & 3) ||
+        ((uintptr_t)scale_out & 3))
         return FP8Q_EINVAL;
     const bool pc = n_range > 1;
     IntArgs a = {};
@@ -298,22 +266,13 @@ int ocp_launch(int mode, const void *in, void *out, int in_type, int out_type, i
     a.delta_out = scale_out;
     a.C = n_range;
     int_geometry(a, C, inner, pc);
-    const bool f16 = in_type == FP8Q_DT_F16 || out_type == FP8Q_DT_F16;
-    if (mode == kEncode) {
-        if (in_type == FP8Q_DT_F32) launch_fmt<kEncode, IoF32, IoCodes>(fmt, in, out, a, pc, st);
-        else if (f16) launch_fmt<kEncode, IoH16<F16>, IoCodes>(fmt, in, out, a, pc, st);
-        else launch_fmt<kEncode, IoH16<BF16>, IoCodes>(fmt, in, out, a, pc, st);
-    } else if (mode == kDecode) {
-        if (out_type == FP8Q_DT_F32) launch_fmt<kDecode, IoCodes, IoF32>(fmt, in, out, a, pc, st);
-        else if (f16) launch_fmt<kDecode, IoCodes, IoH16<F16>>(fmt, in, out, a, pc, st);
-        else launch_fmt<kDecode, IoCodes, IoH16<BF16>>(fmt, in, out, a, pc, st);
-    } else {
-        if (in_type == FP8Q_DT_F32) launch_fmt<kQuant, IoF32, IoF32>(fmt, in, out, a, pc, st);
-        else if (f16 && out_type == FP8Q_DT_F32) launch_fmt<kQuant, IoH16<F16>, IoF32>(fmt, in, out, a, pc, st);
-        else if (f16) launch_fmt<kQuant, IoH16<F16>, IoH16<F16>>(fmt, in, out, a, pc, st);
-        else if (out_type == FP8Q_DT_F32) launch_fmt<kQuant, IoH16<BF16>, IoF32>(fmt, in, out, a, pc, st);
-        else launch_fmt<kQuant, IoH16<BF16>, IoH16<BF16>>(fmt, in, out, a, pc, st);
-    }
+    io_dispatch(mode, in_type, out_type, [&](auto m, auto ti, auto to) {
+        constexpr int MODE = decltype(m)::value;
+        typedef decltype(ti) IN;
+        typedef decltype(to) OUT;
+        if (fmt == FP8Q_OCP_E4M3FN) launch_io<MODE, FP8Q_OCP_E4M3FN, IN, OUT>(in, out, a, pc, st);
+        else launch_io<MODE, FP8Q_OCP_E5M2, IN, OUT>(in, out, a, pc, st);
+    });
     return launch_rc();
 }
 

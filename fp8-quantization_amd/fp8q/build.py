@@ -4,7 +4,9 @@ Twenty-one translation units (the quantize / min-max family: long rows, short ro
 multi-tensor plan; MSE grid, fused epilogue, storage codes, the float64 lane, the interval-histogram MSE search,
 uniform INT quantization, the fp16 / bf16 lane, the FP quantizer's backward, the INT quantizers' backward, the INT quantizers' integer codes,
 uniform INT quantization on fp16 / bf16, percentile selection, the storage codes of fp16 / bf16 tensors, the fused epilogue of the INT quantizers, the OCP E4M3FN / E5M2 lane, the block-scaled MX lane) compiled in parallel and
-linked into one library.  In-tree build: the .so is git-ignored but travels to the GPU box with the repo snapshot.
+linked into one library.  HEADERS are what they share; the code lanes' pieces are in fp8q_io.h (launch modes, element policies, the
+FP8 conversion layer, the one I/O dispatcher), fp8q_half.h (the dword vectors, the half lane's helpers) and fp8q_intq.h (the INT
+argument block, code packing).  In-tree build: the .so is git-ignored but travels to the GPU box with the repo snapshot.
 """
 import concurrent.futures
 import os

@@ -150,6 +150,43 @@ def _decode_out_dtype(out, out_dtype):
     return dt
 
 
+def _quantize_out_dtype(x, out, out_dtype):
+    """result dtype of a quantize-style call on the code lanes: float32 for a float32 x (out_dtype, when given, must say so),
+    _half_out_dtype's for a float16 / bfloat16 x"""
+    if x.dtype in _HALF:
+        return _half_out_dtype(x, out, out_dtype)
+    _check_out_dtype(x, out_dtype)
+    return torch.float32
+
+
+def _lane(*dtypes, f32="_f32"):
+    """(suffix of the entry point, the FP8Q_DT_* it takes) for a call whose value side(s) have `dtypes`: the _h16 entry with
+    its type arguments when the first is float16 / bfloat16, else the float32 entry, which takes none"""
+    return ("_h16", tuple(_DT[d] for d in dtypes)) if dtypes[0] in _HALF else (f32, ())
+
+
+def _run(fn, t, *args):
+    """lib().<fn>(*args, stream) on t's device and torch's current stream there; a non-zero status raises"""
+    with _on_device(t):
+        rc = getattr(lib(), fn)(*args, _stream(t))
+    check(rc, fn)
+
+
+def _codes_fmt(codes, fmt, formats, names, hint):
+    """the format of `codes` for a decode: their own dtype when it is one of `formats`, else uint8 codes with fmt= naming it"""
+    if not isinstance(codes, torch.Tensor) or not codes.is_cuda:
+        raise Fp8qError("codes must be a CUDA(HIP) tensor: the FP8 engine has no CPU path")
+    if codes.dtype in formats:
+        if fmt is not None and fmt != codes.dtype:
+            raise Fp8qError(f"codes are {codes.dtype} but fmt is {fmt}")
+        return codes.dtype
+    if codes.dtype != torch.uint8:
+        raise Fp8qError(f"codes must be {names} or uint8, got {codes.dtype}")
+    if fmt is None:
+        raise Fp8qError(f"uint8 codes carry no format: pass fmt={hint}")
+    return fmt
+
+
 def _quantize_h16(x, maxval, mbits, n_bits, sign_bits, out, out_dtype):
     """K1 on float16 / bfloat16 (fp8q_quantize_h16): x widened exactly, the fp32 contract, the result stored as float32
     or rounded once to x.dtype"""
@@ -808,10 +845,7 @@ def _int_codec(fn, x, name, in_dtype, out_dtype, delta, zero_float, signed_flag,
     if xk.numel() == 0:
         return res
     types = () if half is None else (_DT[half],)
-    with _on_device(xk):
-        rc = getattr(lib(), fn)(xk.data_ptr(), y.data_ptr(), *types, C, inner, pd, pz, n, ps, int(n_bits),
-                                int(bool(symmetric)), float(eps), _stream(xk))
-    check(rc, fn)
+    _run(fn, xk, xk.data_ptr(), y.data_ptr(), *types, C, inner, pd, pz, n, ps, int(n_bits), int(bool(symmetric)), float(eps))
     return res
 
 
@@ -1411,18 +1445,11 @@ def encode(x, maxval, mbits, n_bits=8, sign_bits=1, out=None):
     if n_mv != 1 and n_mv != C:
         raise Fp8qError(f"maxval has {n_mv} elements, expected 1 or {C}")
     codes = _out(out, x, torch.uint8)
-    if x.dtype in _HALF:
-        if x.numel() == 0:      # (nothing to launch: fp8q_encode_u8 answers FP8Q_OK here, the _h16 entries refuse empty shapes)
-            return codes
-        with _on_device(x):
-            rc = lib().fp8q_encode_h16(x.data_ptr(), codes.data_ptr(), _DT[x.dtype], C, inner, maxval.data_ptr(), n_mv,
-                                       float(mbits), int(n_bits), int(sign_bits), _stream(x))
-        check(rc, "fp8q_encode_h16")
+    sfx, types = _lane(x.dtype, f32="_u8")
+    if types and x.numel() == 0:      # (nothing to launch: fp8q_encode_u8 answers FP8Q_OK here, the _h16 entries refuse empty shapes)
         return codes
-    with _on_device(x):
-        rc = lib().fp8q_encode_u8(x.data_ptr(), codes.data_ptr(), C, inner, maxval.data_ptr(), n_mv, float(mbits),
-                                  int(n_bits), int(sign_bits), _stream(x))
-    check(rc, "fp8q_encode_u8")
+    _run("fp8q_encode" + sfx, x, x.data_ptr(), codes.data_ptr(), *types, C, inner, maxval.data_ptr(), n_mv, float(mbits),
+         int(n_bits), int(sign_bits))
     return codes
 
 
@@ -1443,18 +1470,11 @@ def decode(codes, maxval, mbits, n_bits=8, sign_bits=1, out=None, out_dtype=None
     if n_mv != 1 and n_mv != C:
         raise Fp8qError(f"maxval has {n_mv} elements, expected 1 or {C}")
     y = _out(out, codes, dt)
-    if dt in _HALF:
-        if codes.numel() == 0:  # (as in encode: the same empty result as the float32 route)
-            return y
-        with _on_device(codes):
-            rc = lib().fp8q_decode_h16(codes.data_ptr(), y.data_ptr(), _DT[dt], C, inner, maxval.data_ptr(), n_mv,
-                                       float(mbits), int(n_bits), int(sign_bits), _stream(codes))
-        check(rc, "fp8q_decode_h16")
+    sfx, types = _lane(dt, f32="_u8")
+    if types and codes.numel() == 0:  # (as in encode: the same empty result as the float32 route)
         return y
-    with _on_device(codes):
-        rc = lib().fp8q_decode_u8(codes.data_ptr(), y.data_ptr(), C, inner, maxval.data_ptr(), n_mv, float(mbits),
-                                  int(n_bits), int(sign_bits), _stream(codes))
-    check(rc, "fp8q_decode_u8")
+    _run("fp8q_decode" + sfx, codes, codes.data_ptr(), y.data_ptr(), *types, C, inner, maxval.data_ptr(), n_mv, float(mbits),
+         int(n_bits), int(sign_bits))
     return y
 
 
@@ -1489,9 +1509,7 @@ def ocp_scale(maxval, fmt, eps=1e-8):
     maxval = maxval.detach().contiguous().view(-1)
     scale = torch.empty_like(maxval)
     if maxval.numel():
-        with _on_device(maxval):
-            rc = lib().fp8q_ocp_scale_f32(maxval.data_ptr(), maxval.numel(), f, float(eps), scale.data_ptr(), _stream(maxval))
-        check(rc, "fp8q_ocp_scale_f32")
+        _run("fp8q_ocp_scale_f32", maxval, maxval.data_ptr(), maxval.numel(), f, float(eps), scale.data_ptr())
     return scale
 
 
@@ -1514,17 +1532,9 @@ def ocp_encode(x, maxval, fmt, eps=1e-8, out=None, want_scale=True):
     scale = torch.empty_like(maxval) if want_scale else None
     if x.numel() == 0:
         return codes.view(fmt), (ocp_scale(maxval, fmt, eps) if want_scale else None)
-    ps = scale.data_ptr() if want_scale else None
-    with _on_device(x):
-        if x.dtype in _HALF:
-            fn = "fp8q_ocp_encode_h16"
-            rc = lib().fp8q_ocp_encode_h16(x.data_ptr(), codes.data_ptr(), _DT[x.dtype], C, inner, maxval.data_ptr(), n, f,
-                                           float(eps), ps, _stream(x))
-        else:
-            fn = "fp8q_ocp_encode_f32"
-            rc = lib().fp8q_ocp_encode_f32(x.data_ptr(), codes.data_ptr(), C, inner, maxval.data_ptr(), n, f, float(eps), ps,
-                                           _stream(x))
-    check(rc, fn)
+    sfx, types = _lane(x.dtype)
+    _run("fp8q_ocp_encode" + sfx, x, x.data_ptr(), codes.data_ptr(), *types, C, inner, maxval.data_ptr(), n, f, float(eps),
+         scale.data_ptr() if want_scale else None)
     return codes.view(fmt), scale
 
 
@@ -1534,16 +1544,7 @@ def ocp_decode(codes, scale, out=None, out_dtype=None, fmt=None):
     [C] CUDA float32 (ocp_encode's).  float32 unless a float16 / bfloat16 `out` or out_dtype asks for a half type (the float32
     product rounded once).  One launch."""
     dt = _decode_out_dtype(out, out_dtype)
-    if not isinstance(codes, torch.Tensor) or not codes.is_cuda:
-        raise Fp8qError("codes must be a CUDA(HIP) tensor: the FP8 engine has no CPU path")
-    if codes.dtype in _OCP_FMT:
-        if fmt is not None and fmt != codes.dtype:
-            raise Fp8qError(f"codes are {codes.dtype} but fmt is {fmt}")
-        fmt = codes.dtype
-    elif codes.dtype != torch.uint8:
-        raise Fp8qError(f"codes must be float8_e4m3fn, float8_e5m2 or uint8, got {codes.dtype}")
-    elif fmt is None:
-        raise Fp8qError("uint8 codes carry no format: pass fmt=torch.float8_e4m3fn or torch.float8_e5m2")
+    fmt = _codes_fmt(codes, fmt, _OCP_FMT, "float8_e4m3fn, float8_e5m2", "torch.float8_e4m3fn or torch.float8_e5m2")
     f = _ocp_fmt(fmt)
     scale = _ocp_range(scale, "scale", codes)
     n = scale.numel()
@@ -1552,15 +1553,8 @@ def ocp_decode(codes, scale, out=None, out_dtype=None, fmt=None):
     y = _out(out, codes, dt)
     if codes.numel() == 0:
         return y
-    with _on_device(codes):
-        if dt in _HALF:
-            fn = "fp8q_ocp_decode_h16"
-            rc = lib().fp8q_ocp_decode_h16(codes.data_ptr(), y.data_ptr(), _DT[dt], C, inner, scale.data_ptr(), n, f,
-                                           _stream(codes))
-        else:
-            fn = "fp8q_ocp_decode_f32"
-            rc = lib().fp8q_ocp_decode_f32(codes.data_ptr(), y.data_ptr(), C, inner, scale.data_ptr(), n, f, _stream(codes))
-    check(rc, fn)
+    sfx, types = _lane(dt)
+    _run("fp8q_ocp_decode" + sfx, codes, codes.data_ptr(), y.data_ptr(), *types, C, inner, scale.data_ptr(), n, f)
     return y
 
 
@@ -1570,11 +1564,7 @@ def ocp_quantize(x, maxval, fmt, eps=1e-8, out=None, out_dtype=None):
     result rounded once)."""
     f = _ocp_fmt(fmt)
     _require(x, "x", _VALUES)
-    if x.dtype in _HALF:
-        dt = _half_out_dtype(x, out, out_dtype)
-    else:
-        _check_out_dtype(x, out_dtype)
-        dt = torch.float32
+    dt = _quantize_out_dtype(x, out, out_dtype)
     maxval = _ocp_range(maxval, "maxval", x)
     n = maxval.numel()
     x = x.contiguous()
@@ -1582,16 +1572,8 @@ def ocp_quantize(x, maxval, fmt, eps=1e-8, out=None, out_dtype=None):
     y = _out(out, x, dt)
     if x.numel() == 0:
         return y
-    with _on_device(x):
-        if x.dtype in _HALF:
-            fn = "fp8q_ocp_quantize_h16"
-            rc = lib().fp8q_ocp_quantize_h16(x.data_ptr(), y.data_ptr(), _DT[x.dtype], _DT[dt], C, inner, maxval.data_ptr(), n,
-                                             f, float(eps), _stream(x))
-        else:
-            fn = "fp8q_ocp_quantize_f32"
-            rc = lib().fp8q_ocp_quantize_f32(x.data_ptr(), y.data_ptr(), C, inner, maxval.data_ptr(), n, f, float(eps),
-                                             _stream(x))
-    check(rc, fn)
+    sfx, types = _lane(x.dtype, dt)
+    _run("fp8q_ocp_quantize" + sfx, x, x.data_ptr(), y.data_ptr(), *types, C, inner, maxval.data_ptr(), n, f, float(eps))
     return y
 
 
@@ -1656,15 +1638,8 @@ def mx_encode(x, fmt, rounding="floor", out=None, scales_out=None):
     codes = _mx_bytes(out, cshape, fmt, "out", x)
     scales = _mx_bytes(scales_out, sshape, MX_SCALE_DTYPE, "scales_out", x)
     if x.numel():
-        with _on_device(x):
-            if x.dtype in _HALF:
-                fn = "fp8q_mx_encode_h16"
-                rc = lib().fp8q_mx_encode_h16(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), _DT[x.dtype], R, K, f, r,
-                                              _stream(x))
-            else:
-                fn = "fp8q_mx_encode_f32"
-                rc = lib().fp8q_mx_encode_f32(x.data_ptr(), codes.data_ptr(), scales.data_ptr(), R, K, f, r, _stream(x))
-        check(rc, fn)
+        sfx, types = _lane(x.dtype)
+        _run("fp8q_mx_encode" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), *types, R, K, f, r)
     return codes.view(fmt).view(cshape), scales.view(MX_SCALE_DTYPE).view(sshape)
 
 
@@ -1674,16 +1649,7 @@ def mx_decode(codes, scales, fmt=None, out_dtype=None, out=None):
     one per block of 32 along the last dimension (mx_encode's).  float32 unless a float16 / bfloat16 `out` or out_dtype asks
     for a half type (the float32 product rounded once).  One launch."""
     dt = _decode_out_dtype(out, out_dtype)
-    if not isinstance(codes, torch.Tensor) or not codes.is_cuda:
-        raise Fp8qError("codes must be a CUDA(HIP) tensor: the FP8 engine has no CPU path")
-    if codes.dtype in _MX_FMT:
-        if fmt is not None and fmt != codes.dtype:
-            raise Fp8qError(f"codes are {codes.dtype} but fmt is {fmt}")
-        fmt = codes.dtype
-    elif codes.dtype != torch.uint8:
-        raise Fp8qError(f"codes must be float8_e4m3fn, float8_e5m2, float4_e2m1fn_x2 or uint8, got {codes.dtype}")
-    elif fmt is None:
-        raise Fp8qError("uint8 codes carry no format: pass fmt=")
+    fmt = _codes_fmt(codes, fmt, _MX_FMT, "float8_e4m3fn, float8_e5m2, float4_e2m1fn_x2", "")
     f = _mx_fmt(fmt)
     _require(scales, "scales", (MX_SCALE_DTYPE, torch.uint8), codes)
     if codes.dim() == 0:
@@ -1704,14 +1670,8 @@ def mx_decode(codes, scales, fmt=None, out_dtype=None, out=None):
         y = out
     if R * K == 0:
         return y
-    with _on_device(codes):
-        if dt in _HALF:
-            fn = "fp8q_mx_decode_h16"
-            rc = lib().fp8q_mx_decode_h16(codes.data_ptr(), scales.data_ptr(), y.data_ptr(), _DT[dt], R, K, f, _stream(codes))
-        else:
-            fn = "fp8q_mx_decode_f32"
-            rc = lib().fp8q_mx_decode_f32(codes.data_ptr(), scales.data_ptr(), y.data_ptr(), R, K, f, _stream(codes))
-    check(rc, fn)
+    sfx, types = _lane(dt)
+    _run("fp8q_mx_decode" + sfx, codes, codes.data_ptr(), scales.data_ptr(), y.data_ptr(), *types, R, K, f)
     return y
 
 
@@ -1721,24 +1681,14 @@ def mx_quantize(x, fmt, rounding="floor", out_dtype=None, out=None):
     or out_dtype=x.dtype ask for x's own dtype (the float32 result rounded once)."""
     f, r = _mx_fmt(fmt), _mx_rounding(rounding)
     _require(x, "x", _VALUES)
-    if x.dtype in _HALF:
-        dt = _half_out_dtype(x, out, out_dtype)
-    else:
-        _check_out_dtype(x, out_dtype)
-        dt = torch.float32
+    dt = _quantize_out_dtype(x, out, out_dtype)
     x = x.detach().contiguous()
     R, K, _, _ = _mx_geometry(x.shape, fmt)
     y = _out(out, x, dt)
     if x.numel() == 0:
         return y
-    with _on_device(x):
-        if x.dtype in _HALF:
-            fn = "fp8q_mx_quantize_h16"
-            rc = lib().fp8q_mx_quantize_h16(x.data_ptr(), y.data_ptr(), _DT[x.dtype], _DT[dt], R, K, f, r, _stream(x))
-        else:
-            fn = "fp8q_mx_quantize_f32"
-            rc = lib().fp8q_mx_quantize_f32(x.data_ptr(), y.data_ptr(), R, K, f, r, _stream(x))
-    check(rc, fn)
+    sfx, types = _lane(x.dtype, dt)
+    _run("fp8q_mx_quantize" + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, f, r)
     return y
 
 

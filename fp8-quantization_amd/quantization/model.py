@@ -209,6 +209,26 @@ def requantize_weights(model):
     return len(mods)
 
 
+def _exportable_weights(model, cls, ready=None):
+    """(name, quantizer, detached weight) of every layer whose weight an export_*_weights() can encode: a hijacker that
+    quantizes its weights by the stock quantize_weights, through a quantizer of class `cls`, the weight on the GPU.  `ready`:
+    the manager must be in fix_ranges and ready(quantizer) hold (None: a quantizer without ranges, any state)."""
+    from .layers import QuantizationHijacker
+    from .manager import Qstates
+    for name, m in model.named_modules():
+        if not isinstance(m, QuantizationHijacker) or not getattr(m, "_qw", False):
+            continue
+        if type(m).quantize_weights is not QuantizationHijacker.quantize_weights:
+            continue
+        mgr = m.weight_quantizer
+        q = getattr(mgr, "quantizer", None)
+        if not isinstance(q, cls) or (ready is not None and (mgr.state != Qstates.fix_ranges or not ready(q))):
+            continue
+        w = m.get_weight_bias()[0].detach()
+        if w.is_cuda:
+            yield name, q, w
+
+
 def export_fp8_weights(model):
     """{layer name: {codes uint8 [like the weight], maxval [1] or [C], mantissa_bits, sign_bits, n_bits}} for every
     layer whose weights go through an FP8 quantizer with fixed ranges: the 1-byte storage form of what the layer
@@ -220,21 +240,8 @@ def export_fp8_weights(model):
 
     import fp8q
     from .fp8 import FPQuantizer
-    from .layers import QuantizationHijacker
-    from .manager import Qstates
     out = {}
-    for name, m in model.named_modules():
-        if not isinstance(m, QuantizationHijacker) or not getattr(m, "_qw", False):
-            continue
-        if type(m).quantize_weights is not QuantizationHijacker.quantize_weights:
-            continue
-        mgr = m.weight_quantizer
-        q = getattr(mgr, "quantizer", None)
-        if not isinstance(q, FPQuantizer) or mgr.state != Qstates.fix_ranges or q.maxval is None:
-            continue
-        w = m.get_weight_bias()[0].detach()
-        if not w.is_cuda:
-            continue
+    for name, q, w in _exportable_weights(model, FPQuantizer, lambda q: q.maxval is not None):
         mv = q.maxval.detach().to(device=w.device, dtype=torch.float32).reshape(-1)
         codes = fp8q.ops.encode(w.contiguous(), mv, float(q.mantissa_bits), int(q.n_bits), int(q.sign_bits))
         out[name] = dict(codes=codes.cpu(), maxval=mv.cpu(), mantissa_bits=float(q.mantissa_bits),
@@ -257,22 +264,9 @@ def export_int_weights(model):
     fp8q.ops.int_encode) with the ranges that turn them back, all as CPU tensors.  decode(codes) == the layer's quantized
     weight bit for bit.  The symmetric sign flag is copied to the host here, once per layer; the kernels never do.
     float16 / bfloat16 weights of quantizers built with keep_dtype=True are encoded as they are (fp8q_int_encode_h16)."""
-    from .layers import QuantizationHijacker
-    from .manager import Qstates
     from .uniform import AsymmetricUniformQuantizer
     out = {}
-    for name, m in model.named_modules():
-        if not isinstance(m, QuantizationHijacker) or not getattr(m, "_qw", False):
-            continue
-        if type(m).quantize_weights is not QuantizationHijacker.quantize_weights:
-            continue
-        mgr = m.weight_quantizer
-        q = getattr(mgr, "quantizer", None)
-        if not isinstance(q, AsymmetricUniformQuantizer) or mgr.state != Qstates.fix_ranges or not q.is_initialized:
-            continue
-        w = m.get_weight_bias()[0].detach()
-        if not w.is_cuda:
-            continue
+    for name, q, w in _exportable_weights(model, AsymmetricUniformQuantizer, lambda q: q.is_initialized):
         codes = q.encode(w.contiguous())
         out[name] = dict(codes=codes.cpu(), delta=q._delta.detach().reshape(-1).cpu(),
                          zero_float=None if q.symmetric else q._zero_float.detach().reshape(-1).cpu(),
@@ -300,22 +294,9 @@ def export_ocp_weights(model):
     fmt the dtype.  decode(codes) * scale == the layer's quantized weight bit for bit.  float16 / bfloat16 weights are encoded
     as they are (fp8q_ocp_encode_h16: the codes of the exactly widened weight)."""
     import fp8q
-    from .layers import QuantizationHijacker
-    from .manager import Qstates
     from .ocp import OCPFP8Quantizer
     out = {}
-    for name, m in model.named_modules():
-        if not isinstance(m, QuantizationHijacker) or not getattr(m, "_qw", False):
-            continue
-        if type(m).quantize_weights is not QuantizationHijacker.quantize_weights:
-            continue
-        mgr = m.weight_quantizer
-        q = getattr(mgr, "quantizer", None)
-        if not isinstance(q, OCPFP8Quantizer) or mgr.state != Qstates.fix_ranges or not q.is_initialized:
-            continue
-        w = m.get_weight_bias()[0].detach()
-        if not w.is_cuda:
-            continue
+    for name, q, w in _exportable_weights(model, OCPFP8Quantizer, lambda q: q.is_initialized):
         codes, scale = fp8q.ops.ocp_encode(w.contiguous(), q._range_for(w), q.fmt, q.eps)
         out[name] = dict(codes=codes.cpu(), scale=scale.cpu(), fmt=q.fmt)
     return out
@@ -336,20 +317,9 @@ def export_mx_weights(model):
     cut as the quantizer cuts the weight (flatten_rows: [shape[0], -1]); shape is the weight's.  An MX quantizer has no range,
     so the manager's state does not matter.  decode(codes, scales) == the layer's quantized weight bit for bit.  float16 /
     bfloat16 weights are encoded as they are (fp8q_mx_encode_h16: the codes of the exactly widened weight)."""
-    from .layers import QuantizationHijacker
     from .mx import MXQuantizer
     out = {}
-    for name, m in model.named_modules():
-        if not isinstance(m, QuantizationHijacker) or not getattr(m, "_qw", False):
-            continue
-        if type(m).quantize_weights is not QuantizationHijacker.quantize_weights:
-            continue
-        q = getattr(m.weight_quantizer, "quantizer", None)
-        if not isinstance(q, MXQuantizer):
-            continue
-        w = m.get_weight_bias()[0].detach()
-        if not w.is_cuda:
-            continue
+    for name, q, w in _exportable_weights(model, MXQuantizer):
         codes, scales = q.encode(w)
         out[name] = dict(codes=codes.cpu(), scales=scales.cpu(), fmt=q.fmt, shape=tuple(w.shape))
     return out

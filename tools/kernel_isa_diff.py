@@ -63,18 +63,28 @@ def parse(path, demangle):
             out.setdefault(m.group(1), [None, None])[1] = normalise(lines[i:j + 1])
             i = j + 1
             continue
-        if ln.endswith(":") and ln[:-1] in names and cur is None:
-            cur = ln[:-1]
+        lab = re.match(r"(\S+):\s*(;.*)?$", ln)      # (the compiler may print "; @name" behind a function's label)
+        if lab and lab.group(1) in names and cur is None:
+            cur = lab.group(1)
             j = i
             while not re.match(r"\.Lfunc_end\d+:", lines[j]):
                 j += 1
             out.setdefault(cur, [None, None])[0] = normalise(lines[i:j])
+            for d in range(i, j):      # (the descriptor block may sit in front of the function's end label)
+                if re.match(r"\s*\.amdhsa_kernel\s+" + re.escape(cur) + r"\s*$", lines[d]):
+                    e = d
+                    while ".end_amdhsa_kernel" not in lines[e]:
+                        e += 1
+                    out[cur][1] = normalise(lines[d:e + 1])
             i = j + 1
             cur = None
             continue
         if "__hip_cuid" not in ln and not ln.lstrip().startswith((".file", ".ident")):
             rest.append(ln)
         i += 1
+    lost = [names[k] for k, v in out.items() if v[0] is None or v[1] is None]
+    if lost:      # a kernel whose body went unrecognised would be compared by its descriptor alone
+        sys.exit("%s: no body or no descriptor found for %d kernels, first %s" % (path, len(lost), lost[0]))
     return {names[k]: tuple(v) for k, v in out.items()}, normalise(rest)
 
 
