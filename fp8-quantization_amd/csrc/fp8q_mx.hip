@@ -1,7 +1,7 @@
 // fp8q_mx.hip -- the microscaling (MX) lane (gfx950 only): blocks of 32 elements along the last dimension under ONE E8M0
-// power-of-two scale byte each, elements in OCP E4M3FN, E5M2 or the 4-bit E2M1 -- the operand form of gfx950's scaled matrix
-// instructions (v_mfma_scale_f32_*_f8f6f4) and of torch.float8_e8m0fnu / torch.float4_e2m1fn_x2.  Nothing here multiplies
-// matrices; the lane makes, reads and fake-quantizes the operands.
+// power-of-two scale byte each, elements in OCP E4M3FN, E5M2, the 6-bit E2M3 / E3M2 or the 4-bit E2M1 -- the operand forms of
+// gfx950's scaled matrix instructions (v_mfma_scale_f32_*_f8f6f4) and of torch.float8_e8m0fnu / torch.float4_e2m1fn_x2 (torch
+// has no 6-bit dtype).  Nothing here multiplies matrices; the lane makes, reads and fake-quantizes the operands.
 //
 // Arithmetic contract (include/fp8q.h states it for callers).  The tensor is [R, K], K contiguous; row r is cut into the
 // blocks [32j, min(32j + 32, K)): the last block of a row may be short, no block crosses a row.
@@ -9,6 +9,9 @@
 //   E4M3FN     8     448    0x600000
 //   E5M2      15   57344    0x600000
 //   E2M1       2       6    0x400000
+//   E2M3       2     7.5    0x700000        s1 e2 m3, bias 1
+//   E3M2       4      28    0x600000        s1 e3 m2, bias 3
+//   (the ids: E4M3FN 0, E5M2 1, E2M1 2, E2M3 4, E3M2 5; id 3 stays unassigned and FP8Q_EUNSUPPORTED like every other number)
 //   m    = the largest bits(|x|) of the block, compared as unsigned integers (so NaN and inf patterns are the largest)
 //   E    = m >> 23, man = m & 0x7fffff
 //   code = max(E - emax + bump, 0)           bump = 0 (floor, the OCP MX v1.0 rule X = 2^(floor(log2 amax) - emax)) or
@@ -19,9 +22,15 @@
 //                                            unless it lands in fp32's subnormal range, far below every format's smallest
 //                                            midpoint, where the element is a zero of x's sign either way
 //   elem = RNE(q) in the element format      subnormals included, -0 keeps its sign (0x80 / 0x8); a 0xFF block stores 0x7F
-//                                            (FP8) / 0x0 (FP4) everywhere
+//                                            (FP8) / 0x0 (FP6, FP4) everywhere
 //   E2M1: the codes 0..7 are {0, .5, 1, 1.5, 2, 3, 4, 6}, the sign in bit 3, a tie goes to the even code; two elements
 //   share a byte, the even-indexed one in the low nibble (K must be even)
+//   FP6: the magnitude code c is the low 5 bits, the sign bit 5, no NaN and no infinity among the 64 codes, a tie goes to the
+//   even code, -0 is 0x20.  E2M3: e = c >> 3, m = c & 7, value m * 0.125 (e == 0) or (1 + m / 8) * 2^(e - 1); E3M2: e = c >> 2,
+//   m = c & 3, value m * 0.0625 (e == 0) or (1 + m / 4) * 2^(e - 3).  The codes of a row are one little-endian bit string,
+//   element i in bits [6i, 6i + 6): four elements are three bytes, b0 = e0 | e1 << 6, b1 = e1 >> 2 | e2 << 4,
+//   b2 = e2 >> 4 | e3 << 2 (K % 4 == 0 is required: no byte is shared between rows, every block starts on a byte); a full
+//   block is 24 bytes, the 6-VGPR operand of the matrix instruction; codes are [R, 3K / 4] bytes
 //   decode(elem) = value(elem) * X           ONE fp32 multiplication, subnormal products kept; every element of a 0xFF block
 //                                            is NaN; a half output rounds that product once
 //   quantize(x)  = decode(encode(x))         the same device functions in one pass
@@ -29,22 +38,35 @@
 // What does the conversions.  FP8: v_cvt_pk_fp8_f32 / v_cvt_pk_bf8_f32 on the clamped q and v_cvt_f32_fp8 / v_cvt_f32_bf8,
 // exactly as fp8q_ocp.hip uses them (RNE, subnormals, -0, E5M2's infinities on decode).  FP4: integer arithmetic -- seven
 // comparisons against the midpoints {.25, .75, 1.25, 1.75, 2.5, 3.5, 5}, `>=` at those whose upper neighbour is the even
-// code -- and the value's bits built from the code.  gfx950's scaled conversions (v_cvt_scalef32_pk_fp4_f32 and kin) are
-// NOT used: nothing has shown yet that they reproduce this contract on subnormal inputs and ties.
+// code -- and the value's bits built from the code.  FP6: one integer routine for both formats, parameterised by the mantissa
+// width M (fp6_code / fp6_value): a normal q is rebiased and rounded on its bits, the carry running into the exponent; a
+// subnormal one is rounded by one fp32 addition of 2^(24 - bias - M), whose unit in the last place is the grid's step; the
+// value is the code's bits read as an fp32 (subnormal where e == 0) times 2^(127 - bias), which is exact.  gfx950's scaled
+// conversions (v_cvt_scalef32_pk_fp4_f32, v_cvt_scalef32_pk32_fp6_f32 and kin) are NOT used: nothing has shown yet that they
+// reproduce this contract on subnormal inputs and ties.
 //
 // Kernels.  k_mx<MODE, F, IN, OUT, NT>, the fast route: K % 32 == 0 and x / y / codes 16-byte aligned.  Then blocks tile the
 // flat tensor, block b covers elements [32b, 32b + 32) and owns scale byte b, and a workgroup takes 4096 consecutive elements.
 //   encode: a lane owns 16 consecutive elements, its 16-byte loads (four of fp32, two of half) issued before any arithmetic;
 //           the two lanes of a block exchange their integer maxima in one DPP step; 16 FP8 codes leave as ONE
-//           16-byte word, 16 FP4 codes as one 8-byte word; the even lane stores the block's scale byte (a plain 1-byte store)
+//           16-byte word, 16 FP4 codes as one 8-byte word, 16 FP6 codes as three dwords at byte 12 * lane of the chunk's
+//           codes (4-byte aligned; a wave writes 768 contiguous bytes); the even lane stores the block's scale byte (a plain
+//           1-byte store)
 //   decode, quantize: lane <-> group of 4 elements, four groups per lane 1024 elements apart, so that every store instruction
 //           of a wave writes whole lines; quantize folds the maxima of a block's 8 lanes in three DPP steps; decode reads the
 //           block's scale byte in each of its 8 lanes (one byte, broadcast by the cache)
+//           FP6 decode keeps that geometry: a group's three code bytes lie at byte 3g, so a lane fetches them from the one
+//           or two aligned dwords that hold them (v_alignbyte_b32; the second dword only where the group crosses into it) and
+//           the value stores stay as they are.  The other candidate -- the encode geometry, a lane of 16 elements with three
+//           aligned dword loads and its own 16-byte value stores -- measured 1.6x (bfloat16) to 4.8x (float32) slower on
+//           [8192, 8192] (profiles/mx6_mb.txt): each of a wave's store instructions then touches 64 lines a quarter each
 // Every element is read exactly once.  NT: nontemporal loads and stores from 64 MiB (kNtBytes), the rule of the INT kernels.
-// k_mx_plain<MODE, F, IN, OUT>, the general route (ragged K, misaligned views): one lane per block, element by element, the
-// block read twice by encode and quantize.  A correctness path; no rate is claimed for it.
+// k_mx_plain<MODE, F, IN, OUT>, the general route (ragged K, misaligned views): one lane per block, element by element (FP4:
+// two elements and a byte, FP6: four elements and three bytes at a time, the code side at any address), the block read twice by
+// encode and quantize.  A correctness path; no rate is claimed for it.
 // One launch per call, nothing read back, no allocation, no workspace.
-// HBM traffic per element, fast route: FP8 encode 4 + 1 + 1/32 B (2 + 1 + 1/32 from half), FP4 encode 4 + 1/2 + 1/32.
+// HBM traffic per element, fast route: FP8 encode 4 + 1 + 1/32 B (2 + 1 + 1/32 from half), FP6 encode 4 + 3/4 + 1/32, FP4
+// encode 4 + 1/2 + 1/32.
 // Shared with fp8q_ocp.hip through fp8q_io.h: the launch modes, the Io* element policies, Fp8Fmt (the conversion instructions)
 // and io_dispatch(), the (mode, in_type, out_type) ladder that mx_launch ends in.
 #include "fp8q_common.h"
@@ -74,6 +96,23 @@ struct MxFmt<FP8Q_MX_E2M1> {
     static constexpr float fmax = 6.0f;
     static constexpr uint32_t man_fmax = 0x400000u;
 };
+// the 6-bit formats: M mantissa bits under 5 - M exponent bits of bias 2^(4 - M) - 1
+template <>
+struct MxFmt<FP8Q_MX_E2M3> {
+    static constexpr int emax = 2;
+    static constexpr float fmax = 7.5f;
+    static constexpr uint32_t man_fmax = 0x700000u;
+    static constexpr int M = 3, bias = 1;
+};
+template <>
+struct MxFmt<FP8Q_MX_E3M2> {
+    static constexpr int emax = 4;
+    static constexpr float fmax = 28.0f;
+    static constexpr uint32_t man_fmax = 0x600000u;
+    static constexpr int M = 2, bias = 3;
+};
+template <int F>
+constexpr bool kFp6 = F == FP8Q_MX_E2M3 || F == FP8Q_MX_E3M2;
 
 __device__ __forceinline__ uint32_t abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
 
@@ -119,15 +158,49 @@ __device__ __forceinline__ float fp4_value(uint32_t code)
     return __uint_as_float(mag | ((code & 8u) << 28));
 }
 
-// The codes of four elements under the scale byte sc: FP8 a dword, FP4 the low 16 bits (element 0 in the low nibble)
+// FP6 code (M mantissa bits, exponent bias BIAS) of a finite q within +-fmax, the sign in bit 5.  A normal q: the exponent
+// field rebiased, the 23 - M dropped mantissa bits rounded to nearest even on the integer, the carry running into the exponent
+// (fmax itself is exact, so nothing passes code 31).  A subnormal q: |q| + 2^(24 - BIAS - M), whose unit in the last place is
+// the grid's step 2^(1 - BIAS - M) -- the one fp32 addition rounds to nearest even and leaves m = 0 .. 2^M in the low bits,
+// 2^M being the code of the smallest normal.
+template <int M, int BIAS>
+__device__ __forceinline__ uint32_t fp6_code(float q)
+{
+    constexpr int sh = 23 - M;
+    constexpr uint32_t one = (uint32_t)(128 - BIAS) << 23;              // bits of 2^(1 - BIAS), the smallest normal
+    constexpr uint32_t magic = (uint32_t)(127 + 24 - BIAS - M) << 23;
+    const uint32_t a = abs_bits(q);
+    const uint32_t t = a - ((uint32_t)(127 - BIAS) << 23);
+    const uint32_t n = (t + ((1u << (sh - 1)) - 1u) + ((t >> sh) & 1u)) >> sh;
+    const uint32_t s = __float_as_uint(__uint_as_float(a) + __uint_as_float(magic)) - magic;
+    return (a >= one ? n : s) | ((__float_as_uint(q) >> 26) & 0x20u);
+}
+
+// the value of an FP6 code: its magnitude bits as an fp32's exponent and top mantissa bits -- a subnormal fp32 where e == 0 --
+// times 2^(127 - BIAS), which is exact
+template <int M, int BIAS>
+__device__ __forceinline__ float fp6_value(uint32_t code)
+{
+    const uint32_t b = ((code & 0x1fu) << (23 - M)) | ((code & 0x20u) << 26);
+    return __uint_as_float(b) * __uint_as_float((uint32_t)(254 - BIAS) << 23);
+}
+
+// The codes of four elements under the scale byte sc: FP8 a dword, FP6 the low 24 bits (element 0 in the low six), FP4 the low
+// 16 bits (element 0 in the low nibble)
 template <int F>
 __device__ __forceinline__ uint32_t mx_code4(const float *v, uint32_t sc)
 {
-    if (sc == 0xffu) return F == FP8Q_MX_E2M1 ? 0u : 0x7f7f7f7fu;
+    if (sc == 0xffu) return (F == FP8Q_MX_E2M1 || kFp6<F>) ? 0u : 0x7f7f7f7fu;
     const float inv = scale_inv(sc);
     const float q0 = mx_q<F>(v[0], inv), q1 = mx_q<F>(v[1], inv), q2 = mx_q<F>(v[2], inv), q3 = mx_q<F>(v[3], inv);
-    if constexpr (F == FP8Q_MX_E2M1) return fp4_code(q0) | (fp4_code(q1) << 4) | (fp4_code(q2) << 8) | (fp4_code(q3) << 12);
-    else return MxFmt<F>::cvt4(q0, q1, q2, q3);
+    if constexpr (F == FP8Q_MX_E2M1) {
+        return fp4_code(q0) | (fp4_code(q1) << 4) | (fp4_code(q2) << 8) | (fp4_code(q3) << 12);
+    } else if constexpr (kFp6<F>) {
+        constexpr int M = MxFmt<F>::M, B = MxFmt<F>::bias;
+        return fp6_code<M, B>(q0) | (fp6_code<M, B>(q1) << 6) | (fp6_code<M, B>(q2) << 12) | (fp6_code<M, B>(q3) << 18);
+    } else {
+        return MxFmt<F>::cvt4(q0, q1, q2, q3);
+    }
 }
 
 // value(elem) * X of element B of mx_code4()'s word; a NaN (a NaN code, a NaN scale) is the one quiet NaN
@@ -136,6 +209,7 @@ __device__ __forceinline__ float mx_value_at(uint32_t w, float X)
 {
     float v;
     if constexpr (F == FP8Q_MX_E2M1) v = fp4_value((w >> (4 * B)) & 0xfu);
+    else if constexpr (kFp6<F>) v = fp6_value<MxFmt<F>::M, MxFmt<F>::bias>(w >> (6 * B));
     else v = MxFmt<F>::template value<B>(w);
     const float y = v * X;
     return (y != y) ? __uint_as_float(0x7fc00000u) : y;
@@ -166,6 +240,19 @@ __device__ __forceinline__ uint32_t umax_xor(uint32_t m)
     constexpr int ctrl = STEP == 1 ? 0xB1 : (STEP == 2 ? 0x4E : 0x141);
     const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)m, ctrl, 0xf, 0xf, false);
     return o > m ? o : m;
+}
+
+// The three code bytes of the FP6 group g (elements 4g .. 4g + 3: byte 3g of `codes`, which is 16-byte aligned) out of the one
+// or two aligned dwords that hold them; the second dword is fetched only where the group crosses into it, so it holds codes too
+template <bool NT>
+__device__ __forceinline__ uint32_t fp6_load3(const uint8_t *codes, int64_t g)
+{
+    const int64_t at = 3 * g;
+    const uint32_t *p = reinterpret_cast<const uint32_t *>(codes) + (at >> 2);
+    const uint32_t r = (uint32_t)at & 3u;
+    const uint32_t lo = ldv<NT>(p);
+    const uint32_t hi = r >= 2u ? ldv<NT>(p + 1) : 0u;
+    return __builtin_amdgcn_alignbyte(hi, lo, r) & 0xffffffu;
 }
 
 struct MxArgs {
@@ -211,10 +298,17 @@ k_mx(const void *__restrict__ in, void *__restrict__ out, MxArgs a)
 #pragma unroll
         for (int g = 0; g < 4; ++g) w[g] = mx_code4<F>(v + 4 * g, sc);
         if (live) {
-            if constexpr (F == FP8Q_MX_E2M1)
+            if constexpr (F == FP8Q_MX_E2M1) {
                 stv<NT>(reinterpret_cast<u2v *>(y + (e >> 1)), u2v{w[0] | (w[1] << 16), w[2] | (w[3] << 16)});
-            else
+            } else if constexpr (kFp6<F>) {
+                // 96 bits at byte 12 * lane of the chunk's codes: 4-byte aligned, dword by dword
+                uint32_t *c = reinterpret_cast<uint32_t *>(y + 3 * (e >> 2));
+                stv<NT>(c, w[0] | (w[1] << 24));
+                stv<NT>(c + 1, (w[1] >> 8) | (w[2] << 16));
+                stv<NT>(c + 2, (w[2] >> 16) | (w[3] << 8));
+            } else {
                 stv<NT>(reinterpret_cast<u4v *>(y + e), u4v{w[0], w[1], w[2], w[3]});
+            }
             if (!(tid & 1)) a.scales_out[e >> 5] = (uint8_t)sc;
         }
     } else {
@@ -242,6 +336,7 @@ k_mx(const void *__restrict__ in, void *__restrict__ out, MxArgs a)
             if (!live) return;
             if constexpr (MODE == kQuant) IN::template load4<NT>(x + e0 + off, v);
             else if constexpr (F == FP8Q_MX_E2M1) w = ldv<NT>(reinterpret_cast<const uint16_t *>(x + ((e0 + off) >> 1)));
+            else if constexpr (kFp6<F>) w = fp6_load3<NT>(x, (e0 + off) >> 2);
             else w = IoCodes::load4<NT>(x + e0 + off);
         };
         if (left == kMxChunk) {
@@ -290,24 +385,31 @@ k_mx_plain(const void *__restrict__ in, void *__restrict__ out, MxArgs a)
         sc = scale_code<F>(m, a.ceil_rule);
         if constexpr (MODE == kEncode) a.scales_out[b] = (uint8_t)sc;
     }
-    // E2M1: K is even, so base and len are: the two elements of a byte lie in one block
-    constexpr int kStep = F == FP8Q_MX_E2M1 ? 2 : 1;
+    // kStep elements are kBytes whole bytes of codes.  E2M1: K is even, FP6: K is a multiple of 4, so base and len are: the
+    // elements of a step lie in one block, and no step shares a byte with another
+    constexpr int kStep = F == FP8Q_MX_E2M1 ? 2 : (kFp6<F> ? 4 : 1);
+    constexpr int kBytes = kFp6<F> ? 3 : 1;
     for (int i = 0; i < len; i += kStep) {
         const int64_t e = base + i;
-        uint32_t w;
+        const int64_t cb = e / kStep * kBytes;
+        uint32_t w = 0u;
         if constexpr (MODE == kDecode) {
-            w = x[F == FP8Q_MX_E2M1 ? e >> 1 : e];
+#pragma unroll
+            for (int k = 0; k < kBytes; ++k) w |= (uint32_t)x[cb + k] << (8 * k);
         } else {
-            float v[4] = {IN::load1(x + e), 0.0f, 0.0f, 0.0f};
-            if constexpr (F == FP8Q_MX_E2M1) v[1] = IN::load1(x + e + 1);
-            w = mx_code4<F>(v, sc) & 0xffu;
+            float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int k = 0; k < kStep; ++k) v[k] = IN::load1(x + e + k);
+            w = mx_code4<F>(v, sc) & ((1u << (8 * kBytes)) - 1u);
         }
         if constexpr (MODE == kEncode) {
-            y[F == FP8Q_MX_E2M1 ? e >> 1 : e] = (uint8_t)w;
+#pragma unroll
+            for (int k = 0; k < kBytes; ++k) y[cb + k] = (uint8_t)(w >> (8 * k));
         } else {
-            const float X = scale_value(sc);
-            OUT::store1(y + e, mx_value_at<F, 0>(w, X));
-            if constexpr (F == FP8Q_MX_E2M1) OUT::store1(y + e + 1, mx_value_at<F, 1>(w, X));
+            float r[4];
+            mx_value4<F>(w, sc, r);
+#pragma unroll
+            for (int k = 0; k < kStep; ++k) OUT::store1(y + e + k, r[k]);
         }
     }
 }
@@ -331,9 +433,10 @@ int mx_launch(int mode, const void *in, void *out, const uint8_t *scales, int in
               int fmt, int rounding, hipStream_t st)
 {
     if (!in || !out || (mode != kQuant && !scales) || R <= 0 || K <= 0) return FP8Q_EINVAL;
-    if (fmt != FP8Q_MX_E4M3FN && fmt != FP8Q_MX_E5M2 && fmt != FP8Q_MX_E2M1) return FP8Q_EUNSUPPORTED;
+    const bool fp6 = fmt == FP8Q_MX_E2M3 || fmt == FP8Q_MX_E3M2;
+    if (fmt != FP8Q_MX_E4M3FN && fmt != FP8Q_MX_E5M2 && fmt != FP8Q_MX_E2M1 && !fp6) return FP8Q_EUNSUPPORTED;
     if (rounding != FP8Q_MX_FLOOR && rounding != FP8Q_MX_CEIL) return FP8Q_EINVAL;
-    if (fmt == FP8Q_MX_E2M1 && (K & 1)) return FP8Q_EINVAL;
+    if ((fmt == FP8Q_MX_E2M1 && (K & 1)) || (fp6 && (K & 3))) return FP8Q_EINVAL;
     if (value_side_misaligned(in, in_type) || value_side_misaligned(out, out_type)) return FP8Q_EINVAL;
     const int64_t nb = cdiv(K, kMxBlock);
     if (R > INT64_MAX / K || R > INT64_MAX / nb || cdiv(R * nb, kBlock) > (int64_t)INT32_MAX) return FP8Q_EINVAL;
@@ -352,6 +455,8 @@ int mx_launch(int mode, const void *in, void *out, const uint8_t *scales, int in
         typedef decltype(to) OUT;
         if (fmt == FP8Q_MX_E4M3FN) launch_io<MODE, FP8Q_MX_E4M3FN, IN, OUT>(in, out, a, fast, st);
         else if (fmt == FP8Q_MX_E5M2) launch_io<MODE, FP8Q_MX_E5M2, IN, OUT>(in, out, a, fast, st);
+        else if (fmt == FP8Q_MX_E2M3) launch_io<MODE, FP8Q_MX_E2M3, IN, OUT>(in, out, a, fast, st);
+        else if (fmt == FP8Q_MX_E3M2) launch_io<MODE, FP8Q_MX_E3M2, IN, OUT>(in, out, a, fast, st);
         else launch_io<MODE, FP8Q_MX_E2M1, IN, OUT>(in, out, a, fast, st);
     });
     return launch_rc();

@@ -1578,16 +1578,23 @@ def ocp_quantize(x, maxval, fmt, eps=1e-8, out=None, out_dtype=None):
 
 
 # ---- microscaling: blocks of 32 under an E8M0 scale byte (csrc/fp8q_mx.hip; the contract is in include/fp8q.h) ----
-_MX_FMT = {torch.float8_e4m3fn: 0, torch.float8_e5m2: 1, torch.float4_e2m1fn_x2: 2}      # FP8Q_MX_* (include/fp8q.h)
+MX_E2M3, MX_E3M2 = "e2m3", "e3m2"      # the 6-bit formats: torch has no dtype for them, so strings name them and codes are uint8
+_MX_FP6 = (MX_E2M3, MX_E3M2)
+_MX_FMT = {torch.float8_e4m3fn: 0, torch.float8_e5m2: 1, torch.float4_e2m1fn_x2: 2, MX_E2M3: 4, MX_E3M2: 5}   # FP8Q_MX_* (include/fp8q.h; 3 is unassigned)
 _MX_ROUNDING = {"floor": 0, "ceil": 1}
 MX_BLOCK = 32
 MX_SCALE_DTYPE = torch.float8_e8m0fnu
 
 
 def _mx_fmt(fmt):
-    if fmt not in _MX_FMT:
-        raise Fp8qError(f"fmt must be torch.float8_e4m3fn, torch.float8_e5m2 or torch.float4_e2m1fn_x2, got {fmt}")
+    if not isinstance(fmt, (torch.dtype, str)) or fmt not in _MX_FMT:
+        raise Fp8qError(f"fmt must be torch.float8_e4m3fn, torch.float8_e5m2, torch.float4_e2m1fn_x2, 'e2m3' or 'e3m2', got {fmt!r}")
     return _MX_FMT[fmt]
+
+
+def _mx_code_dtype(fmt):
+    """the dtype codes of `fmt` are handed out as: the format's own, uint8 for the 6-bit formats"""
+    return torch.uint8 if fmt in _MX_FP6 else fmt
 
 
 def _mx_rounding(rounding):
@@ -1606,7 +1613,9 @@ def _mx_geometry(shape, fmt):
         R *= int(s)
     if fmt == torch.float4_e2m1fn_x2 and K % 2:
         raise Fp8qError(f"two E2M1 elements share a byte: the last dimension must be even, got {K}")
-    kc = K // 2 if fmt == torch.float4_e2m1fn_x2 else K
+    if fmt in _MX_FP6 and K % 4:
+        raise Fp8qError(f"four FP6 elements share three bytes: the last dimension must be a multiple of 4, got {K}")
+    kc = K // 2 if fmt == torch.float4_e2m1fn_x2 else (3 * K // 4 if fmt in _MX_FP6 else K)
     return R, K, lead + (kc,), lead + ((K + MX_BLOCK - 1) // MX_BLOCK,)
 
 
@@ -1627,35 +1636,48 @@ def _mx_bytes(out, shape, dtype, name, like):
 def mx_encode(x, fmt, rounding="floor", out=None, scales_out=None):
     """MX operands of x: (codes, scales).  Blocks of 32 along the last dimension, one E8M0 scale byte each (include/fp8q.h
     states the arithmetic).  fmt: torch.float8_e4m3fn / torch.float8_e5m2 (codes shaped like x) or torch.float4_e2m1fn_x2
-    (codes [..., K / 2], the even-indexed element in the low nibble; K must be even).  scales: torch.float8_e8m0fnu
+    (codes [..., K / 2], the even-indexed element in the low nibble; K must be even) or MX_E2M3 / MX_E3M2, the strings "e2m3" /
+    "e3m2" (torch has no 6-bit dtype: codes are torch.uint8 [..., 3K / 4], four elements in three bytes, element i of a row
+    in bits [6i, 6i + 6) of its little-endian bit string; K must be a multiple of 4).  scales: torch.float8_e8m0fnu
     [..., ceil(K / 32)].  rounding: "floor" (OCP MX v1.0: the largest elements of a block may saturate) or "ceil" (the smallest
     power of two under which none does).  x float32, or float16 / bfloat16 (widened exactly).  `out` / `scales_out`: contiguous
     tensors of the result's dtype or uint8.  One launch; the range is found in the same pass."""
     f, r = _mx_fmt(fmt), _mx_rounding(rounding)
+    if isinstance(x, torch.Tensor):
+        _mx_geometry(x.shape, fmt)      # (argument errors before the device check: they need no GPU to be told)
     _require(x, "x", _VALUES)
     x = x.detach().contiguous()
     R, K, cshape, sshape = _mx_geometry(x.shape, fmt)
-    codes = _mx_bytes(out, cshape, fmt, "out", x)
+    cdt = _mx_code_dtype(fmt)
+    codes = _mx_bytes(out, cshape, cdt, "out", x)
     scales = _mx_bytes(scales_out, sshape, MX_SCALE_DTYPE, "scales_out", x)
     if x.numel():
         sfx, types = _lane(x.dtype)
         _run("fp8q_mx_encode" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), *types, R, K, f, r)
-    return codes.view(fmt).view(cshape), scales.view(MX_SCALE_DTYPE).view(sshape)
+    return codes.view(cdt).view(cshape), scales.view(MX_SCALE_DTYPE).view(sshape)
 
 
 def mx_decode(codes, scales, fmt=None, out_dtype=None, out=None):
     """Values of MX operands: value(elem) * 2^(scale - 127), one float32 multiplication; every element of a 0xFF block is NaN.
-    codes: a CUDA tensor of an MX element dtype, or uint8 with `fmt` naming the format; scales: torch.float8_e8m0fnu or uint8,
+    codes: a CUDA tensor of an MX element dtype, or uint8 with `fmt` naming the format (the only way for "e2m3" / "e3m2", whose
+    values have codes.shape[-1] * 4 / 3 elements in the last dimension); scales: torch.float8_e8m0fnu or uint8,
     one per block of 32 along the last dimension (mx_encode's).  float32 unless a float16 / bfloat16 `out` or out_dtype asks
     for a half type (the float32 product rounded once).  One launch."""
     dt = _decode_out_dtype(out, out_dtype)
+    if isinstance(codes, torch.Tensor) and codes.dtype == torch.uint8:      # (argument errors before the device check)
+        if fmt is None:
+            raise Fp8qError("uint8 codes carry no format: pass fmt=")
+        if fmt in _MX_FP6 and codes.dim() and codes.shape[-1] % 3:
+            raise Fp8qError(f"four FP6 elements share three bytes: the codes' last dimension must be a multiple of 3, "
+                            f"got {codes.shape[-1]}")
     fmt = _codes_fmt(codes, fmt, _MX_FMT, "float8_e4m3fn, float8_e5m2, float4_e2m1fn_x2", "")
     f = _mx_fmt(fmt)
     _require(scales, "scales", (MX_SCALE_DTYPE, torch.uint8), codes)
     if codes.dim() == 0:
         raise Fp8qError("MX blocks run along the last dimension: codes need at least one")
     codes = codes.contiguous().view(torch.uint8)
-    vshape = tuple(codes.shape[:-1]) + (codes.shape[-1] * (2 if fmt == torch.float4_e2m1fn_x2 else 1),)
+    kv = codes.shape[-1] * 4 // 3 if fmt in _MX_FP6 else codes.shape[-1] * (2 if fmt == torch.float4_e2m1fn_x2 else 1)
+    vshape = tuple(codes.shape[:-1]) + (kv,)
     R, K, _, sshape = _mx_geometry(vshape, fmt)
     scales = scales.contiguous().view(torch.uint8)
     if tuple(scales.shape) != sshape:
@@ -1680,6 +1702,8 @@ def mx_quantize(x, fmt, rounding="floor", out_dtype=None, out=None):
     launch, the scales never leaving the registers.  x float32 gives float32; x float16 / bfloat16 gives float32 unless `out`
     or out_dtype=x.dtype ask for x's own dtype (the float32 result rounded once)."""
     f, r = _mx_fmt(fmt), _mx_rounding(rounding)
+    if isinstance(x, torch.Tensor):
+        _mx_geometry(x.shape, fmt)      # (argument errors before the device check, as in mx_encode)
     _require(x, "x", _VALUES)
     dt = _quantize_out_dtype(x, out, out_dtype)
     x = x.detach().contiguous()

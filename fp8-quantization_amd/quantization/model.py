@@ -313,10 +313,13 @@ def decode_ocp_weights(exported, device="cuda", dtype=None):
 def export_mx_weights(model):
     """{layer name: {codes, scales, fmt, shape}} for every layer whose weights go through an MXQuantizer -- the twin of
     export_ocp_weights for the block-scaled formats: codes is a CPU tensor of dtype torch.float8_e4m3fn / torch.float8_e5m2
-    ([..., K]) or torch.float4_e2m1fn_x2 ([..., K / 2]), scales a CPU torch.float8_e8m0fnu tensor [..., ceil(K / 32)], both
+    ([..., K]) or torch.float4_e2m1fn_x2 ([..., K / 2]), or torch.uint8 ([..., 3K / 4]) for the 6-bit formats, whose fmt is the
+    string "e2m3" / "e3m2"; scales a CPU torch.float8_e8m0fnu tensor [..., ceil(K / 32)], both
     cut as the quantizer cuts the weight (flatten_rows: [shape[0], -1]); shape is the weight's.  An MX quantizer has no range,
     so the manager's state does not matter.  decode(codes, scales) == the layer's quantized weight bit for bit.  float16 /
-    bfloat16 weights are encoded as they are (fp8q_mx_encode_h16: the codes of the exactly widened weight)."""
+    bfloat16 weights are encoded as they are (fp8q_mx_encode_h16: the codes of the exactly widened weight).  Rows are never
+    padded: a 6-bit quantizer on a weight whose rows are no multiple of 4 long -- a [64, 3, 7, 7] convolution under
+    flatten_rows has 147 -- raises the geometry error of fp8q.ops.mx_encode (an odd row does under E2M1)."""
     from .mx import MXQuantizer
     out = {}
     for name, q, w in _exportable_weights(model, MXQuantizer):

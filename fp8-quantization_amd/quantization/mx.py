@@ -1,6 +1,7 @@
 """Microscaling (MX) fake-quantizer: blocks of 32 elements under one E8M0 power-of-two scale byte, elements in OCP E4M3FN,
-E5M2 or the 4-bit E2M1 -- the operands of the MI355X's scaled matrix instructions, held by torch.float8_e8m0fnu and
-torch.float4_e2m1fn_x2.
+E5M2, the 6-bit E2M3 / E3M2 or the 4-bit E2M1 -- the operands of the MI355X's scaled matrix instructions, held by
+torch.float8_e8m0fnu and torch.float4_e2m1fn_x2.  torch has no 6-bit dtype: fmt="e2m3" / "e3m2" name those formats, their
+codes are torch.uint8 [..., 3K / 4] (four elements in three bytes), and the row length K must be a multiple of 4.
 
     forward(x) = decode(encode(x))      on the kernels of csrc/fp8q_mx.hip (include/fp8q.h states the arithmetic)
 
@@ -20,8 +21,9 @@ from fp8q import ops as _ops
 from .fp8 import QuantizerBase
 
 _HALF = (torch.float16, torch.bfloat16)
-_BITS = {torch.float8_e4m3fn: 8, torch.float8_e5m2: 8, torch.float4_e2m1fn_x2: 4}
-_NAME = {torch.float8_e4m3fn: "E4M3FN", torch.float8_e5m2: "E5M2", torch.float4_e2m1fn_x2: "E2M1"}
+_BITS = {torch.float8_e4m3fn: 8, torch.float8_e5m2: 8, torch.float4_e2m1fn_x2: 4, _ops.MX_E2M3: 6, _ops.MX_E3M2: 6}
+_NAME = {torch.float8_e4m3fn: "E4M3FN", torch.float8_e5m2: "E5M2", torch.float4_e2m1fn_x2: "E2M1", _ops.MX_E2M3: "E2M3",
+         _ops.MX_E3M2: "E3M2"}
 
 
 class MXQuantizer(QuantizerBase):
@@ -29,8 +31,9 @@ class MXQuantizer(QuantizerBase):
 
     def __init__(self, n_bits=None, fmt=torch.float8_e4m3fn, rounding="floor", keep_dtype=False, flatten_rows=False,
                  per_channel=False, scale_domain=None, **kwargs):
-        if fmt not in _BITS:
-            raise ValueError(f"fmt must be torch.float8_e4m3fn, torch.float8_e5m2 or torch.float4_e2m1fn_x2, got {fmt}")
+        if not isinstance(fmt, (torch.dtype, str)) or fmt not in _BITS:
+            raise ValueError(f"fmt must be torch.float8_e4m3fn, torch.float8_e5m2, torch.float4_e2m1fn_x2, 'e2m3' or 'e3m2', "
+                             f"got {fmt!r}")
         if n_bits is not None and n_bits != _BITS[fmt]:
             raise ValueError(f"{_NAME[fmt]} elements have {_BITS[fmt]} bits, got n_bits={n_bits}")
         if rounding not in ("floor", "ceil"):
@@ -78,8 +81,9 @@ class MXQuantizer(QuantizerBase):
         return y.view(x_float.shape)
 
     def encode(self, x_float):
-        """(codes, scales) of forward(x): codes of dtype `fmt` ([..., K] for FP8, [..., K / 2] for E2M1), scales
-        torch.float8_e8m0fnu [..., ceil(K / 32)]; with flatten_rows, of the [shape[0], -1] view."""
+        """(codes, scales) of forward(x): codes of dtype `fmt` ([..., K] for FP8, [..., K / 2] for E2M1; torch.uint8
+        [..., 3K / 4] for the 6-bit formats), scales torch.float8_e8m0fnu [..., ceil(K / 32)]; with flatten_rows, of the
+        [shape[0], -1] view."""
         return _ops.mx_encode(self._rows(x_float.detach()), self.fmt, self.rounding)
 
     def decode(self, codes, scales, out_dtype=None):

@@ -834,9 +834,9 @@ int fp8q_ocp_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_
                           int64_t n_maxval, int fmt, float eps, fp8q_stream_t stream);
 int fp8q_ocp_scale_f32(const float *maxval, int64_t n, int fmt, float eps, float *scale, fp8q_stream_t stream);
 
-/* ---- microscaling (MX): blocks of 32 under an E8M0 scale byte, elements in E4M3FN / E5M2 / E2M1 (csrc/fp8q_mx.hip) ---------
- * The operand form of gfx950's scaled matrix instructions (v_mfma_scale_f32_*_f8f6f4), carried by torch.float8_e8m0fnu and
- * torch.float4_e2m1fn_x2.  These entries make, read and fake-quantize such operands; nothing here performs the multiplication,
+/* ---- microscaling (MX): blocks of 32 under an E8M0 scale byte, elements in E4M3FN / E5M2 / E2M3 / E3M2 / E2M1 ----------------
+ * (csrc/fp8q_mx.hip)  The operand forms of gfx950's scaled matrix instructions (v_mfma_scale_f32_*_f8f6f4), carried by
+ * torch.float8_e8m0fnu and torch.float4_e2m1fn_x2 (the 6-bit formats have no torch dtype: plain bytes).  These entries make, read and fake-quantize such operands; nothing here performs the multiplication,
  * and the scale bytes are in plain [R, ceil(K / 32)] order, not in any library's pre-swizzled layout.
  * Arithmetic contract.  The tensor is [R, K], K contiguous.  Row r is cut into the blocks [32j, min(32j + 32, K)): the last
  * block of a row may be short, and no block crosses a row.
@@ -844,6 +844,8 @@ int fp8q_ocp_scale_f32(const float *maxval, int64_t n, int fmt, float eps, float
  *   FP8Q_MX_E4M3FN     8      448    0x600000
  *   FP8Q_MX_E5M2      15    57344    0x600000
  *   FP8Q_MX_E2M1       2        6    0x400000
+ *   FP8Q_MX_E2M3       2      7.5    0x700000        s1 e2 m3, bias 1
+ *   FP8Q_MX_E3M2       4       28    0x600000        s1 e3 m2, bias 3
  * The scale byte of a block, in integer arithmetic only:
  *   m    = the largest of the block's bits(|x|), compared as unsigned integers (NaN and inf patterns are the largest)
  *   E    = m >> 23, man = m & 0x7fffff
@@ -856,10 +858,18 @@ int fp8q_ocp_scale_f32(const float *maxval, int64_t n, int fmt, float eps, float
  *   q    = clamp(x * 2^(127 - code), -fmax, fmax)   ONE float32 multiplication by an exactly representable power of two.  It
  *          is exact except where it lands in float32's subnormal range, which is far below every format's smallest
  *          midpoint: those elements are a zero of x's sign either way
- *   elem = RNE(q) in the element format, subnormals included; -0 keeps its sign (0x80 in FP8, 0x8 in FP4)
- *   a 0xFF block stores 0x7F (FP8) / 0x0 (FP4) in every element
+ *   elem = RNE(q) in the element format, subnormals included; -0 keeps its sign (0x80 in FP8, 0x20 in FP6, 0x8 in FP4)
+ *   a 0xFF block stores 0x7F (FP8) / 0x0 (FP6, FP4) in every element
  *   E2M1: the codes 0..7 are the values {0, .5, 1, 1.5, 2, 3, 4, 6}, the sign is bit 3, a tie goes to the even code; two
  *   elements share a byte, the even-indexed one in the low nibble, so codes holds R * K / 2 bytes and K must be even
+ *   E2M3, E3M2 (FP6): the magnitude code c is the low 5 bits and the sign is bit 5; there is no NaN and no infinity among
+ *   the 64 codes; a tie goes to the even code
+ *     E2M3: e = c >> 3, m = c & 7; the value is m * 0.125 for e == 0, else (1 + m / 8) * 2^(e - 1)
+ *     E3M2: e = c >> 2, m = c & 3; the value is m * 0.0625 for e == 0, else (1 + m / 4) * 2^(e - 3)
+ *   The FP6 codes of a row are one little-endian bit string, element i in bits [6i, 6i + 6): four elements are three bytes,
+ *   b0 = e0 | e1 << 6, b1 = e1 >> 2 | e2 << 4, b2 = e2 >> 4 | e3 << 2.  K must be a multiple of 4 (the counterpart of E2M1's
+ *   even K): then no byte is shared between rows and every block, ragged or not, starts on a byte.  codes holds R * 3K / 4
+ *   bytes; a full block is 24 bytes, the 6-VGPR operand of the matrix instruction
  * decode(elem) = value(elem) * X, ONE float32 multiplication; subnormal products are kept; every element of a 0xFF block
  * decodes to NaN, as does a NaN element code; a half output rounds the float32 product once (round to nearest even).
  * quantize(x) = decode(encode(x)) bit for bit, in one launch.  Half inputs are widened exactly; fp8q_mx_quantize_h16's y_type
@@ -868,13 +878,16 @@ int fp8q_ocp_scale_f32(const float *maxval, int64_t n, int fmt, float eps, float
  * K % 32 == 0 with x / y / codes 16-byte aligned takes the vector route (the range is found in the wave, every element is
  * read once); anything else goes block by block, one lane each, with the same results.
  * Errors, all reported before the launch: FP8Q_EINVAL for null pointers, empty shapes (R or K <= 0), an fp32 pointer off its
- * 4-byte / a half pointer off its 2-byte alignment, an odd K with FP8Q_MX_E2M1, an unknown rounding, a type that is not a
- * half type (y_type: nor FP8Q_DT_F32) or two different half types; FP8Q_EUNSUPPORTED for any other fmt.  One launch per call,
- * enqueue-only, no workspace.  FP8Q_VERSION is unchanged: the entries are additive.
+ * 4-byte / a half pointer off its 2-byte alignment, an odd K with FP8Q_MX_E2M1, a K that is no multiple of 4 with
+ * FP8Q_MX_E2M3 / FP8Q_MX_E3M2, an unknown rounding, a type that is not a half type (y_type: nor FP8Q_DT_F32) or two different
+ * half types; FP8Q_EUNSUPPORTED for any other fmt -- the id 3 included, which stays unassigned.  One launch per call,
+ * enqueue-only, no workspace.  FP8Q_VERSION is unchanged: the entries, and the two FP6 ids they take, are additive.
  */
 #define FP8Q_MX_E4M3FN 0
 #define FP8Q_MX_E5M2 1
 #define FP8Q_MX_E2M1 2
+#define FP8Q_MX_E2M3 4
+#define FP8Q_MX_E3M2 5
 #define FP8Q_MX_FLOOR 0
 #define FP8Q_MX_CEIL 1
 int fp8q_mx_encode_f32(const float *x, uint8_t *codes, uint8_t *scales, int64_t R, int64_t K, int fmt, int rounding,

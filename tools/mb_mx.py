@@ -5,9 +5,11 @@
   ocp_encode / ocp_decode / ocp_quantize       fp8q_ocp_*, E4M3FN, one scale per tensor                      the yardsticks
   minmax + ocp_encode                          what a user composes today for dynamic scaling: two passes over x
   mx_encode / mx_decode / mx_quantize          fp8q_mx_*, E4M3FN and E2M1, floor; the range found in the same pass
+  the same three for e2m3 / e3m2               the 6-bit formats, four codes in three bytes; their yardstick is the MXFP8 row
+                                               of the same call on the same tensor (MXFP6 moves fewer bytes than MXFP8)
 
 Algorithmic bytes per element (v = 4 for float32, 2 for bfloat16): FP8 encode / decode v + 1 (+ 1/32 with block scales),
-FP4 encode / decode v + 1/2 + 1/32, quantize 2v, minmax + encode 2v + 1.  The aim of an MX kernel is its OCP twin's time
+FP6 encode / decode v + 3/4 + 1/32, FP4 encode / decode v + 1/2 + 1/32, quantize 2v, minmax + encode 2v + 1.  The aim of an MX kernel is its OCP twin's time
 scaled by the ratio of their bytes, which the last column states next to the measured ratio.
 
 The candidates are interleaved: three rounds, each timing every candidate once as the time per call of `reps` back-to-back
@@ -30,6 +32,7 @@ import torch  # noqa: E402
 SHAPES = [(8192, 8192), (4096, 4096)]
 ROUNDS = 3
 PEAK = 8e12
+FP6 = ("e2m3", "e3m2")
 
 
 def _per_call(fn, reps):
@@ -70,6 +73,10 @@ def main():
             y = torch.empty_like(x)
             c8 = torch.empty(shape, dtype=torch.uint8, device="cuda")
             c4 = torch.empty((shape[0], shape[1] // 2), dtype=torch.uint8, device="cuda")
+            c6 = {f: torch.empty((shape[0], 3 * shape[1] // 4), dtype=torch.uint8, device="cuda") for f in FP6}
+            s6 = {f: torch.empty((shape[0], shape[1] // 32), dtype=torch.uint8, device="cuda") for f in FP6}
+            for f in FP6:
+                ops.mx_encode(x, f, out=c6[f], scales_out=s6[f])
             sc = torch.empty((shape[0], shape[1] // 32), dtype=torch.uint8, device="cuda")
             ops.mx_encode(x, e4, out=c8, scales_out=sc)            # decode's inputs are real operands
             ops.mx_encode(x, e2, out=c4, scales_out=sc)
@@ -91,8 +98,13 @@ def main():
                      ("mx_encode e2m1", v + 0.5 + b32, "ocp_encode e4m3fn", lambda: ops.mx_encode(x, e2, out=c4, scales_out=sc)),
                      ("mx_decode e2m1", v + 0.5 + b32, "ocp_decode e4m3fn", lambda: ops.mx_decode(c4, sc, fmt=e2, out=y)),
                      ("mx_quantize e2m1", 2 * v, "ocp_quantize e4m3fn", lambda: ops.mx_quantize(x, e2, out=y))]
+            for f in FP6:
+                cands += [(f"mx_encode {f}", v + 0.75 + b32, "mx_encode e4m3fn",
+                           lambda f=f: ops.mx_encode(x, f, out=c6[f], scales_out=s6[f])),
+                          (f"mx_decode {f}", v + 0.75 + b32, "mx_decode e4m3fn", lambda f=f: ops.mx_decode(c6[f], s6[f], fmt=f, out=y)),
+                          (f"mx_quantize {f}", 2 * v, "mx_quantize e4m3fn", lambda f=f: ops.mx_quantize(x, f, out=y))]
             # the order of the timed loop: decode candidates read what the encode candidates of their own format wrote
-            order = [0, 1, 2, 3, 7, 8, 9, 4, 5, 6]
+            order = [0, 1, 2, 3, 7, 8, 9, 4, 5, 6] + list(range(10, len(cands)))
             times = {name: [] for name, _, _, _ in cands}
             for _ in range(ROUNDS):
                 for i in order:
@@ -106,10 +118,10 @@ def main():
                 rounds = " ".join(f"{u * 1e6:8.1f}" for u in times[name])
                 rate = b * n / t
                 extra = f"   {t / med[twin]:5.3f} x {twin} (bytes {b / nbytes[twin]:5.3f})" if twin else ""
-                say(f"  {name:20s} rounds {rounds} us  median {t * 1e6:8.1f} us  {rate / 1e12:6.3f} TB/s  {rate / PEAK:5.3f} of peak{extra}")
+                say(f"  {name:26s} rounds {rounds} us  median {t * 1e6:8.1f} us  {rate / 1e12:6.3f} TB/s  {rate / PEAK:5.3f} of peak{extra}")
             spread = max(max(times[k]) / min(times[k]) for k, _, twin, _ in cands if twin is None)
             say(f"  round-to-round spread of the yardsticks (max / min): {spread:5.3f}")
-            del x, y, c8, c4, sc, s8
+            del x, y, c8, c4, sc, s8, c6, s6
             torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
