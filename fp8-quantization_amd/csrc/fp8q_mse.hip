@@ -787,6 +787,7 @@ size_t fp8q_mse_hist_workspace_bytes(int64_t n, int64_t n_pairs);
 bool fp8q_mse_hist_supported(const QFmt *fmts, int n_m, int n_bits);
 int fp8q_mse_hist_launch(const float *x, int64_t n, const float *grid, int64_t n_cand, const QFmt *fmts, int n_m, float *mses,
                          void *ws, size_t ws_bytes, hipStream_t st, int brute, int overwrite, const SelOne *sel);
+int fp8q_mse_hist_plan(int64_t n, int64_t n_cand, const QFmt *fmts, int n_m, fp8q_mse_route_info *out);
 // (fp8q_quant.hip) K1 of a per-tensor quantizer with the winner selection in its prologue
 int fp8q_quantize_select_f32(const float *x, float *y, int64_t n, const float *mses, const float *grid, int n_m, int n_cand,
                              const SelOne *so, int n_bits, int sign_bits, hipStream_t st);
@@ -922,6 +923,24 @@ static RowGeo mse_row_geo(int64_t C, int64_t inner, int64_t n_cand, int n_m)
     return g;
 }
 
+// The kernel a call runs and the launch that finishes its table: decided here for mse_grid_impl AND for fp8q_mse_route
+// (include/fp8q.h), so the query cannot drift from the launcher.  `x_aligned`: x is 4-byte aligned (k_mse_row reads words).
+enum { kRouteGrid = 0, kRouteRow = 1, kRouteHist = 2 };
+enum { kFinishNone = 0, kFinishTile = 1, kFinishWave = 2 };
+
+static int mse_route_kernel(int64_t C, int64_t inner, int64_t n_cand, const QFmt *fmts, int n_m, int n_bits, bool x_aligned)
+{
+    if (mse_use_hist_shape(C, inner, n_cand, n_m) && fp8q_mse_hist_supported(fmts, n_m, n_bits)) return kRouteHist;
+    return mse_use_row(C, inner) && x_aligned ? kRouteRow : kRouteGrid;
+}
+
+// k_mse_grid with one split per row writes the table itself; few partial sums per row: k_mse_final_tile, else k_mse_final
+static int mse_route_finish(int kernel, int64_t C, int64_t nsplit)
+{
+    if (kernel == kRouteHist || (kernel == kRouteGrid && nsplit == 1)) return kFinishNone;
+    return nsplit <= 32 && cdiv(C, kFinTC) <= 65535 ? kFinishTile : kFinishWave;
+}
+
 size_t fp8q_mse_workspace_bytes(int64_t C, int64_t inner, int64_t n_cand, int n_m)
 {
     if (C <= 0 || inner <= 0 || n_cand <= 0 || n_m <= 0) return 16;
@@ -976,13 +995,13 @@ static int mse_grid_impl(const float *x, int64_t C, int64_t inner, const float *
     a.overwrite = overwrite;
     a.first_min = a.first_max = a.first_absmax = a.first_grid = nullptr;
     hipStream_t st = (hipStream_t)stream;
-    if (mse_use_hist_shape(C, inner, n_cand, n_m) && fp8q_mse_hist_supported(a.fmt, n_m, n_bits))
-    {
+    const int kernel = mse_route_kernel(C, inner, n_cand, a.fmt, n_m, n_bits, ((uintptr_t)x & 3) == 0);
+    if (kernel == kRouteHist) {
         if (sel_done) *sel_done = so.enabled;
         return fp8q_mse_hist_launch(x, inner, grid, n_cand, a.fmt, n_m, mses, ws, ws_bytes, st, mse_hist_mode() == 2, overwrite, &so);
     }
     int64_t nsplit = a.nsplit;
-    if (mse_use_row(C, inner) && ((uintptr_t)x & 3) == 0) {
+    if (kernel == kRouteRow) {
         const RowGeo g = mse_row_geo(C, inner, n_cand, n_m);
         nsplit = g.nblk;
         hipLaunchKernelGGL(k_mse_row, dim3((unsigned)g.nblk, (unsigned)g.ngroup, (unsigned)C), dim3(64), 0, st, x, grid,
@@ -1004,11 +1023,12 @@ static int mse_grid_impl(const float *x, int64_t C, int64_t inner, const float *
         }
         hipLaunchKernelGGL(k_mse_grid, dim3((unsigned)a.nsplit, (unsigned)(n_m * a.cgroups), (unsigned)C),
                            dim3(kMseBlock), shmem, st, x, grid, (double *)ws, a, mses, 1.0 / (double)inner);
-        if (a.nsplit == 1) return launch_rc();
     }
+    const int finish = mse_route_finish(kernel, C, nsplit);
+    if (finish == kFinishNone) return launch_rc();
     if (int rc = launch_rc()) return rc;
     const int64_t rows = C * n_m * n_cand;
-    if (nsplit <= 32 && cdiv(C, kFinTC) <= 65535)
+    if (finish == kFinishTile)
         hipLaunchKernelGGL(k_mse_final_tile, dim3((unsigned)cdiv(n_m * n_cand, kFinTM), (unsigned)cdiv(C, kFinTC)), dim3(kBlock), 0, st,
                            (const double *)ws, mses, C, (int64_t)n_m * n_cand, (int)nsplit, 1.0 / (double)inner, overwrite, grid, n_m,
                            (int)n_cand, so);
@@ -1024,6 +1044,30 @@ int fp8q_mse_grid_f32(const float *x, int64_t C, int64_t inner, const float *gri
                       void *ws, size_t ws_bytes, fp8q_stream_t stream)
 {
     return mse_grid_impl(x, C, inner, grid, n_cand, mbits_host, n_m, n_bits, sign_bits, mses, ws, ws_bytes, stream, 0);
+}
+
+// What mse_grid_impl would launch for this call (x 4-byte aligned): host arithmetic only -- the argument checks in the
+// launcher's order, then the launcher's own route functions.
+int fp8q_mse_route(int64_t C, int64_t inner, int64_t n_cand, const float *mbits_host, int n_m, int n_bits, int sign_bits,
+                   fp8q_mse_route_info *out)
+{
+    if (!mbits_host || !out || C <= 0 || inner <= 0 || n_cand <= 0 || n_m <= 0 || n_m > kMseMaxM || n_cand > (1 << 20))
+        return FP8Q_EINVAL;
+    if (C > 65535) return FP8Q_ETOOMANY;
+    QFmt fmt[kMseMaxM];
+    for (int m = 0; m < n_m; ++m)
+        if (int rc = make_fmt(mbits_host[m], n_bits, sign_bits, &fmt[m])) return rc;
+    fp8q_mse_route_info r;
+    memset(&r, 0, sizeof(r));
+    r.kernel = mse_route_kernel(C, inner, n_cand, fmt, n_m, n_bits, true);
+    if (r.kernel == kRouteHist) {
+        if (int rc = fp8q_mse_hist_plan(inner, n_cand, fmt, n_m, &r)) return rc;
+    } else {
+        r.nsplit = r.kernel == kRouteRow ? mse_row_geo(C, inner, n_cand, n_m).nblk : mse_nsplit(C, inner, n_cand, n_m);
+        r.finish = mse_route_finish(r.kernel, C, r.nsplit);
+    }
+    *out = r;
+    return FP8Q_OK;
 }
 
 size_t fp8q_mse_calibrate_workspace_bytes(int64_t C, int64_t inner, int64_t n_cand, int n_m, size_t *minmax_bytes, size_t *select_bytes)

@@ -728,7 +728,8 @@ __device__ __forceinline__ uint32_t subbin_of(uint32_t v) { return (v >> (kHShif
 // The sort is one more most-significant-digit step: the bucket's borders share their top 11 key bits, the next 10 bits
 // (sub-bin) place a border to within ~2 positions -- count, scan, place -- and the rank inside a sub-bin is the number of
 // smaller {value, owner} pairs there.  (A 66-stage bitonic network on 2048 pairs took 39 us per launch.)  The scan is also
-// the bucket's sub-bin table for k_moments.  More than kSortLds borders (never seen): the network on global memory.
+// the bucket's sub-bin table for k_moments.  More than kSortLds borders (a thousand candidates or more of a wide
+// mantissa: tests/test_mse_routes.py::test_hist_global_sort_1000_candidates): the network on global memory.
 __device__ __forceinline__ void border_sort_body(int b, uint32_t *s_raw, const float *__restrict__ bt, const uint32_t *__restrict__ btab,
                                                  const uint32_t *__restrict__ bhist, int n_pairs, int stride,
                                                  uint32_t *__restrict__ sb, uint32_t *__restrict__ rank,
@@ -1530,6 +1531,53 @@ HistLayout hist_layout(int64_t n, int64_t n_pairs, int stride, int bcap, int sli
     return L;
 }
 
+// cells of one candidate of a format: 2^(M+1) + 1 + (pmax - 1)(2^M + 1) + 1 (the clamp cell)
+int hist_ncells(const QFmt &f)
+{
+    const int M = (int)f.M;
+    return (2 << M) + 1 + (f.pmax - 1) * ((1 << M) + 1) + 1;
+}
+
+// Every choice fp8q_mse_hist_launch takes from the size of the call, made in ONE place: the launcher runs this plan and
+// fp8q_mse_hist_plan (behind fp8q_mse_route, include/fp8q.h) reports it, so a test can assert which arm its shape reaches.
+struct HistPlan {
+    int stride;                 // max cells of one candidate: row pitch of the per-candidate border tables
+    int bcap, slice_min;
+    int64_t ntiles;             // partition tiles
+    int tpw, pwgs;              // tiles per partition workgroup; partition workgroups (<= kPartWgs, none of them empty)
+    int mom_nt;                 // threads per k_moments workgroup: 512 or 256
+    bool top_scan;              // more superblock totals than k_mse_eval scans for itself: k_iv_scan_top runs
+    HistLayout L;
+};
+
+HistPlan hist_plan(int64_t n, int64_t n_cand, const QFmt *fmts, int n_m)
+{
+    HistPlan P;
+    P.stride = 0;
+    for (int m = 0; m < n_m; ++m)
+        if (hist_ncells(fmts[m]) > P.stride) P.stride = hist_ncells(fmts[m]);
+    P.bcap = hist_bcap();
+    P.slice_min = hist_slice_min(n);
+    const int64_t n_pairs = (int64_t)n_m * n_cand;
+    P.L = hist_layout(n, n_pairs, P.stride, P.bcap, P.slice_min);
+    P.ntiles = cdiv(n, kPartTile);
+    // (round 6: an even split of the tiles over all 768 workgroups -- 4 or 5 tiles each instead of 628 workgroups of 5 on
+    // [64,32,112,112] -- was slower: histogram 21.8 -> 23.8 us, scatter 44.4 -> 47.9)
+    P.tpw = (int)cdiv(P.ntiles, kPartWgs);
+    P.pwgs = (int)cdiv(P.ntiles, P.tpw);
+    // threads per k_moments workgroup.  At 25.7 M keys the kernel is bound by VALU issue (~44 instructions per key) and 256 threads are
+    // best (48.6 us against 51.7 with 111 pairs, 88 against 107 with 666); on MobileNetV2's smaller activations a few hundred
+    // units of one or two 4096-key batches each leave most CUs with one workgroup, the unit's own latency is the launch's
+    // duration, and 512 threads halve it: 25.9 -> 17.7 us at 0.5 M elements, 42.1 -> 27.4 at 7.2 M with 666 pairs
+    // (profiles/r06_moments_nt_ab.txt).  Third session, after the branch-free bisection: the same rule holds -- with 111 pairs 256
+    // threads win from 4.8 M keys (10.7 us against 14.1), with 666 pairs 512 threads up to 12.8 M (33.2 against 37.5; 19.3 M: 51.7
+    // against 47.8) -- the second threshold moved from 12 M to 16 M elements.  FP8Q_MSE_MOM_NT = 256 / 512 overrides.
+    static const int mom_env = env_int("FP8Q_MSE_MOM_NT", 0, 0, 512);
+    P.mom_nt = mom_env >= 256 ? (mom_env >= 512 ? 512 : 256) : (n <= (n_pairs > 256 ? (16ll << 20) : (3ll << 20)) ? 512 : 256);
+    P.top_scan = P.L.nsb > kTopLds;          // (more than half a million intervals: thousands of candidates)
+    return P;
+}
+
 }  // namespace
 
 // (called from fp8q_mse.hip)
@@ -1547,6 +1595,20 @@ bool fp8q_mse_hist_supported(const QFmt *fmts, int n_m, int n_bits)
     return true;
 }
 
+// the plan of a call this route takes, for fp8q_mse_route: the launcher's own hist_plan(), nothing recomputed
+int fp8q_mse_hist_plan(int64_t n, int64_t n_cand, const QFmt *fmts, int n_m, fp8q_mse_route_info *out)
+{
+    const HistPlan P = hist_plan(n, n_cand, fmts, n_m);
+    if (P.stride > kStrideBound) return FP8Q_EUNSUPPORTED;
+    out->tiles_per_wg = P.tpw;
+    out->part_wgs = P.pwgs;
+    out->slice_min = P.slice_min;
+    out->moments_threads = P.mom_nt;
+    out->n_superblocks = P.L.nsb;
+    out->top_scan = P.top_scan ? 1 : 0;
+    return FP8Q_OK;
+}
+
 int fp8q_mse_hist_launch(const float *x, int64_t n, const float *grid, int64_t n_cand, const QFmt *fmts, int n_m, float *mses,
                          void *ws, size_t ws_bytes, hipStream_t st, int brute, int overwrite, const SelOne *sel)
 {
@@ -1556,19 +1618,18 @@ int fp8q_mse_hist_launch(const float *x, int64_t n, const float *grid, int64_t n
     a.n_m = n_m;
     a.n_cand = (int)n_cand;
     a.n = n;
-    a.stride = 0;
     a.uns = fmts[0].sign_bits == 0;
     a.overwrite = overwrite;
     for (int m = 0; m < n_m; ++m) {
         a.fmt[m] = fmts[m];
-        const int M = (int)fmts[m].M;
-        a.ncells[m] = (2 << M) + 1 + (fmts[m].pmax - 1) * ((1 << M) + 1) + 1;
-        if (a.ncells[m] > a.stride) a.stride = a.ncells[m];
+        a.ncells[m] = hist_ncells(fmts[m]);
     }
+    const HistPlan P = hist_plan(n, n_cand, fmts, n_m);
+    a.stride = P.stride;
     if (a.stride > kStrideBound) return FP8Q_EUNSUPPORTED;
-    const int bcap = hist_bcap(), slice_min = hist_slice_min(n);
+    const int bcap = P.bcap, slice_min = P.slice_min;
     const int64_t n_pairs = (int64_t)n_m * n_cand;
-    const HistLayout L = hist_layout(n, n_pairs, a.stride, bcap, slice_min);
+    const HistLayout &L = P.L;
     if (ws_bytes < L.total) return FP8Q_EWORKSPACE;
     char *w = (char *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
     auto at = [&](size_t off) { return (void *)(w + off); };
@@ -1588,11 +1649,8 @@ int fp8q_mse_hist_launch(const float *x, int64_t n, const float *grid, int64_t n
     DD *p1 = (DD *)at(L.p1), *p2 = (DD *)at(L.p2), *t1 = (DD *)at(L.t1), *t2 = (DD *)at(L.t2);
 
     const uint32_t *xb = reinterpret_cast<const uint32_t *>(x);
-    const int64_t ntiles = cdiv(n, kPartTile);
-    // (round 6: an even split of the tiles over all 768 workgroups -- 4 or 5 tiles each instead of 628 workgroups of 5 on
-    // [64,32,112,112] -- was slower: histogram 21.8 -> 23.8 us, scatter 44.4 -> 47.9)
-    const int tpw = (int)cdiv(ntiles, kPartWgs);              // tiles per partition workgroup
-    const int pwgs = (int)cdiv(ntiles, tpw);                  // <= kPartWgs, none of them empty
+    const int64_t ntiles = P.ntiles;
+    const int tpw = P.tpw, pwgs = P.pwgs;
     if (a.uns)
         hipLaunchKernelGGL(k_stage1<true>, dim3((unsigned)(n_pairs + pwgs)), dim3(kBlock), 0, st, xb, n, ntiles, tpw, ktab, kmax, kneg,
                            grid, a, brute, bt, bq, cflag, btab);
@@ -1625,15 +1683,7 @@ int fp8q_mse_hist_launch(const float *x, int64_t n, const float *grid, int64_t n
         if (int rc = launch_rc()) return rc;
     }
     const size_t shmem = (size_t)kMomTabWords * 4 + (size_t)((bcap + 3) & ~3) * 4 + (size_t)(bcap + 1) * 16;
-    // threads per k_moments workgroup.  At 25.7 M keys the kernel is bound by VALU issue (~44 instructions per key) and 256 threads are
-    // best (48.6 us against 51.7 with 111 pairs, 88 against 107 with 666); on MobileNetV2's smaller activations a few hundred
-    // units of one or two 4096-key batches each leave most CUs with one workgroup, the unit's own latency is the launch's
-    // duration, and 512 threads halve it: 25.9 -> 17.7 us at 0.5 M elements, 42.1 -> 27.4 at 7.2 M with 666 pairs
-    // (profiles/r06_moments_nt_ab.txt).  Third session, after the branch-free bisection: the same rule holds -- with 111 pairs 256
-    // threads win from 4.8 M keys (10.7 us against 14.1), with 666 pairs 512 threads up to 12.8 M (33.2 against 37.5; 19.3 M: 51.7
-    // against 47.8) -- the second threshold moved from 12 M to 16 M elements.  FP8Q_MSE_MOM_NT = 256 / 512 overrides.
-    static const int mom_env = env_int("FP8Q_MSE_MOM_NT", 0, 0, 512);
-    const int mom_nt = mom_env >= 256 ? (mom_env >= 512 ? 512 : 256) : (n <= (n_pairs > 256 ? (16ll << 20) : (3ll << 20)) ? 512 : 256);
+    const int mom_nt = P.mom_nt;
     if (shmem > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(mom_nt == 512 ? (const void *)k_moments<512> : (const void *)k_moments<256>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1650,7 +1700,7 @@ int fp8q_mse_hist_launch(const float *x, int64_t n, const float *grid, int64_t n
     hipLaunchKernelGGL(k_iv_scan_super, dim3((unsigned)L.nsb), dim3(kSuper), 0, st, boff, gn, gd, gd2lo, gd2hi, L.ni, p1, p2, pn, t1,
                        t2, tn);
     if (int rc = launch_rc()) return rc;
-    if (L.nsb > kTopLds) {          // (more than half a million intervals: thousands of candidates)
+    if (P.top_scan) {
         hipLaunchKernelGGL(k_iv_scan_top, dim3(1), dim3(64), 0, st, t1, t2, tn, L.nsb);
         if (int rc = launch_rc()) return rc;
     }

@@ -20,6 +20,12 @@ class MseState(ctypes.Structure):
                 ("xmin", _vp), ("mbits", _vp), ("vote", _vp)]
 
 
+class MseRouteInfo(ctypes.Structure):
+    """fp8q_mse_route_info (include/fp8q.h): the kernel a K4 call reaches and the choices its launcher takes from the shape"""
+    _fields_ = [("kernel", _i), ("finish", _i), ("nsplit", _i64), ("tiles_per_wg", _i), ("part_wgs", _i), ("slice_min", _i),
+                ("moments_threads", _i), ("n_superblocks", _i64), ("top_scan", _i), ("reserved", _i)]
+
+
 class AffinePre(ctypes.Structure):
     """fp8q_affine_pre (include/fp8q.h): the BN + activation (+ residual) in front of a per-tensor MSE-calibrated quantizer"""
     _fields_ = [("x", _vp), ("residual", _vp), ("alpha_beta", _vp), ("N", _i64), ("C", _i64), ("HW", _i64), ("act", _i)]
@@ -47,6 +53,7 @@ SIGNATURES = {
     "fp8q_mse_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64, _i]),
     "fp8q_mse_grid_f32": (_i, [_vp, _i64, _i64, _vp, _i64, ctypes.POINTER(_f), _i, _i, _i, _vp, _vp,
                                ctypes.c_size_t, _vp]),
+    "fp8q_mse_route": (_i, [_i64, _i64, _i64, ctypes.POINTER(_f), _i, _i, _i, ctypes.POINTER(MseRouteInfo)]),
     "fp8q_mse_linspace_f32": (_i, [_vp, _i64, _i, ctypes.c_double, ctypes.c_double, _vp, _vp]),
     "fp8q_minmax_linspace_f32": (_i, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _i, ctypes.c_double, ctypes.c_double, _vp,
                                       ctypes.c_size_t, _vp]),

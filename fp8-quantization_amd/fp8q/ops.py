@@ -1126,6 +1126,21 @@ def mse_grid(x, per_channel, grid, mbits_list, n_bits, sign_bits, mses):
     return mses
 
 
+def mse_route(C, inner, n_cand, mbits_list, n_bits=8, sign_bits=1):
+    """The kernel mse_grid reaches for x [C, inner] with grid [n_cand, C] and these widths, and the choices its launcher takes
+    from the shape (fp8q_mse_route, include/fp8q.h), as a dict: kernel (0 k_mse_grid, 1 k_mse_row, 2 the interval histogram),
+    finish (0 none, 1 k_mse_final_tile, 2 k_mse_final), nsplit and, for the histogram, tiles_per_wg, part_wgs, slice_min,
+    moments_threads, n_superblocks, top_scan.  Host arithmetic only: needs no GPU.  Raises Fp8qError as mse_grid would."""
+    import ctypes
+    from ._lib import MseRouteInfo
+    n_m = len(mbits_list)
+    mb = (ctypes.c_float * max(n_m, 1))(*[float(v) for v in mbits_list])
+    info = MseRouteInfo()
+    check(lib().fp8q_mse_route(int(C), int(inner), int(n_cand), mb, n_m, int(n_bits), int(sign_bits), ctypes.byref(info)),
+          "fp8q_mse_route")
+    return {name: int(getattr(info, name)) for name, _ in MseRouteInfo._fields_ if name != "reserved"}
+
+
 _linspace_checked = {}     # (steps, fractions) -> True: the device kernel reproduces torch.linspace; False: host fall-back
 
 

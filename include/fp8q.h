@@ -160,9 +160,9 @@ int fp8q_minmax_quantize_f32(const float *x, float *y, int64_t C, int64_t inner,
  *                             element could take the other neighbour, which moved entries carried by a few elements -- the
  *                             search grid's last candidate 1.2 max|x| puts the largest element on a tie for M = 1, 3, 5 -- by up
  *                             to 4e-5);
- *   per-tensor rows of a format of <= 8 bits (signed or unsigned), long enough to pay for ~60 us of fixed cost (>= ~1 M elements
- *   for 111 (width, candidate) pairs, >= ~0.5 M for 666: FP_MSE_Estimator with the mantissa search, LineSearchEstimator's
- *   1000 candidates)               the interval histogram (csrc/fp8q_mse_hist.hip): a quantizer is a step function of |x|, so the
+ *   per-tensor rows (C == 1) of >= 16384 and < 2^31 elements, formats of <= 8 bits (all widths signed or all unsigned), at most
+ *   4096 (width, candidate) pairs: FP_MSE_Estimator with or without the mantissa search, LineSearchEstimator's 1000
+ *   candidates                the interval histogram (csrc/fp8q_mse_hist.hip): a quantizer is a step function of |x|, so the
  *                             exact borders of all cells of all candidates (the smallest float at which the reference's own
  *                             fp32 decisions flip) cut |x| into intervals; the nonzero keys are partitioned ONCE by their top
  *                             11 bits, integer moments {n, sum d, sum d^2} of every interval are accumulated with LDS atomics
@@ -177,6 +177,30 @@ size_t fp8q_mse_workspace_bytes(int64_t C, int64_t inner, int64_t n_cand, int n_
 int fp8q_mse_grid_f32(const float *x, int64_t C, int64_t inner, const float *grid, int64_t n_cand,
                       const float *mbits_host, int n_m, int n_bits, int sign_bits, float *mses,
                       void *ws, size_t ws_bytes, fp8q_stream_t stream);
+
+/*
+ * Which of K4's routes a call takes, and the size-dependent choices inside it: what fp8q_mse_grid_f32 (and the table step of
+ * fp8q_mse_calibrate_f32) would launch for this shape and these formats with a 4-byte-aligned x.  Host arithmetic only -- no
+ * launch, no device access, no allocation -- computed by the functions the launcher itself calls, so that a test can assert
+ * the kernel its shape reaches and a moved threshold fails that test instead of emptying it.  Arguments are checked as
+ * fp8q_mse_grid_f32 checks them (FP8Q_EINVAL, FP8Q_ETOOMANY, FP8Q_EUNSUPPORTED); `out` is written on FP8Q_OK only.
+ */
+typedef struct fp8q_mse_route_info {
+    int kernel;               /* 0 k_mse_grid (lane = candidate), 1 k_mse_row (lane = element), 2 the interval histogram */
+    int finish;               /* the launch that turns partial sums into table entries: 0 none (the kernel writes the table
+                                 itself), 1 k_mse_final_tile (<= 32 partial sums per row), 2 k_mse_final */
+    int64_t nsplit;           /* partial sums per (channel, width, candidate) row; 0 on the histogram route */
+    /* histogram route only (0 elsewhere) */
+    int tiles_per_wg;         /* 8192-key tiles per partition workgroup */
+    int part_wgs;             /* partition workgroups (<= 768) */
+    int slice_min;            /* smallest key slice of a k_moments unit: 2048 ... 16384 */
+    int moments_threads;      /* threads per k_moments workgroup: 512 or 256 */
+    int64_t n_superblocks;    /* 1024-interval superblocks of the prefix scan */
+    int top_scan;             /* 1: more than 512 superblocks, k_iv_scan_top runs between the scan and the evaluation */
+    int reserved;
+} fp8q_mse_route_info;
+int fp8q_mse_route(int64_t C, int64_t inner, int64_t n_cand, const float *mbits_host, int n_m, int n_bits, int sign_bits,
+                   fp8q_mse_route_info *out);
 
 /*
  * Sync-free MSE calibration.  The reference's FP_MSE_Estimator goes back to the host three times per call

@@ -417,11 +417,15 @@ def test_mse_grid_large_tensor(ops):
 
 
 def test_mse_row_kernel_all_paths(ops):
-    """k_mse_row (lane = element; rows >= 2048 elements) over ranges that take each of its per-candidate paths: one scale
-    mantissa (the usual case), two (ranges whose low binades round k - bias differently), the exact path (tiny / huge /
-    degenerate ranges, many exponent bits), unsigned formats, several rows with their own grids, a ragged last tile."""
+    """Ranges that take each per-candidate path of K4's kernels: one scale mantissa (the usual case), two (ranges whose low
+    binades round k - bias differently), the exact path (tiny / huge / degenerate ranges, many exponent bits), unsigned
+    formats, several rows with their own grids, a ragged last tile.  The route of every case is asserted: (1, 70001), a
+    per-tensor row of >= 16384 elements, goes through the interval histogram since round 6; (3, 5000) and (2, 4099) reach
+    k_mse_row (lane = element; rows >= 2048 elements); (4, 300) the lane-per-candidate kernel.  The same candidates on a
+    per-tensor row that k_mse_row serves: test_mse_routes.py::test_row_kernel_per_tensor_candidate_paths."""
     rng = np.random.RandomState(11)
-    for C, inner, sign in ((1, 70001, 1), (3, 5000, 1), (4, 300, 1), (2, 4099, 0)):   # (4, 300): the lane-per-candidate kernel
+    for C, inner, sign, kernel in ((1, 70001, 1, 2), (3, 5000, 1, 1), (4, 300, 1, 0), (2, 4099, 0, 1)):
+        assert ops.mse_route(C, inner, 68, [1.0, 2.0, 3.0, 4.0, 5.0, 6.0, 7.0], 8, sign)["kernel"] == kernel, (C, inner)
         x = (rng.randn(C, inner) * rng.uniform(0.3, 3.0, (C, 1))).astype(np.float32)
         if sign == 0:
             x = np.abs(x)
@@ -449,9 +453,15 @@ def test_mse_row_kernel_tile_dependent_paths(ops):
     the candidate's first binade), the float magic-number rounding (fixed-step subnormal range present) and their
     clamp-free twins (candidate range covers the tile).  Tensors built so that neighbouring 2048-element tiles take
     different paths: sparse tiles (exact zeros, -0), tiles with a few tiny / denormal nonzeros, tiles beyond every
-    candidate, exact rounding ties, one-sided data on an unsigned format, +-inf (clamps) and NaN (NaN table)."""
+    candidate, exact rounding ties, one-sided data on an unsigned format, +-inf (clamps) and NaN (NaN table).
+    Since round 6 a per-tensor row of this size (49 152 elements) is evaluated by the interval histogram -- asserted below --
+    so this data now checks that route; k_mse_row, whose tile has become 4096 elements, gets the same recipe on its own tile
+    and by shape in test_mse_routes.py::test_row_kernel_per_tensor_tile_paths / _per_channel_tile_paths."""
     rng = np.random.RandomState(23)
     n = 2048 * 24
+    assert ops.mse_route(1, n, 111, [1.0, 2.0, 3.0, 4.0, 5.0, 6.0], 8, 1)["kernel"] == 2
+    assert ops.mse_route(1, n, 111, [1.0, 2.0, 3.0, 4.0, 5.0, 6.0], 8, 0)["kernel"] == 2
+    assert ops.mse_route(1, n, 111, [2.0, 3.0], 8, 1)["kernel"] == 2          # (the NaN case at the end)
     for sign, special in ((1, False), (0, False), (1, True)):
         x = rng.randn(n).astype(np.float32)
         t = x.reshape(24, 2048)
