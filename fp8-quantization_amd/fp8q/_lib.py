@@ -31,6 +31,12 @@ class AffinePre(ctypes.Structure):
     _fields_ = [("x", _vp), ("residual", _vp), ("alpha_beta", _vp), ("N", _i64), ("C", _i64), ("HW", _i64), ("act", _i)]
 
 
+class MxtRouteInfo(ctypes.Structure):
+    """fp8q_mxt_route_info (include/fp8q.h): the kernel a transposed-MX call reaches and its tile"""
+    _fields_ = [("kernel", _i), ("tile_rows", _i), ("tile_cols", _i), ("nontemporal", _i), ("code_store_bytes", _i),
+                ("reserved", _i)]
+
+
 class TensorDesc(ctypes.Structure):
     """fp8q_tensor_desc (include/fp8q.h)"""
     _fields_ = [("x", _vp), ("y", _vp), ("maxval", _vp), ("C", _i64), ("inner", _i64), ("n_maxval", _i64),
@@ -145,6 +151,13 @@ SIGNATURES = {
     "fp8q_mx_decode_h16": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _vp]),
     "fp8q_mx_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _vp]),
     "fp8q_mx_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _i, _vp]),
+    "fp8q_mxt_route": (_i, [_i64, _i64, _i, _i, _i, ctypes.POINTER(MxtRouteInfo)]),
+    "fp8q_mxt_encode_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp]),
+    "fp8q_mxt_encode_h16": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _vp]),
+    "fp8q_mxt_encode_both_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _vp]),
+    "fp8q_mxt_encode_both_h16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i, _i, _vp]),
+    "fp8q_mxt_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _vp]),
+    "fp8q_mxt_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _i, _vp]),
 }
 
 

@@ -1731,6 +1731,102 @@ def mx_quantize(x, fmt, rounding="floor", out_dtype=None, out=None):
     return y
 
 
+# ---- microscaling with the blocks along dim 0: the operands of x.t() from x as it lies (csrc/fp8q_mx_t.hip) ----
+def _mx_t_geometry(x, fmt, need_r=True, need_k=False):
+    """(R, K) of a 2-D x whose MX blocks run along dim 0; need_r / need_k: the packing of codes along R / K must come out in
+    whole bytes (the encoders).  Everything here is told from the shape alone, so it is raised before the device check."""
+    if not isinstance(x, torch.Tensor):
+        raise Fp8qError("x must be a CUDA(HIP) tensor: the FP8 engine has no CPU path")
+    if x.dim() != 2:
+        raise Fp8qError(f"the transposed MX operands are those of a matrix: x must be 2-D, got {x.dim()}-D {tuple(x.shape)} "
+                        f"(reshape it to [R, K] first: the blocks run along dim 0 of that view)")
+    R, K = int(x.shape[0]), int(x.shape[1])
+    for need, n, what in ((need_r, R, "dim 0 (rows)"), (need_k, K, "the last dimension")):
+        if need and fmt == torch.float4_e2m1fn_x2 and n % 2:
+            raise Fp8qError(f"two E2M1 elements share a byte: {what} must be even, got {n}")
+        if need and fmt in _MX_FP6 and n % 4:
+            raise Fp8qError(f"four FP6 elements share three bytes: {what} must be a multiple of 4, got {n}")
+    return R, K
+
+
+def mx_t_route(R, K, fmt, dtype, aligned16=True):
+    """The kernel mx_encode_t / mx_encode_both / mx_quantize_t reach for an [R, K] tensor of `dtype` -- fp8q_mxt_route, the
+    launchers' own rule, host arithmetic only (no GPU needed).  aligned16: every tensor of the call starts on 16 bytes.
+    A dict: kernel "tile" or "general", tile_rows / tile_cols (the tile kernel's), nontemporal, code_store_bytes."""
+    from ._lib import MxtRouteInfo
+    import ctypes
+    if dtype not in _DT:
+        raise Fp8qError(f"dtype must be float32, float16 or bfloat16, got {dtype}")
+    info = MxtRouteInfo()
+    check(lib().fp8q_mxt_route(int(R), int(K), _mx_fmt(fmt), _DT[dtype], int(bool(aligned16)), ctypes.byref(info)),
+          "fp8q_mxt_route")
+    return {"kernel": "tile" if info.kernel == 0 else "general", "tile_rows": info.tile_rows, "tile_cols": info.tile_cols,
+            "nontemporal": bool(info.nontemporal), "code_store_bytes": info.code_store_bytes}
+
+
+def mx_encode_t(x, fmt, rounding="floor", out=None, scales_out=None):
+    """MX operands of x.t() made from x as it lies: (codes_t, scales_t), byte for byte mx_encode(x.t().contiguous(), fmt,
+    rounding) -- blocks of 32 along dim 0 of x, for a product that reduces over it -- in one launch that reads x once and
+    makes no transposed copy.  x: 2-D [R, K] (reshape anything else), float32 / float16 / bfloat16.  codes_t: [K, R] (FP8),
+    [K, R / 2] (E2M1: rows 2i and 2i + 1 of a column share a byte, R even) or uint8 [K, 3R / 4] ("e2m3" / "e3m2": R a multiple
+    of 4); scales_t: torch.float8_e8m0fnu [K, ceil(R / 32)].  mx_decode(codes_t, scales_t).t() gives the values back."""
+    f, r = _mx_fmt(fmt), _mx_rounding(rounding)
+    _mx_t_geometry(x, fmt)
+    _require(x, "x", _VALUES)
+    x = x.detach().contiguous()
+    R, K = x.shape
+    _, _, cshape, sshape = _mx_geometry((K, R), fmt)
+    cdt = _mx_code_dtype(fmt)
+    codes = _mx_bytes(out, cshape, cdt, "out", x)
+    scales = _mx_bytes(scales_out, sshape, MX_SCALE_DTYPE, "scales_out", x)
+    if x.numel():
+        sfx, types = _lane(x.dtype)
+        _run("fp8q_mxt_encode" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), *types, R, K, f, r)
+    return codes.view(cdt).view(cshape), scales.view(MX_SCALE_DTYPE).view(sshape)
+
+
+def mx_encode_both(x, fmt, rounding="floor", out=None, scales_out=None, out_t=None, scales_out_t=None):
+    """Both orientations of x's MX operands from ONE read of x: (codes, scales, codes_t, scales_t) = mx_encode(x) +
+    mx_encode_t(x), byte for byte, in one launch.  x: 2-D; E2M1 needs R and K even, the 6-bit formats multiples of 4.
+    out / scales_out / out_t / scales_out_t: contiguous tensors of the results' dtype or uint8, as in mx_encode."""
+    f, r = _mx_fmt(fmt), _mx_rounding(rounding)
+    _mx_t_geometry(x, fmt, need_k=True)
+    _require(x, "x", _VALUES)
+    x = x.detach().contiguous()
+    R, K = x.shape
+    _, _, cshape, sshape = _mx_geometry((R, K), fmt)
+    _, _, ctshape, stshape = _mx_geometry((K, R), fmt)
+    cdt = _mx_code_dtype(fmt)
+    codes = _mx_bytes(out, cshape, cdt, "out", x)
+    scales = _mx_bytes(scales_out, sshape, MX_SCALE_DTYPE, "scales_out", x)
+    codes_t = _mx_bytes(out_t, ctshape, cdt, "out_t", x)
+    scales_t = _mx_bytes(scales_out_t, stshape, MX_SCALE_DTYPE, "scales_out_t", x)
+    if x.numel():
+        sfx, types = _lane(x.dtype)
+        _run("fp8q_mxt_encode_both" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), codes_t.data_ptr(),
+             scales_t.data_ptr(), *types, R, K, f, r)
+    return (codes.view(cdt).view(cshape), scales.view(MX_SCALE_DTYPE).view(sshape),
+            codes_t.view(cdt).view(ctshape), scales_t.view(MX_SCALE_DTYPE).view(stshape))
+
+
+def mx_quantize_t(x, fmt, rounding="floor", out_dtype=None, out=None):
+    """Fake-quantize x with the MX blocks along dim 0, in x's own layout: mx_decode(*mx_encode_t(x, fmt, rounding)).t() bit
+    for bit, in one launch.  x: 2-D, any R and K -- nothing is packed, so E2M1 and the 6-bit formats need no divisible shape
+    here (mx_encode_t does).  Output dtype as mx_quantize."""
+    f, r = _mx_fmt(fmt), _mx_rounding(rounding)
+    _mx_t_geometry(x, fmt, need_r=False)
+    _require(x, "x", _VALUES)
+    dt = _quantize_out_dtype(x, out, out_dtype)
+    x = x.detach().contiguous()
+    R, K = x.shape
+    y = _out(out, x, dt)
+    if x.numel() == 0:
+        return y
+    sfx, types = _lane(x.dtype, dt)
+    _run("fp8q_mxt_quantize" + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, f, r)
+    return y
+
+
 def _nchw(x):
     """[N, C, *spatial] -> (N, C, HW)."""
     if x.dim() < 2:

@@ -9,7 +9,11 @@ The scale of a block is a function of that block's own largest element, found in
 to estimate, calibrate, fix or learn.  `range_free = True` tells QuantizationManager so -- it calls the quantizer directly in
 every state and never runs its estimator.  Blocks run along the last dimension, the reduction dimension of a Linear weight
 [out, in] and of its input; flatten_rows=True views a tensor of more than two dimensions as [shape[0], -1] first, which is
-what a convolution weight [out, in, kh, kw] wants.
+what a convolution weight [out, in, kh, kw] wants.  block_axis=-2 runs the blocks along dim 0 of that 2-D view instead
+(csrc/fp8q_mx_t.hip): the operand of a product that reduces over dim 0 -- dx = dy . W over W's rows, dW = dy^T . x over the
+tokens -- whose blocks hold other elements than the row-wise ones, so its scales and rounding differ.  encode() then returns
+the operands of the transpose, [K, R]-shaped, and the tensor must be 2-D after flatten_rows and as divisible along dim 0 as
+the format's packing asks (E2M1: even, the 6-bit formats: a multiple of 4).
 
 It follows the quantizer protocol (QuantizerBase) and the model zoo takes it as `method=MXQuantizer`; it is deliberately NOT a
 member of QMethods (the CLI's choices).  Forward only: there is no backward kernel, and a call that would need a gradient
@@ -30,7 +34,7 @@ class MXQuantizer(QuantizerBase):
     range_free = True
 
     def __init__(self, n_bits=None, fmt=torch.float8_e4m3fn, rounding="floor", keep_dtype=False, flatten_rows=False,
-                 per_channel=False, scale_domain=None, **kwargs):
+                 per_channel=False, scale_domain=None, block_axis=-1, **kwargs):
         if not isinstance(fmt, (torch.dtype, str)) or fmt not in _BITS:
             raise ValueError(f"fmt must be torch.float8_e4m3fn, torch.float8_e5m2, torch.float4_e2m1fn_x2, 'e2m3' or 'e3m2', "
                              f"got {fmt!r}")
@@ -38,6 +42,9 @@ class MXQuantizer(QuantizerBase):
             raise ValueError(f"{_NAME[fmt]} elements have {_BITS[fmt]} bits, got n_bits={n_bits}")
         if rounding not in ("floor", "ceil"):
             raise ValueError(f"rounding must be 'floor' or 'ceil', got {rounding!r}")
+        if block_axis not in (-1, -2) or isinstance(block_axis, bool):
+            raise ValueError(f"block_axis must be -1 (blocks along the last dimension) or -2 (along dim 0 of the 2-D view), "
+                             f"got {block_axis!r}")
         # per_channel is the protocol's argument; the scales are per block either way
         super().__init__(n_bits=_BITS[fmt], per_channel=per_channel, **kwargs)
         self.fmt = fmt
@@ -45,6 +52,7 @@ class MXQuantizer(QuantizerBase):
         # float16 / bfloat16 inputs: False returns float32, True the input's dtype (the float32 value rounded once)
         self.keep_dtype = keep_dtype
         self.flatten_rows = flatten_rows
+        self.block_axis = block_axis
 
     @property
     def is_initialized(self):
@@ -72,24 +80,40 @@ class MXQuantizer(QuantizerBase):
             return t.contiguous().view(t.shape[0], -1)
         return t
 
+    def _matrix(self, t):
+        """_rows(t) for block_axis=-2: it must be a matrix whose transposed operands can be made (ops.mx_encode_t's rules),
+        so that decode(*encode(x)) == forward(x) holds for every tensor forward takes"""
+        t = self._rows(t)
+        _ops._mx_t_geometry(t, self.fmt)
+        return t
+
     def forward(self, x_float):
         if torch.is_grad_enabled() and x_float.requires_grad:
             raise NotImplementedError("MXQuantizer is forward-only: there is no backward kernel for the MX lane (call it "
                                       "under torch.no_grad(), or on a detached tensor)")
         out_dtype = x_float.dtype if (self.keep_dtype and x_float.dtype in _HALF) else None
-        y = _ops.mx_quantize(self._rows(x_float), self.fmt, self.rounding, out_dtype=out_dtype)
+        if self.block_axis == -2:
+            y = _ops.mx_quantize_t(self._matrix(x_float), self.fmt, self.rounding, out_dtype=out_dtype)
+        else:
+            y = _ops.mx_quantize(self._rows(x_float), self.fmt, self.rounding, out_dtype=out_dtype)
         return y.view(x_float.shape)
 
     def encode(self, x_float):
         """(codes, scales) of forward(x): codes of dtype `fmt` ([..., K] for FP8, [..., K / 2] for E2M1; torch.uint8
         [..., 3K / 4] for the 6-bit formats), scales torch.float8_e8m0fnu [..., ceil(K / 32)]; with flatten_rows, of the
-        [shape[0], -1] view."""
+        [shape[0], -1] view.  block_axis=-2: the operands of that view's transpose, ops.mx_encode_t's."""
+        if self.block_axis == -2:
+            return _ops.mx_encode_t(self._matrix(x_float.detach()), self.fmt, self.rounding)
         return _ops.mx_encode(self._rows(x_float.detach()), self.fmt, self.rounding)
 
     def decode(self, codes, scales, out_dtype=None):
         """Values of encode()'s operands, float32 or out_dtype (float16 / bfloat16: the float32 value rounded once), shaped as
-        encode() saw them: decode(*encode(x)) == forward(x) bit for bit (after .view(x.shape) with flatten_rows)."""
+        encode() saw them: decode(*encode(x)) == forward(x) bit for bit (after .view(x.shape) with flatten_rows).
+        block_axis=-2: the transposed operands decode to [K, R]; the result is that, transposed back (a view)."""
+        if self.block_axis == -2:
+            return _ops.mx_decode(codes, scales, fmt=self.fmt, out_dtype=out_dtype).t()
         return _ops.mx_decode(codes, scales, fmt=self.fmt, out_dtype=out_dtype)
 
     def extra_repr(self):
-        return f"{super().extra_repr()}, fmt={_NAME[self.fmt]}, rounding={self.rounding}, flatten_rows={self.flatten_rows}"
+        return f"{super().extra_repr()}, fmt={_NAME[self.fmt]}, rounding={self.rounding}, flatten_rows={self.flatten_rows}, " \
+               f"block_axis={self.block_axis}"

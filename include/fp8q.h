@@ -926,6 +926,59 @@ int fp8q_mx_quantize_f32(const float *x, float *y, int64_t R, int64_t K, int fmt
 int fp8q_mx_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int fmt, int rounding,
                          fp8q_stream_t stream);
 
+/* ---- microscaling with the blocks along dim 0: the operands of the transpose, made from x as it lies -----------------------
+ * (csrc/fp8q_mx_t.hip)  A product that reduces over dim 0 of x -- dx = dy . W over W's rows, dW = dy^T . x over the tokens --
+ * needs x's MX blocks along dim 0, and those are not a permutation of the row-wise ones.  x is [R, K], K contiguous, float32
+ * or a half type (widened exactly).
+ * Contract, by reference: the transposed operands of x are, byte for byte, the operands of the contiguous [K, R] tensor x^T
+ * under the MX contract above (the same scale rule, the 0xFF block, element arithmetic and packing; fmt and rounding as
+ * there).  So column c of x is cut into the blocks of rows [32j, min(32j + 32, R)); codes_t is [K, R] bytes for FP8,
+ * [K, R / 2] for E2M1 (rows 2i and 2i + 1 of a column share a byte) and [K, 3R / 4] for FP6 (four consecutive rows of a column
+ * are three bytes); scales_t is [K, ceil(R / 32)].  fp8q_mx_decode_* reads them as the [K, R] operands they are; there is no
+ * transposing decode.
+ *   fp8q_mxt_encode_*       writes codes_t and scales_t
+ *   fp8q_mxt_encode_both_*  writes codes / scales, equal to fp8q_mx_encode_*'s, and codes_t / scales_t, equal to
+ *                           fp8q_mxt_encode_*'s, from one read of x
+ *   fp8q_mxt_quantize_*     fake-quantize in x's own layout: y[r][c] = the decode of the transposed operands at [c][r]; the
+ *                           type pairs are fp8q_mx_quantize_*'s
+ * Divisibility: an encoder packs codes along R, so fp8q_mxt_encode_* needs an even R for FP8Q_MX_E2M1 and R % 4 == 0 for the
+ * FP6 formats, and fp8q_mxt_encode_both_* needs the same of R and of K.  fp8q_mxt_quantize_* packs nothing and takes every R
+ * and K.
+ * Errors, all reported before the launch, as the MX entries report them: FP8Q_EINVAL for null pointers, R or K <= 0, a value
+ * pointer off its element's alignment, an unknown rounding, the divisibility above, a wrong type or pair of types, a size
+ * whose element count or grid overflows; FP8Q_EUNSUPPORTED for any other fmt, 3 included.
+ * fp8q_mxt_route is host arithmetic only: it reports the kernel the three entries reach for a shape -- every launcher calls
+ * it -- so that a test can assert the route before it trusts a shape.  aligned16: whether every pointer of the call is
+ * 16-byte aligned.  The tile kernel (rows readable with 16-byte loads: K % 4 == 0 for float32, K % 8 == 0 for a half type;
+ * aligned16) reads every element once and writes codes_t in runs of a tile's rows; anything else goes block by block, one
+ * lane each, with the same results.  One launch per call, enqueue-only, no workspace.
+ * Names: these entries are fp8q_mxt_*, not fp8q_mx_*_t: the set of fp8q_mx_* entries is the row-wise lane's six.
+ * FP8Q_VERSION is unchanged: the entries are additive.
+ */
+#define FP8Q_MXT_TILE 0
+#define FP8Q_MXT_GENERAL 1
+typedef struct fp8q_mxt_route_info {
+    int kernel;             /* FP8Q_MXT_TILE or FP8Q_MXT_GENERAL */
+    int tile_rows;          /* rows of x under one workgroup of the tile kernel: a multiple of 32 */
+    int tile_cols;          /* its columns: a multiple of 4 */
+    int nontemporal;        /* the tile kernel's nontemporal variant (R * K * 4 bytes from 64 MiB) */
+    int code_store_bytes;   /* bytes per store of transposed codes: 16 where a codes_t row is a multiple of 16 bytes, else 4
+                               or 1 (the encoders on the tile kernel; 1 on the general route) */
+    int reserved;
+} fp8q_mxt_route_info;
+int fp8q_mxt_route(int64_t R, int64_t K, int fmt, int x_type, int aligned16, fp8q_mxt_route_info *info);
+int fp8q_mxt_encode_f32(const float *x, uint8_t *codes_t, uint8_t *scales_t, int64_t R, int64_t K, int fmt, int rounding,
+                        fp8q_stream_t stream);
+int fp8q_mxt_encode_h16(const void *x, uint8_t *codes_t, uint8_t *scales_t, int x_type, int64_t R, int64_t K, int fmt,
+                        int rounding, fp8q_stream_t stream);
+int fp8q_mxt_encode_both_f32(const float *x, uint8_t *codes, uint8_t *scales, uint8_t *codes_t, uint8_t *scales_t, int64_t R,
+                             int64_t K, int fmt, int rounding, fp8q_stream_t stream);
+int fp8q_mxt_encode_both_h16(const void *x, uint8_t *codes, uint8_t *scales, uint8_t *codes_t, uint8_t *scales_t, int x_type,
+                             int64_t R, int64_t K, int fmt, int rounding, fp8q_stream_t stream);
+int fp8q_mxt_quantize_f32(const float *x, float *y, int64_t R, int64_t K, int fmt, int rounding, fp8q_stream_t stream);
+int fp8q_mxt_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int fmt, int rounding,
+                          fp8q_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
