@@ -33,6 +33,14 @@ struct AffineArgs {
 constexpr int kAffinePiece = kBlock * 4 * 4;   // elements per block and step (16 KiB)
 constexpr int kAffineMagicMaxHW = kMagicMaxDivisor;   // above: a piece spans <= 2 planes (compare instead of divide)
 
+// The staged kernels behind a batch norm keep the constants of a piece's planes in registers when there are at most two
+// (`direct`: uniform addresses, scalar loads) and stage them in LDS otherwise.  One rule for the FP8 and the INT kernel and
+// for fp8q_affine_act_route, which reports it.
+__host__ __device__ __forceinline__ bool affine_direct(const AffineArgs &a)
+{
+    return a.has_bn && a.cpp <= 2;
+}
+
 // {alpha, beta'} of one channel: alpha = invstd * gamma, beta' = fma(-mean, alpha, beta) (ATen's eval-mode batch norm) --
 // or, with has_bn == 2, read from the folded [C, 2] vector that fp8q_bn_fold_f32 wrote (`mean` then points to it): one
 // 8-byte load instead of four 4-byte ones per plane, the same two numbers.

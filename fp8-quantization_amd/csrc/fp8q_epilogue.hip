@@ -56,7 +56,7 @@ k_affine_act(const float *__restrict__ x, const float *__restrict__ res, float *
     // (uniform addresses: scalar loads) -- no LDS staging and no barrier per step, which is what separates the BN
     // variant from the plain one on the large early layers (75 -> 70 us at [64,64,112,112]; the same with up to
     // four planes in registers, for 56x56 planes, was measured and rejected: 94 us)
-    const bool direct = a.has_bn && a.cpp <= 2;
+    const bool direct = affine_direct(a);
     __syncthreads();       // lut is complete
     for (int base = blockIdx.x * (kBlock * U); base < nvec; base += gridDim.x * (kBlock * U)) {
         float2 p0, p1;
@@ -331,6 +331,32 @@ static int affine_quantize_impl(const float *x, const float *residual, float *y,
                                g, dim3(kBlock), shm, st, xp, rp, yp, mean, invstd, gamma, beta, maxval, f, a);
     });
     return launch_rc();
+}
+
+// What affine_quantize_impl would launch for this shape: its own affine_args + affine_dispatch with a callback that records
+// instead of launching.  Host arithmetic only.
+static_assert((int)AffineKernel::StagedNt == FP8Q_AFFINE_STAGED_NT && (int)AffineKernel::Small == FP8Q_AFFINE_SMALL &&
+              (int)AffineKernel::Staged1 == FP8Q_AFFINE_STAGED1 && (int)AffineKernel::Staged4 == FP8Q_AFFINE_STAGED4,
+              "fp8q_affine_route_info.kernel is AffineKernel's value");
+
+int fp8q_affine_act_route(int64_t N, int64_t C, int64_t HW, int has_bn, fp8q_affine_route_info *info)
+{
+    if (!info || has_bn < 0 || has_bn > 2) return FP8Q_EINVAL;
+    AffineArgs a;
+    if (int rc = affine_args(N, C, HW, 0, has_bn, false, &a)) return rc;
+    fp8q_affine_route_info r = {};
+    r.kernel = -1;      // N == 0: nothing is launched
+    r.cpp = a.cpp;
+    affine_dispatch(N, a, true, [&](AffineKernel kind, dim3 g, size_t, int64_t) {
+        if (r.launches++ == 0) {
+            r.kernel = (int)kind;
+            r.direct = kind != AffineKernel::Small && affine_direct(a);
+            r.grid_x = g.x;
+            r.grid_y = g.y;
+        }
+    });
+    *info = r;
+    return FP8Q_OK;
 }
 
 size_t fp8q_affine_act_minmax_workspace_bytes(int64_t N, int64_t C, int64_t HW)

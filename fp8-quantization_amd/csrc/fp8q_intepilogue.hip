@@ -89,7 +89,7 @@ k_int_affine_act(const float *x, const float *res, float *y, const float *__rest
     const vf4 *rv = reinterpret_cast<const vf4 *>(res + (a.has_res ? base0 : 0));
     vf4 *yv = reinterpret_cast<vf4 *>(y + base0);
     const uint32_t HW = (uint32_t)a.HW;
-    const bool direct = a.has_bn && a.cpp <= 2;
+    const bool direct = affine_direct(a);
     for (int base = blockIdx.x * (kBlock * U); base < nvec; base += gridDim.x * (kBlock * U)) {
         float2 p0, p1;
         const uint32_t phase = affine_step_planes(base, direct, a, p0, p1, cst, [&](uint32_t ch) {

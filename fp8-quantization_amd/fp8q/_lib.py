@@ -31,6 +31,11 @@ class AffinePre(ctypes.Structure):
     _fields_ = [("x", _vp), ("residual", _vp), ("alpha_beta", _vp), ("N", _i64), ("C", _i64), ("HW", _i64), ("act", _i)]
 
 
+class AffineRouteInfo(ctypes.Structure):
+    """fp8q_affine_route_info (include/fp8q.h): the kernel the fused FP8 epilogue reaches for a shape and its launches"""
+    _fields_ = [("kernel", _i), ("direct", _i), ("cpp", _i), ("launches", _i), ("grid_x", _i64), ("grid_y", _i64)]
+
+
 class MxtRouteInfo(ctypes.Structure):
     """fp8q_mxt_route_info (include/fp8q.h): the kernel a transposed-MX call reaches and its tile"""
     _fields_ = [("kernel", _i), ("tile_rows", _i), ("tile_cols", _i), ("nontemporal", _i), ("code_store_bytes", _i),
@@ -86,6 +91,7 @@ SIGNATURES = {
     "fp8q_quantizer_prepare_f32": (_i, [_vp, _f, _i, _i, _vp, _vp]),
     "fp8q_affine_act_quantize_ab_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i, _vp, _vp, _f, _i, _i, _vp]),
     "fp8q_affine_act_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i, _vp]),
+    "fp8q_affine_act_route": (_i, [_i64, _i64, _i64, _i, ctypes.POINTER(AffineRouteInfo)]),
     "fp8q_affine_act_minmax_linspace_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i, _vp, _vp, _vp, _vp, _i, ctypes.c_double,
                                                  ctypes.c_double, _vp, ctypes.c_size_t, _vp]),
     "fp8q_affine_act_minmax_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64]),

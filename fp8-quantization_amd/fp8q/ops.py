@@ -1956,6 +1956,23 @@ def affine_act(x, bn_ab=None, residual=None, act=0, out=None):
     return y
 
 
+AFFINE_KERNELS = ("staged_nt", "small", "staged1", "staged4")      # FP8Q_AFFINE_* (include/fp8q.h)
+
+
+def affine_act_route(N, C, HW, has_bn):
+    """The kernel affine_act_quantize / affine_act reach for an [N, C, HW] tensor with or without a batch norm
+    (fp8q_affine_act_route, include/fp8q.h), as a dict: kernel ("staged_nt" k_affine_act<true, 4>, "small" k_affine_act_small,
+    "staged1" k_affine_act<false, 1>, "staged4" k_affine_act<false, 4>; None when nothing is launched), direct (the staged
+    kernel keeps the BN constants of a piece's two planes in registers, not in LDS), cpp, launches, grid_x, grid_y (of the
+    first launch).  Host arithmetic only: needs no GPU.  Raises Fp8qError as affine_act_quantize would for the shape."""
+    import ctypes
+    from ._lib import AffineRouteInfo
+    info = AffineRouteInfo()
+    check(lib().fp8q_affine_act_route(int(N), int(C), int(HW), int(bool(has_bn)), ctypes.byref(info)), "fp8q_affine_act_route")
+    return {"kernel": AFFINE_KERNELS[info.kernel] if info.kernel >= 0 else None, "direct": bool(info.direct),
+            "cpp": int(info.cpp), "launches": int(info.launches), "grid_x": int(info.grid_x), "grid_y": int(info.grid_y)}
+
+
 def int_affine_act_quantize(x, delta, zero_float, signed_flag, n_bits, symmetric, eps, bn_ab=None, residual=None, act=0,
                             out=None):
     """N2 for the uniform quantizers: int_quantize(affine_act(x, bn_ab, residual, act)) in ONE pass

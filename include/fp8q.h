@@ -372,6 +372,29 @@ int fp8q_affine_act_quantize_ab_f32(const float *x, const float *residual, float
  * [C, 2] vector of fp8q_bn_fold_f32, or NULL (no batch norm). */
 int fp8q_affine_act_f32(const float *x, const float *residual, float *y, int64_t N, int64_t C, int64_t HW, const float *alpha_beta,
                         int act, fp8q_stream_t stream);
+/*
+ * Which kernel the three quantizing entries above (fp8q_affine_act_quantize_f32, _ab_, fp8q_affine_act_f32) launch for an
+ * [N, C, HW] tensor, with (has_bn 1 or 2) or without (0) a batch norm, at the process's settings.  Host arithmetic only: no
+ * launch, no device -- the launcher's own argument block and dispatch with a callback that records, so that a test can assert
+ * the route before it trusts a shape.  kernel: FP8Q_AFFINE_* below (-1 with launches == 0 when N == 0); direct: a staged
+ * kernel behind a batch norm keeps the constants of a piece's planes in registers (at most two planes per piece) instead of
+ * staging them in LDS; cpp: most planes one 4096-element piece overlaps; launches: one per 65535 images; grid_x / grid_y: of
+ * the first launch.  Errors as the entries report them for the shape: FP8Q_EINVAL (N < 0, C or HW not positive, has_bn
+ * outside 0..2, info NULL), FP8Q_EUNSUPPORTED (C * HW not a multiple of 4, C * HW >= 2^31, HW >= 2^24, C * HW * HW >= 2^48);
+ * `info` is written on FP8Q_OK only.
+ */
+#define FP8Q_AFFINE_STAGED_NT 0 /* k_affine_act<true, 4>: 16 KiB pieces, nontemporal (tensors of 64 MiB and more) */
+#define FP8Q_AFFINE_SMALL 1     /* k_affine_act_small: one 16-byte group per lane */
+#define FP8Q_AFFINE_STAGED1 2   /* k_affine_act<false, 1>: HW < 4 behind a batch norm */
+#define FP8Q_AFFINE_STAGED4 3   /* k_affine_act<false, 4>: only with FP8Q_EPI_SMALL_M below the nontemporal threshold */
+typedef struct fp8q_affine_route_info {
+    int kernel;
+    int direct;
+    int cpp;
+    int launches;
+    int64_t grid_x, grid_y;
+} fp8q_affine_route_info;
+int fp8q_affine_act_route(int64_t N, int64_t C, int64_t HW, int has_bn, fp8q_affine_route_info *info);
 /* The same pass for the FIRST calibration batch of an MSE estimator: t = act(bn(x) + residual) is written AND its minimum /
  * maximum / abs-max and the search grid linspace(lo_frac * max|t|, hi_frac * max|t|, n_cand) ([n_cand, 1]) come out of the same
  * launch (what fp8q_affine_act_f32 + fp8q_minmax_linspace_f32 on t give, bit for bit; 8 B / element instead of 12).

@@ -98,7 +98,10 @@ def test_fused_epilogue_bit_exact(shape, use_bn, use_res, act):
     np.testing.assert_array_equal(mvo.cpu().numpy(), oracle.c_absmax(rmn, rmx))
     mn2, mx2, _ = ops.affine_act_minmax(dev(x2 * 0.5), mn, mx, mode=1, bn=tuple(dev(b) for b in bn) if bn else None,
                                         residual=dev(res) if use_res else None, act=act)
-    assert mn2.item() <= rmn[0] and mx2.item() >= rmx[0]
+    bmn, bmx = oracle.c_minmax(ref_chain(x2 * np.float32(0.5), bn, res if use_res else None, act), False)
+    fmn, fmx = oracle.c_fold(rmn, rmx, bmn, bmx, 1)
+    np.testing.assert_array_equal(mn2.cpu().numpy().view(np.int32), fmn.view(np.int32))
+    np.testing.assert_array_equal(mx2.cpu().numpy().view(np.int32), fmx.view(np.int32))
 
 
 def test_fused_bn_matches_aten_cpu_batch_norm():
