@@ -99,10 +99,13 @@ struct MxArgs {
     int64_t nb;                   // blocks per row
     int64_t blocks;               // R * nb
     int ceil_rule;
+    MxSr sr;                      // the SR kernels' seed and offset
 };
 
 // ---- the fast route: n % 32 == 0, blocks tile the flat tensor, every vector word aligned ----
-template <int MODE, int F, class IN, class OUT, bool NT>
+// SR: elem = RNE(SR(q, r)), the draws by the element's flat index (fp8q_mxq.h); an encoding lane's 16 elements are two whole
+// Philox calls, a quantizing lane's group of 4 is half of one
+template <int MODE, int F, class IN, class OUT, bool NT, bool SR>
 __global__ void __launch_bounds__(kBlock)
 k_mx(const void *__restrict__ in, void *__restrict__ out, MxArgs a)
 {
@@ -131,8 +134,21 @@ k_mx(const void *__restrict__ in, void *__restrict__ out, MxArgs a)
         m = umax_xor<1>(m);
         const uint32_t sc = scale_code<F>(m, a.ceil_rule);
         uint32_t w[4];
+        if constexpr (SR) {
+            const uint64_t i0 = a.sr.offset + (uint64_t)e;      // a multiple of 8
+            uint32_t d[8];
+            mx_draw8(a.sr, i0, d);
+            mx_draw8(a.sr, i0 + 8u, d + 4);
 #pragma unroll
-        for (int g = 0; g < 4; ++g) w[g] = mx_code4<F>(v + 4 * g, sc);
+            for (int g = 0; g < 4; ++g) {
+                uint32_t r[4];
+                mx_split4(d + 2 * g, r);
+                w[g] = mx_code4_sr<F>(v + 4 * g, sc, r);
+            }
+        } else {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) w[g] = mx_code4<F>(v + 4 * g, sc);
+        }
         if (live) {
             if constexpr (F == FP8Q_MX_E2M1) {
                 stv<NT>(reinterpret_cast<u2v *>(y + (e >> 1)), u2v{w[0] | (w[1] << 16), w[2] | (w[3] << 16)});
@@ -158,7 +174,14 @@ k_mx(const void *__restrict__ in, void *__restrict__ out, MxArgs a)
                 m = umax_xor<2>(m);
                 m = umax_xor<4>(m);
                 sc = scale_code<F>(m, a.ceil_rule);
-                w = mx_code4<F>(v, sc);
+                if constexpr (SR) {
+                    uint32_t d[2], r[4];
+                    mx_draw4(a.sr, a.sr.offset + (uint64_t)(e0 + off), d);
+                    mx_split4(d, r);
+                    w = mx_code4_sr<F>(v, sc, r);
+                } else {
+                    w = mx_code4<F>(v, sc);
+                }
             } else if (live) {
                 sc = a.scales_in[(e0 + off) >> 5];
             }
@@ -196,7 +219,7 @@ k_mx(const void *__restrict__ in, void *__restrict__ out, MxArgs a)
 }
 
 // ---- the general route: one lane per block, element by element ----
-template <int MODE, int F, class IN, class OUT>
+template <int MODE, int F, class IN, class OUT, bool SR>
 __global__ void __launch_bounds__(kBlock)
 k_mx_plain(const void *__restrict__ in, void *__restrict__ out, MxArgs a)
 {
@@ -236,7 +259,14 @@ k_mx_plain(const void *__restrict__ in, void *__restrict__ out, MxArgs a)
             float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int k = 0; k < kStep; ++k) v[k] = IN::load1(x + e + k);
-            w = mx_code4<F>(v, sc) & ((1u << (8 * kBytes)) - 1u);
+            if constexpr (SR) {
+                uint32_t r[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                for (int k = 0; k < kStep; ++k) r[k] = mx_draw1(a.sr, a.sr.offset + (uint64_t)(e + k));
+                w = mx_code4_sr<F>(v, sc, r) & ((1u << (8 * kBytes)) - 1u);
+            } else {
+                w = mx_code4<F>(v, sc) & ((1u << (8 * kBytes)) - 1u);
+            }
         }
         if constexpr (MODE == kEncode) {
 #pragma unroll
@@ -250,28 +280,30 @@ k_mx_plain(const void *__restrict__ in, void *__restrict__ out, MxArgs a)
     }
 }
 
-template <int MODE, int F, class IN, class OUT>
+template <int MODE, int F, class IN, class OUT, bool SR>
 void launch_io(const void *in, void *out, const MxArgs &a, bool fast, hipStream_t st)
 {
     const dim3 b(kBlock);
     if (!fast) {
-        hipLaunchKernelGGL((k_mx_plain<MODE, F, IN, OUT>), dim3((unsigned)cdiv(a.blocks, kBlock)), b, 0, st, in, out, a);
+        hipLaunchKernelGGL((k_mx_plain<MODE, F, IN, OUT, SR>), dim3((unsigned)cdiv(a.blocks, kBlock)), b, 0, st, in, out, a);
         return;
     }
     const dim3 g((unsigned)cdiv(a.n, kMxChunk));
-    if (a.n * 4 >= kNtBytes) hipLaunchKernelGGL((k_mx<MODE, F, IN, OUT, true>), g, b, 0, st, in, out, a);
-    else hipLaunchKernelGGL((k_mx<MODE, F, IN, OUT, false>), g, b, 0, st, in, out, a);
+    if (a.n * 4 >= kNtBytes) hipLaunchKernelGGL((k_mx<MODE, F, IN, OUT, true, SR>), g, b, 0, st, in, out, a);
+    else hipLaunchKernelGGL((k_mx<MODE, F, IN, OUT, false, SR>), g, b, 0, st, in, out, a);
 }
 
 // Argument checks (everything is reported before the launch) and the one launch.  in_type / out_type: FP8Q_DT_* of the value
-// side(s), -1 for the side that holds codes.  scales: written by encode, read by decode, unused (null) by quantize.
+// side(s), -1 for the side that holds codes.  scales: written by encode, read by decode, unused (null) by quantize.  sr: the
+// seed and offset of a stochastic-rounding entry (encode, quantize), null for round to nearest even.
 int mx_launch(int mode, const void *in, void *out, const uint8_t *scales, int in_type, int out_type, int64_t R, int64_t K,
-              int fmt, int rounding, hipStream_t st)
+              int fmt, int rounding, hipStream_t st, const MxSr *sr = nullptr)
 {
     if (!in || !out || (mode != kQuant && !scales) || R <= 0 || K <= 0) return FP8Q_EINVAL;
     const bool fp6 = fmt == FP8Q_MX_E2M3 || fmt == FP8Q_MX_E3M2;
     if (fmt != FP8Q_MX_E4M3FN && fmt != FP8Q_MX_E5M2 && fmt != FP8Q_MX_E2M1 && !fp6) return FP8Q_EUNSUPPORTED;
     if (rounding != FP8Q_MX_FLOOR && rounding != FP8Q_MX_CEIL) return FP8Q_EINVAL;
+    if (sr && (sr->offset & 7u)) return FP8Q_EINVAL;
     if ((fmt == FP8Q_MX_E2M1 && (K & 1)) || (fp6 && (K & 3))) return FP8Q_EINVAL;
     if (value_side_misaligned(in, in_type) || value_side_misaligned(out, out_type)) return FP8Q_EINVAL;
     const int64_t nb = cdiv(K, kMxBlock);
@@ -284,16 +316,27 @@ int mx_launch(int mode, const void *in, void *out, const uint8_t *scales, int in
     a.nb = nb;
     a.blocks = R * nb;
     a.ceil_rule = rounding == FP8Q_MX_CEIL;
+    if (sr) a.sr = *sr;
     const bool fast = K % kMxBlock == 0 && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
     io_dispatch(mode, in_type, out_type, [&](auto m, auto ti, auto to) {
         constexpr int MODE = decltype(m)::value;
         typedef decltype(ti) IN;
         typedef decltype(to) OUT;
-        if (fmt == FP8Q_MX_E4M3FN) launch_io<MODE, FP8Q_MX_E4M3FN, IN, OUT>(in, out, a, fast, st);
-        else if (fmt == FP8Q_MX_E5M2) launch_io<MODE, FP8Q_MX_E5M2, IN, OUT>(in, out, a, fast, st);
-        else if (fmt == FP8Q_MX_E2M3) launch_io<MODE, FP8Q_MX_E2M3, IN, OUT>(in, out, a, fast, st);
-        else if (fmt == FP8Q_MX_E3M2) launch_io<MODE, FP8Q_MX_E3M2, IN, OUT>(in, out, a, fast, st);
-        else launch_io<MODE, FP8Q_MX_E2M1, IN, OUT>(in, out, a, fast, st);
+        auto go = [&](auto sr_on) {
+            constexpr bool SR = decltype(sr_on)::value;
+            if (fmt == FP8Q_MX_E4M3FN) launch_io<MODE, FP8Q_MX_E4M3FN, IN, OUT, SR>(in, out, a, fast, st);
+            else if (fmt == FP8Q_MX_E5M2) launch_io<MODE, FP8Q_MX_E5M2, IN, OUT, SR>(in, out, a, fast, st);
+            else if (fmt == FP8Q_MX_E2M3) launch_io<MODE, FP8Q_MX_E2M3, IN, OUT, SR>(in, out, a, fast, st);
+            else if (fmt == FP8Q_MX_E3M2) launch_io<MODE, FP8Q_MX_E3M2, IN, OUT, SR>(in, out, a, fast, st);
+            else launch_io<MODE, FP8Q_MX_E2M1, IN, OUT, SR>(in, out, a, fast, st);
+        };
+        if constexpr (MODE != kDecode) {
+            if (sr) {
+                go(std::true_type{});
+                return;
+            }
+        }
+        go(std::false_type{});
     });
     return launch_rc();
 }
@@ -338,6 +381,37 @@ int fp8q_mx_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t
 {
     if (int rc = check_types(x_type, y_type)) return rc;
     return mx_launch(kQuant, x, y, nullptr, x_type, y_type, R, K, fmt, rounding, (hipStream_t)stream);
+}
+
+// ---- stochastic rounding of the elements: the twins of the four entries above that convert ----
+int fp8q_mxsr_encode_f32(const float *x, uint8_t *codes, uint8_t *scales, int64_t R, int64_t K, int fmt, int rounding,
+                         uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    const MxSr sr = mx_sr_args(seed, offset);
+    return mx_launch(kEncode, x, codes, scales, FP8Q_DT_F32, -1, R, K, fmt, rounding, (hipStream_t)stream, &sr);
+}
+
+int fp8q_mxsr_encode_h16(const void *x, uint8_t *codes, uint8_t *scales, int x_type, int64_t R, int64_t K, int fmt,
+                         int rounding, uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    if (!half_type(x_type)) return FP8Q_EINVAL;
+    const MxSr sr = mx_sr_args(seed, offset);
+    return mx_launch(kEncode, x, codes, scales, x_type, -1, R, K, fmt, rounding, (hipStream_t)stream, &sr);
+}
+
+int fp8q_mxsr_quantize_f32(const float *x, float *y, int64_t R, int64_t K, int fmt, int rounding, uint64_t seed,
+                           uint64_t offset, fp8q_stream_t stream)
+{
+    const MxSr sr = mx_sr_args(seed, offset);
+    return mx_launch(kQuant, x, y, nullptr, FP8Q_DT_F32, FP8Q_DT_F32, R, K, fmt, rounding, (hipStream_t)stream, &sr);
+}
+
+int fp8q_mxsr_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int fmt, int rounding,
+                           uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    if (int rc = check_types(x_type, y_type)) return rc;
+    const MxSr sr = mx_sr_args(seed, offset);
+    return mx_launch(kQuant, x, y, nullptr, x_type, y_type, R, K, fmt, rounding, (hipStream_t)stream, &sr);
 }
 
 }  // extern "C"

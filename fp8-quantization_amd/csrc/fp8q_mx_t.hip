@@ -70,6 +70,7 @@ struct MxtArgs {
     int64_t tilesC;                   // tiles per 128 rows
     int ceil_rule;
     int gran;                         // bytes per store of transposed codes: 16, 4 or 1
+    MxSr sr;                          // the SR kernels' seed and offset
 };
 
 // one tile's transposed codes from LDS (s) to codes_t (dst: the tile's first byte), G bytes per store; run: the bytes of a
@@ -99,7 +100,10 @@ __device__ __forceinline__ void store_runs(const uint8_t *s, uint8_t *dst, int64
 }
 
 // ---- the tile route ----
-template <int OP, int F, class IN, class OUT, bool NT>
+// SR: elem = RNE(SR(q, r)), the draws by the element's flat index in x as it lies (fp8q_mxq.h): the 4 columns of a lane's row
+// are an aligned group of four (K % 4 == 0, the offset a multiple of 8), half a Philox call, made once and used by the
+// transposed codes and by encode_both's row-wise ones alike
+template <int OP, int F, class IN, class OUT, bool NT, bool SR>
 __global__ void __launch_bounds__(kBlock)
 k_mxt(const void *__restrict__ in, void *__restrict__ out, MxtArgs a)
 {
@@ -134,6 +138,13 @@ k_mxt(const void *__restrict__ in, void *__restrict__ out, MxtArgs a)
         m = o > m ? o : m;
         sct[k] = scale_code<F>(m, a.ceil_rule);
     }
+    // the two draw words of each of the lane's rows: columns 0, 1 in the first, 2, 3 in the second
+    uint32_t dr[SR ? kLaneRows : 1][2];
+    if constexpr (SR) {
+#pragma unroll
+        for (int p = 0; p < kLaneRows; ++p)
+            mx_draw4(a.sr, a.sr.offset + (uint64_t)(row0 + p) * (uint64_t)a.K + (uint64_t)c, dr[p]);
+    }
     // the codes of the lane's rows 4h .. 4h + 3 of column k
     uint32_t wt[4][2];
 #pragma unroll
@@ -141,7 +152,14 @@ k_mxt(const void *__restrict__ in, void *__restrict__ out, MxtArgs a)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const float t[4] = {v[4 * h][k], v[4 * h + 1][k], v[4 * h + 2][k], v[4 * h + 3][k]};
-            wt[k][h] = mx_code4<F>(t, sct[k]);
+            if constexpr (SR) {
+                uint32_t r[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) r[i] = (dr[4 * h + i][k >> 1] >> (16 * (k & 1))) & 0xffffu;
+                wt[k][h] = mx_code4_sr<F>(t, sct[k], r);
+            } else {
+                wt[k][h] = mx_code4<F>(t, sct[k]);
+            }
         }
     }
     if constexpr (OP == kOpQuantT) {
@@ -189,7 +207,14 @@ k_mxt(const void *__restrict__ in, void *__restrict__ out, MxtArgs a)
                 m = umax_xor<2>(m);
                 m = umax_xor<4>(m);
                 const uint32_t sc = scale_code<F>(m, a.ceil_rule);
-                const uint32_t w = mx_code4<F>(v[p], sc);
+                uint32_t w;
+                if constexpr (SR) {
+                    uint32_t r[4];
+                    mx_split4(dr[p], r);
+                    w = mx_code4_sr<F>(v[p], sc, r);
+                } else {
+                    w = mx_code4<F>(v[p], sc);
+                }
                 const int64_t row = row0 + p;
                 if (col_live && row < a.R) {
                     const int64_t e = row * a.K + c;
@@ -231,9 +256,9 @@ k_mxt(const void *__restrict__ in, void *__restrict__ out, MxtArgs a)
 // ---- the general route: one lane per block ----
 // the block of `len` elements `stride` apart from x[base]: its scale byte to *scale_at and its codes from codes_at on (encode),
 // or its values to y at the elements' own places (quantize); four elements at a time, the last group may be short
-template <bool QUANT, int F, class IN, class OUT>
+template <bool QUANT, int F, class IN, class OUT, bool SR>
 __device__ __forceinline__ void plain_block(const typename IN::elem *x, typename OUT::elem *y, int64_t base, int64_t stride,
-                                            int len, int ceil_rule, uint8_t *codes_at, uint8_t *scale_at)
+                                            int len, int ceil_rule, uint8_t *codes_at, uint8_t *scale_at, const MxSr &sr)
 {
     uint32_t m = 0u;
     for (int i = 0; i < len; ++i) {
@@ -248,7 +273,16 @@ __device__ __forceinline__ void plain_block(const typename IN::elem *x, typename
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (k < nv) v[k] = IN::load1(x + base + (i + k) * stride);
-        const uint32_t w = mx_code4<F>(v, sc);
+        uint32_t w;
+        if constexpr (SR) {
+            uint32_t r[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < nv) r[k] = mx_draw1(sr, sr.offset + (uint64_t)(base + (i + k) * stride));
+            w = mx_code4_sr<F>(v, sc, r);
+        } else {
+            w = mx_code4<F>(v, sc);
+        }
         if constexpr (QUANT) {
             float r[4];
             mx_value4<F>(w, sc, r);
@@ -264,7 +298,7 @@ __device__ __forceinline__ void plain_block(const typename IN::elem *x, typename
     }
 }
 
-template <int OP, int F, class IN, class OUT>
+template <int OP, int F, class IN, class OUT, bool SR>
 __global__ void __launch_bounds__(kBlock)
 k_mxt_plain(const void *__restrict__ in, void *__restrict__ out, MxtArgs a)
 {
@@ -276,19 +310,20 @@ k_mxt_plain(const void *__restrict__ in, void *__restrict__ out, MxtArgs a)
         const int64_t j = b / a.K, c = b - j * a.K;        // consecutive lanes: consecutive columns
         const int len = (int)(a.R - kMxBlock * j < kMxBlock ? a.R - kMxBlock * j : kMxBlock);
         if constexpr (OP == kOpQuantT) {
-            plain_block<true, F, IN, OUT>(x, static_cast<typename OUT::elem *>(out), kMxBlock * j * a.K + c, a.K, len,
-                                          a.ceil_rule, nullptr, nullptr);
+            plain_block<true, F, IN, OUT, SR>(x, static_cast<typename OUT::elem *>(out), kMxBlock * j * a.K + c, a.K, len,
+                                              a.ceil_rule, nullptr, nullptr, a.sr);
         } else {
-            plain_block<false, F, IN, IoF32>(x, nullptr, kMxBlock * j * a.K + c, a.K, len, a.ceil_rule,
-                                             a.codes_t + c * a.pitch_t + kMxBlock * j * kBits<F> / 8, a.scales_t + c * a.nbR + j);
+            plain_block<false, F, IN, IoF32, SR>(x, nullptr, kMxBlock * j * a.K + c, a.K, len, a.ceil_rule,
+                                                 a.codes_t + c * a.pitch_t + kMxBlock * j * kBits<F> / 8,
+                                                 a.scales_t + c * a.nbR + j, a.sr);
         }
     } else if constexpr (OP == kOpBoth) {
         const int64_t b2 = b - tblocks;
         if (b2 >= a.R * a.nbK) return;
         const int64_t row = b2 / a.nbK, j = b2 - row * a.nbK;
         const int len = (int)(a.K - kMxBlock * j < kMxBlock ? a.K - kMxBlock * j : kMxBlock);
-        plain_block<false, F, IN, IoF32>(x, nullptr, row * a.K + kMxBlock * j, 1, len, a.ceil_rule,
-                                         a.codes + (row * a.K + kMxBlock * j) * kBits<F> / 8, a.scales + b2);
+        plain_block<false, F, IN, IoF32, SR>(x, nullptr, row * a.K + kMxBlock * j, 1, len, a.ceil_rule,
+                                             a.codes + (row * a.K + kMxBlock * j) * kBits<F> / 8, a.scales + b2, a.sr);
     }
 }
 
@@ -322,16 +357,18 @@ int mxt_route(int64_t R, int64_t K, int fmt, int x_type, int aligned16, fp8q_mxt
 }
 
 // Argument checks (everything is reported before the launch, in mx_launch's order and with its codes) and the one launch.
-// x_type / y_type: FP8Q_DT_*; y and y_type are quantize_t's, the four operand pointers the encoders'.
+// x_type / y_type: FP8Q_DT_*; y and y_type are quantize_t's, the four operand pointers the encoders'.  sr: the seed and offset
+// of a stochastic-rounding entry, null for round to nearest even.
 template <int OP>
 int mxt_launch(const void *x, void *y, uint8_t *codes, uint8_t *scales, uint8_t *codes_t, uint8_t *scales_t, int x_type,
-               int y_type, int64_t R, int64_t K, int fmt, int rounding, hipStream_t st)
+               int y_type, int64_t R, int64_t K, int fmt, int rounding, hipStream_t st, const MxSr *sr = nullptr)
 {
     constexpr bool enc = OP != kOpQuantT;
     if (!x || (enc && (!codes_t || !scales_t)) || (OP == kOpBoth && (!codes || !scales)) || (!enc && !y) || R <= 0 || K <= 0)
         return FP8Q_EINVAL;
     if (!fmt_known(fmt)) return FP8Q_EUNSUPPORTED;
     if (rounding != FP8Q_MX_FLOOR && rounding != FP8Q_MX_CEIL) return FP8Q_EINVAL;
+    if (sr && (sr->offset & 7u)) return FP8Q_EINVAL;
     const int bits = fmt_bits(fmt);
     const int64_t mult = bits == 4 ? 2 : (bits == 6 ? 4 : 1);         // elements that share whole bytes
     if (enc && R % mult) return FP8Q_EINVAL;
@@ -362,14 +399,20 @@ int mxt_launch(const void *x, void *y, uint8_t *codes, uint8_t *scales, uint8_t 
     a.tilesC = tilesC;
     a.ceil_rule = rounding == FP8Q_MX_CEIL;
     a.gran = route.code_store_bytes;
+    if (sr) a.sr = *sr;
     const dim3 g((unsigned)grid), b(kBlock);
-    auto go = [&](auto fc, auto in, auto outp) {
+    auto run = [&](auto fc, auto in, auto outp, auto sr_on) {
         constexpr int F = decltype(fc)::value;
+        constexpr bool SR = decltype(sr_on)::value;
         typedef decltype(in) IN;
         typedef decltype(outp) OUT;
-        if (!tile) hipLaunchKernelGGL((k_mxt_plain<OP, F, IN, OUT>), g, b, 0, st, x, y, a);
-        else if (route.nontemporal) hipLaunchKernelGGL((k_mxt<OP, F, IN, OUT, true>), g, b, 0, st, x, y, a);
-        else hipLaunchKernelGGL((k_mxt<OP, F, IN, OUT, false>), g, b, 0, st, x, y, a);
+        if (!tile) hipLaunchKernelGGL((k_mxt_plain<OP, F, IN, OUT, SR>), g, b, 0, st, x, y, a);
+        else if (route.nontemporal) hipLaunchKernelGGL((k_mxt<OP, F, IN, OUT, true, SR>), g, b, 0, st, x, y, a);
+        else hipLaunchKernelGGL((k_mxt<OP, F, IN, OUT, false, SR>), g, b, 0, st, x, y, a);
+    };
+    auto go = [&](auto fc, auto in, auto outp) {
+        if (sr) run(fc, in, outp, std::true_type{});
+        else run(fc, in, outp, std::false_type{});
     };
     dispatch<FP8Q_MX_E4M3FN, FP8Q_MX_E5M2, FP8Q_MX_E2M3, FP8Q_MX_E3M2, FP8Q_MX_E2M1>(fmt, [&](auto fc) {
         value_io(x_type, [&](auto in) {
@@ -435,6 +478,59 @@ int fp8q_mxt_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_
     if (int rc = check_types(x_type, y_type)) return rc;
     return mxt_launch<kOpQuantT>(x, y, nullptr, nullptr, nullptr, nullptr, x_type, y_type, R, K, fmt, rounding,
                                  (hipStream_t)stream);
+}
+
+// ---- stochastic rounding of the elements: the twins of the six launching entries above ----
+int fp8q_mxsr_encode_t_f32(const float *x, uint8_t *codes_t, uint8_t *scales_t, int64_t R, int64_t K, int fmt, int rounding,
+                           uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    const MxSr sr = mx_sr_args(seed, offset);
+    return mxt_launch<kOpT>(x, nullptr, nullptr, nullptr, codes_t, scales_t, FP8Q_DT_F32, -1, R, K, fmt, rounding,
+                            (hipStream_t)stream, &sr);
+}
+
+int fp8q_mxsr_encode_t_h16(const void *x, uint8_t *codes_t, uint8_t *scales_t, int x_type, int64_t R, int64_t K, int fmt,
+                           int rounding, uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    if (!half_type(x_type)) return FP8Q_EINVAL;
+    const MxSr sr = mx_sr_args(seed, offset);
+    return mxt_launch<kOpT>(x, nullptr, nullptr, nullptr, codes_t, scales_t, x_type, -1, R, K, fmt, rounding,
+                            (hipStream_t)stream, &sr);
+}
+
+int fp8q_mxsr_encode_both_f32(const float *x, uint8_t *codes, uint8_t *scales, uint8_t *codes_t, uint8_t *scales_t, int64_t R,
+                              int64_t K, int fmt, int rounding, uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    const MxSr sr = mx_sr_args(seed, offset);
+    return mxt_launch<kOpBoth>(x, nullptr, codes, scales, codes_t, scales_t, FP8Q_DT_F32, -1, R, K, fmt, rounding,
+                               (hipStream_t)stream, &sr);
+}
+
+int fp8q_mxsr_encode_both_h16(const void *x, uint8_t *codes, uint8_t *scales, uint8_t *codes_t, uint8_t *scales_t, int x_type,
+                              int64_t R, int64_t K, int fmt, int rounding, uint64_t seed, uint64_t offset,
+                              fp8q_stream_t stream)
+{
+    if (!half_type(x_type)) return FP8Q_EINVAL;
+    const MxSr sr = mx_sr_args(seed, offset);
+    return mxt_launch<kOpBoth>(x, nullptr, codes, scales, codes_t, scales_t, x_type, -1, R, K, fmt, rounding,
+                               (hipStream_t)stream, &sr);
+}
+
+int fp8q_mxsr_quantize_t_f32(const float *x, float *y, int64_t R, int64_t K, int fmt, int rounding, uint64_t seed,
+                             uint64_t offset, fp8q_stream_t stream)
+{
+    const MxSr sr = mx_sr_args(seed, offset);
+    return mxt_launch<kOpQuantT>(x, y, nullptr, nullptr, nullptr, nullptr, FP8Q_DT_F32, FP8Q_DT_F32, R, K, fmt, rounding,
+                                 (hipStream_t)stream, &sr);
+}
+
+int fp8q_mxsr_quantize_t_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int fmt, int rounding,
+                             uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    if (int rc = check_types(x_type, y_type)) return rc;
+    const MxSr sr = mx_sr_args(seed, offset);
+    return mxt_launch<kOpQuantT>(x, y, nullptr, nullptr, nullptr, nullptr, x_type, y_type, R, K, fmt, rounding,
+                                 (hipStream_t)stream, &sr);
 }
 
 }  // extern "C"

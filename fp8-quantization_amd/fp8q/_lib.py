@@ -8,6 +8,7 @@ from . import build as _build
 _lib = None
 
 _i64 = ctypes.c_int64
+_u64 = ctypes.c_uint64
 _vp = ctypes.c_void_p
 _f = ctypes.c_float
 _i = ctypes.c_int
@@ -164,6 +165,17 @@ SIGNATURES = {
     "fp8q_mxt_encode_both_h16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i, _i, _vp]),
     "fp8q_mxt_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _vp]),
     "fp8q_mxt_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _i, _vp]),
+    # the stochastic-rounding twins: (seed, offset) in front of the stream
+    "fp8q_mxsr_encode_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _u64, _u64, _vp]),
+    "fp8q_mxsr_encode_h16": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _u64, _u64, _vp]),
+    "fp8q_mxsr_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _u64, _u64, _vp]),
+    "fp8q_mxsr_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _i, _u64, _u64, _vp]),
+    "fp8q_mxsr_encode_t_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _u64, _u64, _vp]),
+    "fp8q_mxsr_encode_t_h16": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _u64, _u64, _vp]),
+    "fp8q_mxsr_encode_both_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _u64, _u64, _vp]),
+    "fp8q_mxsr_encode_both_h16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i, _i, _u64, _u64, _vp]),
+    "fp8q_mxsr_quantize_t_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _u64, _u64, _vp]),
+    "fp8q_mxsr_quantize_t_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _i, _u64, _u64, _vp]),
 }
 
 

@@ -1618,6 +1618,25 @@ def _mx_rounding(rounding):
     return _MX_ROUNDING[rounding]
 
 
+def _mx_u64(v, name):
+    if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 1 << 64:
+        raise Fp8qError(f"{name} must be a Python int in [0, 2^64), got {v!r}")
+    return v
+
+
+def _mx_sr(seed, offset):
+    """the trailing arguments of a stochastic-rounding entry, (seed, offset), or () for seed=None: round to nearest even, the
+    entries without them.  Told from the arguments alone, so raised before the device check."""
+    offset = _mx_u64(offset, "offset")
+    if offset % 8:
+        raise Fp8qError(f"offset must be a multiple of 8 (eight elements share one Philox call), got {offset}")
+    if seed is None:
+        if offset:
+            raise Fp8qError(f"offset={offset} without a seed: round to nearest even draws nothing")
+        return ()
+    return (_mx_u64(seed, "seed"), offset)
+
+
 def _mx_geometry(shape, fmt):
     """(lead, R, K, codes shape, scales shape) of values shaped `shape`: blocks run along the last dimension"""
     if len(shape) == 0:
@@ -1648,7 +1667,7 @@ def _mx_bytes(out, shape, dtype, name, like):
     return out.view(torch.uint8)
 
 
-def mx_encode(x, fmt, rounding="floor", out=None, scales_out=None):
+def mx_encode(x, fmt, rounding="floor", out=None, scales_out=None, *, seed=None, offset=0):
     """MX operands of x: (codes, scales).  Blocks of 32 along the last dimension, one E8M0 scale byte each (include/fp8q.h
     states the arithmetic).  fmt: torch.float8_e4m3fn / torch.float8_e5m2 (codes shaped like x) or torch.float4_e2m1fn_x2
     (codes [..., K / 2], the even-indexed element in the low nibble; K must be even) or MX_E2M3 / MX_E3M2, the strings "e2m3" /
@@ -1656,8 +1675,13 @@ def mx_encode(x, fmt, rounding="floor", out=None, scales_out=None):
     in bits [6i, 6i + 6) of its little-endian bit string; K must be a multiple of 4).  scales: torch.float8_e8m0fnu
     [..., ceil(K / 32)].  rounding: "floor" (OCP MX v1.0: the largest elements of a block may saturate) or "ceil" (the smallest
     power of two under which none does).  x float32, or float16 / bfloat16 (widened exactly).  `out` / `scales_out`: contiguous
-    tensors of the result's dtype or uint8.  One launch; the range is found in the same pass."""
+    tensors of the result's dtype or uint8.  One launch; the range is found in the same pass.
+    seed: None rounds the elements to nearest even; a Python int in [0, 2^64) rounds them stochastically (include/fp8q.h: 16
+    bits of Philox4x32-10 per element, drawn by the element's flat index offset + position in x -- so the same (seed, offset)
+    gives the same draw to the same element in every mx_* op, and a slice encoded with the offset of its first element (a
+    multiple of 8) equals the slice of the whole)."""
     f, r = _mx_fmt(fmt), _mx_rounding(rounding)
+    sr = _mx_sr(seed, offset)
     if isinstance(x, torch.Tensor):
         _mx_geometry(x.shape, fmt)      # (argument errors before the device check: they need no GPU to be told)
     _require(x, "x", _VALUES)
@@ -1668,7 +1692,8 @@ def mx_encode(x, fmt, rounding="floor", out=None, scales_out=None):
     scales = _mx_bytes(scales_out, sshape, MX_SCALE_DTYPE, "scales_out", x)
     if x.numel():
         sfx, types = _lane(x.dtype)
-        _run("fp8q_mx_encode" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), *types, R, K, f, r)
+        _run(("fp8q_mxsr_encode" if sr else "fp8q_mx_encode") + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(),
+             *types, R, K, f, r, *sr)
     return codes.view(cdt).view(cshape), scales.view(MX_SCALE_DTYPE).view(sshape)
 
 
@@ -1712,11 +1737,13 @@ def mx_decode(codes, scales, fmt=None, out_dtype=None, out=None):
     return y
 
 
-def mx_quantize(x, fmt, rounding="floor", out_dtype=None, out=None):
+def mx_quantize(x, fmt, rounding="floor", out_dtype=None, out=None, *, seed=None, offset=0):
     """Fake-quantize the way an MX matrix multiplication sees x: mx_decode(*mx_encode(x, fmt, rounding)) bit for bit, in one
     launch, the scales never leaving the registers.  x float32 gives float32; x float16 / bfloat16 gives float32 unless `out`
-    or out_dtype=x.dtype ask for x's own dtype (the float32 result rounded once)."""
+    or out_dtype=x.dtype ask for x's own dtype (the float32 result rounded once).  seed / offset: as in mx_encode, and
+    mx_quantize(x, seed=s) == mx_decode(*mx_encode(x, seed=s)) bit for bit."""
     f, r = _mx_fmt(fmt), _mx_rounding(rounding)
+    sr = _mx_sr(seed, offset)
     if isinstance(x, torch.Tensor):
         _mx_geometry(x.shape, fmt)      # (argument errors before the device check, as in mx_encode)
     _require(x, "x", _VALUES)
@@ -1727,7 +1754,7 @@ def mx_quantize(x, fmt, rounding="floor", out_dtype=None, out=None):
     if x.numel() == 0:
         return y
     sfx, types = _lane(x.dtype, dt)
-    _run("fp8q_mx_quantize" + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, f, r)
+    _run(("fp8q_mxsr_quantize" if sr else "fp8q_mx_quantize") + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, f, r, *sr)
     return y
 
 
@@ -1764,13 +1791,15 @@ def mx_t_route(R, K, fmt, dtype, aligned16=True):
             "nontemporal": bool(info.nontemporal), "code_store_bytes": info.code_store_bytes}
 
 
-def mx_encode_t(x, fmt, rounding="floor", out=None, scales_out=None):
+def mx_encode_t(x, fmt, rounding="floor", out=None, scales_out=None, *, seed=None, offset=0):
     """MX operands of x.t() made from x as it lies: (codes_t, scales_t), byte for byte mx_encode(x.t().contiguous(), fmt,
     rounding) -- blocks of 32 along dim 0 of x, for a product that reduces over it -- in one launch that reads x once and
     makes no transposed copy.  x: 2-D [R, K] (reshape anything else), float32 / float16 / bfloat16.  codes_t: [K, R] (FP8),
     [K, R / 2] (E2M1: rows 2i and 2i + 1 of a column share a byte, R even) or uint8 [K, 3R / 4] ("e2m3" / "e3m2": R a multiple
-    of 4); scales_t: torch.float8_e8m0fnu [K, ceil(R / 32)].  mx_decode(codes_t, scales_t).t() gives the values back."""
+    of 4); scales_t: torch.float8_e8m0fnu [K, ceil(R / 32)].  mx_decode(codes_t, scales_t).t() gives the values back.
+    seed / offset: as in mx_encode; the draws go by the position in x, not in x.t()."""
     f, r = _mx_fmt(fmt), _mx_rounding(rounding)
+    sr = _mx_sr(seed, offset)
     _mx_t_geometry(x, fmt)
     _require(x, "x", _VALUES)
     x = x.detach().contiguous()
@@ -1781,15 +1810,19 @@ def mx_encode_t(x, fmt, rounding="floor", out=None, scales_out=None):
     scales = _mx_bytes(scales_out, sshape, MX_SCALE_DTYPE, "scales_out", x)
     if x.numel():
         sfx, types = _lane(x.dtype)
-        _run("fp8q_mxt_encode" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), *types, R, K, f, r)
+        _run(("fp8q_mxsr_encode_t" if sr else "fp8q_mxt_encode") + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(),
+             *types, R, K, f, r, *sr)
     return codes.view(cdt).view(cshape), scales.view(MX_SCALE_DTYPE).view(sshape)
 
 
-def mx_encode_both(x, fmt, rounding="floor", out=None, scales_out=None, out_t=None, scales_out_t=None):
+def mx_encode_both(x, fmt, rounding="floor", out=None, scales_out=None, out_t=None, scales_out_t=None, *, seed=None,
+                   offset=0):
     """Both orientations of x's MX operands from ONE read of x: (codes, scales, codes_t, scales_t) = mx_encode(x) +
     mx_encode_t(x), byte for byte, in one launch.  x: 2-D; E2M1 needs R and K even, the 6-bit formats multiples of 4.
-    out / scales_out / out_t / scales_out_t: contiguous tensors of the results' dtype or uint8, as in mx_encode."""
+    out / scales_out / out_t / scales_out_t: contiguous tensors of the results' dtype or uint8, as in mx_encode.
+    seed / offset: as in mx_encode; an element has one draw, used by both orientations."""
     f, r = _mx_fmt(fmt), _mx_rounding(rounding)
+    sr = _mx_sr(seed, offset)
     _mx_t_geometry(x, fmt, need_k=True)
     _require(x, "x", _VALUES)
     x = x.detach().contiguous()
@@ -1803,17 +1836,18 @@ def mx_encode_both(x, fmt, rounding="floor", out=None, scales_out=None, out_t=No
     scales_t = _mx_bytes(scales_out_t, stshape, MX_SCALE_DTYPE, "scales_out_t", x)
     if x.numel():
         sfx, types = _lane(x.dtype)
-        _run("fp8q_mxt_encode_both" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), codes_t.data_ptr(),
-             scales_t.data_ptr(), *types, R, K, f, r)
+        _run(("fp8q_mxsr_encode_both" if sr else "fp8q_mxt_encode_both") + sfx, x, x.data_ptr(), codes.data_ptr(),
+             scales.data_ptr(), codes_t.data_ptr(), scales_t.data_ptr(), *types, R, K, f, r, *sr)
     return (codes.view(cdt).view(cshape), scales.view(MX_SCALE_DTYPE).view(sshape),
             codes_t.view(cdt).view(ctshape), scales_t.view(MX_SCALE_DTYPE).view(stshape))
 
 
-def mx_quantize_t(x, fmt, rounding="floor", out_dtype=None, out=None):
+def mx_quantize_t(x, fmt, rounding="floor", out_dtype=None, out=None, *, seed=None, offset=0):
     """Fake-quantize x with the MX blocks along dim 0, in x's own layout: mx_decode(*mx_encode_t(x, fmt, rounding)).t() bit
     for bit, in one launch.  x: 2-D, any R and K -- nothing is packed, so E2M1 and the 6-bit formats need no divisible shape
-    here (mx_encode_t does).  Output dtype as mx_quantize."""
+    here (mx_encode_t does).  Output dtype as mx_quantize.  seed / offset: as in mx_encode_t."""
     f, r = _mx_fmt(fmt), _mx_rounding(rounding)
+    sr = _mx_sr(seed, offset)
     _mx_t_geometry(x, fmt, need_r=False)
     _require(x, "x", _VALUES)
     dt = _quantize_out_dtype(x, out, out_dtype)
@@ -1823,7 +1857,7 @@ def mx_quantize_t(x, fmt, rounding="floor", out_dtype=None, out=None):
     if x.numel() == 0:
         return y
     sfx, types = _lane(x.dtype, dt)
-    _run("fp8q_mxt_quantize" + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, f, r)
+    _run(("fp8q_mxsr_quantize_t" if sr else "fp8q_mxt_quantize") + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, f, r, *sr)
     return y
 
 

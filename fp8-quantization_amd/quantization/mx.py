@@ -15,6 +15,11 @@ tokens -- whose blocks hold other elements than the row-wise ones, so its scales
 the operands of the transpose, [K, R]-shaped, and the tensor must be 2-D after flatten_rows and as divisible along dim 0 as
 the format's packing asks (E2M1: even, the 6-bit formats: a multiple of 4).
 
+stochastic=True rounds the elements stochastically instead of to nearest even (include/fp8q.h: 16 bits of Philox4x32-10 per
+element), which is what the operands of a backward product want: call number n of forward / encode uses the seed
+(seed + n) mod 2^64 and records it as `last_seed`, so that ops.mx_quantize(x, ..., seed=q.last_seed) reproduces the call;
+reseed(seed) starts the count again.
+
 It follows the quantizer protocol (QuantizerBase) and the model zoo takes it as `method=MXQuantizer`; it is deliberately NOT a
 member of QMethods (the CLI's choices).  Forward only: there is no backward kernel, and a call that would need a gradient
 raises NotImplementedError.  There is no CPU path.
@@ -34,7 +39,7 @@ class MXQuantizer(QuantizerBase):
     range_free = True
 
     def __init__(self, n_bits=None, fmt=torch.float8_e4m3fn, rounding="floor", keep_dtype=False, flatten_rows=False,
-                 per_channel=False, scale_domain=None, block_axis=-1, **kwargs):
+                 per_channel=False, scale_domain=None, block_axis=-1, stochastic=False, seed=0, **kwargs):
         if not isinstance(fmt, (torch.dtype, str)) or fmt not in _BITS:
             raise ValueError(f"fmt must be torch.float8_e4m3fn, torch.float8_e5m2, torch.float4_e2m1fn_x2, 'e2m3' or 'e3m2', "
                              f"got {fmt!r}")
@@ -45,6 +50,9 @@ class MXQuantizer(QuantizerBase):
         if block_axis not in (-1, -2) or isinstance(block_axis, bool):
             raise ValueError(f"block_axis must be -1 (blocks along the last dimension) or -2 (along dim 0 of the 2-D view), "
                              f"got {block_axis!r}")
+        if not isinstance(stochastic, bool):
+            raise ValueError(f"stochastic must be True or False, got {stochastic!r}")
+        self._check_seed(seed)
         # per_channel is the protocol's argument; the scales are per block either way
         super().__init__(n_bits=_BITS[fmt], per_channel=per_channel, **kwargs)
         self.fmt = fmt
@@ -53,6 +61,29 @@ class MXQuantizer(QuantizerBase):
         self.keep_dtype = keep_dtype
         self.flatten_rows = flatten_rows
         self.block_axis = block_axis
+        self.stochastic = stochastic
+        self.reseed(seed)
+
+    @staticmethod
+    def _check_seed(seed):
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed must be a Python int in [0, 2^64), got {seed!r}")
+
+    def reseed(self, seed):
+        """start again from `seed`: the next stochastic call uses it, the one after seed + 1, ..."""
+        self._check_seed(seed)
+        self.seed = seed
+        self.calls = 0
+        self.last_seed = None
+
+    def _draw(self):
+        """the keywords this call adds to its op: none unless stochastic, else seed=(seed + calls) mod 2^64, recorded as
+        last_seed"""
+        if not self.stochastic:
+            return {}
+        self.last_seed = (self.seed + self.calls) % (1 << 64)
+        self.calls += 1
+        return {"seed": self.last_seed}
 
     @property
     def is_initialized(self):
@@ -93,9 +124,10 @@ class MXQuantizer(QuantizerBase):
                                       "under torch.no_grad(), or on a detached tensor)")
         out_dtype = x_float.dtype if (self.keep_dtype and x_float.dtype in _HALF) else None
         if self.block_axis == -2:
-            y = _ops.mx_quantize_t(self._matrix(x_float), self.fmt, self.rounding, out_dtype=out_dtype)
+            t, op = self._matrix(x_float), _ops.mx_quantize_t
         else:
-            y = _ops.mx_quantize(self._rows(x_float), self.fmt, self.rounding, out_dtype=out_dtype)
+            t, op = self._rows(x_float), _ops.mx_quantize
+        y = op(t, self.fmt, self.rounding, out_dtype=out_dtype, **self._draw())
         return y.view(x_float.shape)
 
     def encode(self, x_float):
@@ -103,8 +135,10 @@ class MXQuantizer(QuantizerBase):
         [..., 3K / 4] for the 6-bit formats), scales torch.float8_e8m0fnu [..., ceil(K / 32)]; with flatten_rows, of the
         [shape[0], -1] view.  block_axis=-2: the operands of that view's transpose, ops.mx_encode_t's."""
         if self.block_axis == -2:
-            return _ops.mx_encode_t(self._matrix(x_float.detach()), self.fmt, self.rounding)
-        return _ops.mx_encode(self._rows(x_float.detach()), self.fmt, self.rounding)
+            t, op = self._matrix(x_float.detach()), _ops.mx_encode_t
+        else:
+            t, op = self._rows(x_float.detach()), _ops.mx_encode
+        return op(t, self.fmt, self.rounding, **self._draw())
 
     def decode(self, codes, scales, out_dtype=None):
         """Values of encode()'s operands, float32 or out_dtype (float16 / bfloat16: the float32 value rounded once), shaped as
@@ -115,5 +149,6 @@ class MXQuantizer(QuantizerBase):
         return _ops.mx_decode(codes, scales, fmt=self.fmt, out_dtype=out_dtype)
 
     def extra_repr(self):
+        sr = f"stochastic=True, seed={self.seed}, " if self.stochastic else ""
         return f"{super().extra_repr()}, fmt={_NAME[self.fmt]}, rounding={self.rounding}, flatten_rows={self.flatten_rows}, " \
-               f"block_axis={self.block_axis}"
+               f"{sr}block_axis={self.block_axis}"

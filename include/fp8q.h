@@ -1002,6 +1002,67 @@ int fp8q_mxt_quantize_f32(const float *x, float *y, int64_t R, int64_t K, int fm
 int fp8q_mxt_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int fmt, int rounding,
                           fp8q_stream_t stream);
 
+/* ---- microscaling with seeded stochastic rounding of the elements, every orientation ------------------------------------------
+ * (csrc/fp8q_mxq.h, used by csrc/fp8q_mx.hip and csrc/fp8q_mx_t.hip)  Round to nearest even is biased on a gradient at 4 to 8
+ * bits: whatever is smaller than half a grid step disappears, in every block, every step, in the same direction.  These ten
+ * entries are the twins of the MX entries that convert elements, with `uint64_t seed, uint64_t offset` in front of `stream`.
+ * Everything up to q is the MX contract above: the scale byte (either rule, the 0xFF block, code 0) and
+ * q = clamp(x * 2^(127 - code), -fmax, fmax) are unchanged, and a 0xFF block stores what it stores there.  Only
+ *   elem = RNE(q)   becomes   elem = RNE(SR(q, r))
+ * where SR returns a float32 ON the element format's grid, so the conversion after it is exact.
+ *
+ * The draw.  Element i = offset + r * K + c mod 2^64 is the flat index in x AS IT LIES (the transposed entries index by the
+ * position in x, not in x^T); offset must be a multiple of 8.  Element i takes 16 bits of one Philox4x32-10 call:
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (g & 0xffffffff, g >> 32, 0, 0)          g = i >> 3
+ *   w       = out[(i >> 1) & 3]
+ *   r       = (w >> (16 * (i & 1))) & 0xffff
+ * Philox4x32-10 is the standard one: multipliers 0xD2511F53 and 0xCD9E8D57, Weyl constants 0x9E3779B9 and 0xBB67AE85, ten
+ * rounds.  Known answers (counter words, key words -> output words): all zero -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8; all
+ * ffffffff -> 408f276d 41c83b0e a20bc7c6 6d5451fd; 243f6a88 85a308d3 13198a2e 03707344 with key a4093822 299f31d0 ->
+ * d16cfe09 94fdcceb 5001e420 24126ea1.  An aligned group of four flat indices lies in one call (words 0, 1 or 2, 3).  The
+ * draw belongs to the element, not to the kernel: the same (seed, offset) gives the same r for the same element in all ten
+ * entries, so quantize == decode(encode), encode_both == (encode, encode_t), and a slice encoded with the offset of its first
+ * element equals the slice of the whole.
+ *
+ * The rounding.  M mantissa bits and exponent bias B: E4M3FN 3, 7; E5M2 2, 15; E2M3 3, 1; E3M2 2, 3; E2M1 1, 1.
+ * a = bits(|q|).
+ *   normal range, |q| >= 2^(1 - B):  sh = 23 - M, f16 = (a >> (sh - 16)) & 0xffff, a' = (a >> sh) + ((f16 + r) >> 16); the
+ *     magnitude is the float32 with bits a' << sh.  The carry runs into the exponent; fmax is a grid point (f16 = 0), so
+ *     nothing passes it and E4M3FN never reaches 0x7F.
+ *   format-subnormal range, |q| < 2^(1 - B), grid step 2^(1 - B - M):  u = (uint32) floor(|q| * 2^(16 + B + M - 1)), one
+ *     float32 product, below 2^(M + 16); n = (u + r) >> 16; the magnitude is n * 2^(1 - B - M), n = 2^M being the smallest
+ *     normal.
+ *   The sign of q is kept, on a zero result too (the -0 codes).
+ * So P(round away from zero) = floor(f * 2^16) / 2^16 with f the element's position between its two neighbours, grid points
+ * never move, the result is always one of the two neighbours, and the bias toward zero is below 2^-16 of a step.  Half inputs
+ * are widened exactly; half outputs of quantize round the float32 product once, as in the MX entries.
+ *
+ * Errors are the twin's, all reported before the launch; an offset that is no multiple of 8 is FP8Q_EINVAL.  Routes, launch
+ * geometry and traffic are the twin's.  gfx950's own stochastic conversions (v_cvt_scalef32_sr_*) are not used, for the
+ * reason the MX lane gives for the scaled conversions. */
+int fp8q_mxsr_encode_f32(const float *x, uint8_t *codes, uint8_t *scales, int64_t R, int64_t K, int fmt, int rounding,
+                         uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxsr_encode_h16(const void *x, uint8_t *codes, uint8_t *scales, int x_type, int64_t R, int64_t K, int fmt,
+                         int rounding, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxsr_quantize_f32(const float *x, float *y, int64_t R, int64_t K, int fmt, int rounding, uint64_t seed,
+                           uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxsr_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int fmt, int rounding,
+                           uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxsr_encode_t_f32(const float *x, uint8_t *codes_t, uint8_t *scales_t, int64_t R, int64_t K, int fmt, int rounding,
+                           uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxsr_encode_t_h16(const void *x, uint8_t *codes_t, uint8_t *scales_t, int x_type, int64_t R, int64_t K, int fmt,
+                           int rounding, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxsr_encode_both_f32(const float *x, uint8_t *codes, uint8_t *scales, uint8_t *codes_t, uint8_t *scales_t, int64_t R,
+                              int64_t K, int fmt, int rounding, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxsr_encode_both_h16(const void *x, uint8_t *codes, uint8_t *scales, uint8_t *codes_t, uint8_t *scales_t, int x_type,
+                              int64_t R, int64_t K, int fmt, int rounding, uint64_t seed, uint64_t offset,
+                              fp8q_stream_t stream);
+int fp8q_mxsr_quantize_t_f32(const float *x, float *y, int64_t R, int64_t K, int fmt, int rounding, uint64_t seed,
+                             uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxsr_quantize_t_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int fmt, int rounding,
+                             uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
