@@ -272,7 +272,8 @@ struct fp8q_multi_plan {
     std::vector<PlanStep> steps;
 };
 
-static int plan_build(const fp8q_tensor_desc *descs, int n, fp8q_multi_plan &plan, int mode = 0)
+// step_of (optional, [n]): the index in plan.steps each descriptor landed in, -1 for an empty tensor (fp8q_multi_route)
+static int plan_build(const fp8q_tensor_desc *descs, int n, fp8q_multi_plan &plan, int mode = 0, int *step_of = nullptr)
 {
     if (n < 0 || (n > 0 && !descs)) return FP8Q_EINVAL;
     // validate everything first: nothing is built (or enqueued) if any descriptor is bad
@@ -305,6 +306,7 @@ static int plan_build(const fp8q_tensor_desc *descs, int n, fp8q_multi_plan &pla
     };
     for (int i = 0; i < n; ++i) {
         const fp8q_tensor_desc &t = descs[i];
+        if (step_of) step_of[i] = -1;
         if (t.C == 0 || t.inner == 0) continue;
         QFmt f;
         make_fmt(t.mbits, t.n_bits, t.sign_bits, &f);
@@ -329,10 +331,12 @@ static int plan_build(const fp8q_tensor_desc *descs, int n, fp8q_multi_plan &pla
             one.args.total_chunks = 0;
             one.shmem = 0;
             one.single = t;
+            if (step_of) step_of[i] = (int)plan.steps.size();
             plan.steps.push_back(one);
             continue;
         }
         if (cur.args.n == kMultiMax) flush();
+        if (step_of) step_of[i] = (int)plan.steps.size();   // where the next flush() puts `cur`
         MultiDesc &d = cur.args.d[cur.args.n++];
         d.x = t.x;
         d.y = t.y;
@@ -473,6 +477,20 @@ static int multi_minmax_then(const fp8q_tensor_desc *descs, float *const *maxval
     for (int i = 0; i < n; ++i) q[i].maxval = maxval_out[i];
     // same stream: reads the ranges just written
     return mode == 3 ? fp8q_multi_encode_u8(q.data(), n, stream) : fp8q_multi_quantize_f32(q.data(), n, stream);
+}
+
+int fp8q_multi_route(const fp8q_tensor_desc *descs, int n, int mode, int *step_of, int *batched, int *n_steps)
+{
+    if ((mode != 0 && mode != 3 && mode != 4) || !n_steps || (n > 0 && (!step_of || !batched))) return FP8Q_EINVAL;
+    try {
+        fp8q_multi_plan plan;   // the plan the launch would build, not launched
+        if (int rc = plan_build(descs, n, plan, mode, step_of)) return rc;
+        for (int i = 0; i < n; ++i) batched[i] = step_of[i] < 0 ? -1 : (plan.steps[step_of[i]].batched ? 1 : 0);
+        *n_steps = (int)plan.steps.size();
+        return FP8Q_OK;
+    } catch (...) {
+        return (int)hipErrorOutOfMemory;
+    }
 }
 
 int fp8q_multi_plan_create(const fp8q_tensor_desc *descs, int n, fp8q_multi_plan **plan_out)

@@ -111,6 +111,7 @@ SIGNATURES = {
     "fp8q_multi_plan_launch": (_i, [_vp, _vp]),
     "fp8q_multi_plan_launches": (_i, [_vp]),
     "fp8q_multi_plan_destroy": (None, [_vp]),
+    "fp8q_multi_route": (_i, [ctypes.POINTER(TensorDesc), _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "fp8q_copy_f32": (_i, [_vp, _vp, _i64, _vp]),
     "fp8q_int_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i, _i, _f, _vp]),
     "fp8q_int_set_range_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _f, _vp]),

@@ -499,6 +499,28 @@ def multi_decode(items):
     return outs
 
 
+_MULTI_MODES = {"quantize": 0, "encode": 3, "decode": 4}
+
+
+def multi_route(items, mode="quantize"):
+    """Which launch serves each tensor of a multi-tensor call (fp8q_multi_route, include/fp8q.h): host only, nothing is
+    enqueued.  items: the tuples multi_quantize ("quantize": also multi_minmax_quantize and MultiPlan), multi_minmax_encode
+    ("encode") or multi_decode ("decode") take -- pass `out` to have the real output's alignment decide.  Returns
+    [(step, batched), ...] in item order: the launch the tensor lands in and whether that is the batched kernel (1) or
+    the tensor's own single-tensor launch (0); (-1, -1) for an empty tensor."""
+    import ctypes
+    if mode not in _MULTI_MODES:
+        raise Fp8qError(f"multi_route: mode must be one of {sorted(_MULTI_MODES)}, got {mode!r}")
+    items = [tuple(it) for it in items]
+    if not items:
+        return []
+    descs, _, _keep = _pack_descs(items) if mode == "quantize" else _pack_codec_descs(items, mode == "encode")
+    n = len(items)
+    step_of, batched, n_steps = (ctypes.c_int * n)(), (ctypes.c_int * n)(), ctypes.c_int()
+    check(lib().fp8q_multi_route(descs, n, _MULTI_MODES[mode], step_of, batched, ctypes.byref(n_steps)), "fp8q_multi_route")
+    return [(int(s), int(b)) for s, b in zip(step_of, batched)]
+
+
 class MultiPlan:
     """Prepared multi-tensor K1 (fp8q_multi_plan_*): the descriptors of `items` are validated and packed once;
     launch() re-quantizes every tensor into its output with one ctypes call and one kernel launch per 32 tensors.

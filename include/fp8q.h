@@ -493,6 +493,20 @@ int fp8q_multi_plan_launch(const fp8q_multi_plan *plan, fp8q_stream_t stream);
 int fp8q_multi_plan_launches(const fp8q_multi_plan *plan);
 void fp8q_multi_plan_destroy(fp8q_multi_plan *plan);
 
+/*
+ * Which launch serves each tensor of a multi-tensor call -- host only, nothing is enqueued: the plan that
+ * fp8q_multi_quantize_f32 (mode 0), fp8q_multi_encode_u8 (mode 3) or fp8q_multi_decode_u8 (mode 4) would build from these
+ * descriptors (the same function builds it, pointers included: their alignment decides), reported per descriptor.
+ *   step_of  [n] the plan step (launch, in order) the tensor landed in; -1 for an empty tensor, which gets none
+ *   batched  [n] 1: that step is the batched kernel, shared with up to 31 other tensors; 0: the tensor's own single-tensor
+ *            launch (misaligned pointers, fewer than 4 elements, 2^31 elements or more, rows shorter than 4 or longer than
+ *            60000 elements, per-row tables of one 4096-element chunk beyond 36 KiB, 64 MiB or more); -1: empty
+ *   n_steps  launches of the whole call
+ * Errors are the launch's own (FP8Q_EINVAL / FP8Q_EUNSUPPORTED for a bad descriptor); a mode outside {0, 3, 4} or a NULL
+ * output is FP8Q_EINVAL.  The tests assert it before they compare (tests/test_multi_routes.py).
+ */
+int fp8q_multi_route(const fp8q_tensor_desc *descs, int n, int mode, int *step_of, int *batched, int *n_steps);
+
 /* Plain float4 copy kernel with the same launch shape as K1: the measured HBM ceiling that
  * bench.py reports next to the 8 TB/s spec figure. */
 int fp8q_copy_f32(const float *x, float *y, int64_t n, fp8q_stream_t stream);

@@ -128,7 +128,10 @@ R18_SHAPES = [(64, 3, 7, 7)] + [(64, 64, 3, 3)] * 2 + [(128, 64, 3, 3), (128, 64
 def test_hip_multi_tensor_codec_equals_the_single_tensor_entry_points(M, sb):
     """fp8q_multi_minmax_encode_u8 / fp8q_multi_decode_u8 (k_multi_flat<3> / <4>): a model's weight tensors -- odd row
     lengths, rows that straddle 16-byte groups and chunks, ragged tails, > 32 tensors (two launches), a per-tensor range,
-    unaligned views (single-tensor fall-back inside the call) -- bit-identical to minmax + encode / decode per tensor"""
+    unaligned views (single-tensor fall-back inside the call) -- bit-identical to minmax + encode / decode per tensor.
+    The short rows (5,7) and, below M = 5, (16,10) are too short for per-row tables next to a chunk and take the single-tensor
+    fall-back as well; k_multi_flat's in-group row boundary is reached here through the long odd rows only
+    (tests/test_multi_routes.py asserts the routes and reaches it with short rows)."""
     import fp8q
     ops = fp8q.ops
     rng = np.random.RandomState(M * 10 + sb)

@@ -734,7 +734,11 @@ def test_flat_kernel_resident_grid_mid_size(ops, C, inner, M):
 def test_multi_tensor_quantize(ops):
     """fp8q_multi_quantize_f32: every weight tensor of a model in one launch, bit-identical to one
     fp8q_quantize_f32 per tensor (and to the oracle); mixed formats, per-tensor entries, tensors that fall back
-    to their own launch (depthwise 3x3 rows, unaligned views), empty tensors, > 32 tensors."""
+    to their own launch (depthwise 3x3 rows, unaligned views), empty tensors, > 32 tensors.
+    Of the short rows here -- (7,5), the 3x3 depthwise filters, (16, 10 .. 21) -- only those long enough for their format's
+    per-row tables are batched (M = 4 from inner 12, M = 3 from 19, M = 2 from 34; the per-tensor entries always); most take
+    the single-tensor fall-back inside the call.  The batched kernel's short-row branch is reached, with the route asserted,
+    in tests/test_multi_routes.py."""
     rng = np.random.RandomState(5)
     shapes = [(64, 3, 7, 7)] + [(64, 64, 3, 3)] * 4 + [(128, 64, 3, 3), (128, 128, 3, 3), (128, 64, 1, 1)] + \
              [(128, 128, 3, 3)] * 2 + [(256, 128, 3, 3), (256, 256, 3, 3), (256, 128, 1, 1)] + [(256, 256, 3, 3)] * 2 + \
@@ -773,7 +777,10 @@ def test_multi_tensor_quantize(ops):
 def test_multi_tensor_minmax_quantize(ops):
     """fp8q_multi_minmax_quantize_f32: per-channel current_minmax ranges + quantize of a whole model's weight tensors in
     two launches -- ranges and values bit-identical to the oracle and to one fused fp8q_minmax_quantize_f32 per tensor;
-    short / odd / long rows, a zero channel (NaN quirk), a NaN element, an unaligned view, an empty tensor, > 32 tensors."""
+    short / odd / long rows, a zero channel (NaN quirk), a NaN element, an unaligned view, an empty tensor, > 32 tensors.
+    The range launch (k_multi_rowmax) sees every one of these rows; in the quantize launch behind it the short rows -- (7,5),
+    3x3 depthwise, (16, 10 .. 33) below inner 12 / 19 / 34 at M = 4 / 3 / 2 -- take the single-tensor fall-back, not the batched
+    kernel (tests/test_multi_routes.py asserts the routes and reaches its short-row branch)."""
     rng = np.random.RandomState(6)
     shapes = [(64, 3, 7, 7), (64, 64, 3, 3), (128, 64, 1, 1), (512, 512, 3, 3), (1000, 512), (32, 1, 3, 3), (7, 5), (3, 4099),
               (1, 4), (0, 9), (5, 20000), (24, 144, 1, 1)] + [(16, 10 + i) for i in range(24)]
