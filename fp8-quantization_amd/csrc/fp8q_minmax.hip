@@ -155,7 +155,7 @@ struct LinArgs {
 
 static int minmax_impl(const float *x, int64_t C, int64_t inner, float *cur_min, float *cur_max, float *maxval_out,
                        float *packed, int fold_mode, double momentum, int first, void *ws, size_t ws_bytes,
-                       fp8q_stream_t stream, LinArgs lin = LinArgs())
+                       fp8q_stream_t stream, LinArgs lin = LinArgs(), fp8q_rows_route_info *rec = nullptr)
 {
     if (!x || !cur_min || !cur_max || C <= 0 || inner <= 0 || fold_mode < 0 || fold_mode > 2)
         return FP8Q_EINVAL;
@@ -177,23 +177,24 @@ static int minmax_impl(const float *x, int64_t C, int64_t inner, float *cur_min,
     if (lin.grid && C > 65535) return FP8Q_ETOOMANY;
     if (C > 1) {   // per-channel rows of 128..8192 elements: one launch, the row in registers
         QFmt f = {};
-        const int rc = fp8q_launch_rows_reg(false, x, nullptr, C, inner, cur_min, cur_max, maxval_out, f, fa, st);
+        const int rc = fp8q_launch_rows_reg(false, x, nullptr, C, inner, cur_min, cur_max, maxval_out, f, fa, st, rec);
         if (rc != kNotFlat) return rc;
     }
     if (C > 1) {   // short rows: aligned chunks through LDS
-        const int rc = fp8q_launch_rows_staged_mm(x, C, inner, cur_min, cur_max, maxval_out, fa, st);
+        const int rc = fp8q_launch_rows_staged_mm(x, C, inner, cur_min, cur_max, maxval_out, fa, st, rec);
         if (rc != kNotFlat) return rc;
     }
     if (inner <= fp8q_direct_max_inner() && C > 1 && ((uintptr_t)x & 3) == 0) {
         QFmt f = {};
         return fp8q_launch_rows_direct(kModeMinMax, x, nullptr, C, inner, nullptr, cur_min, cur_max, maxval_out,
-                                  f, fa, st);
+                                  f, fa, st, rec);
     }
-    if (ws_bytes < fp8q_minmax_workspace_bytes(C, inner) || !ws || ((uintptr_t)ws & 7)) return FP8Q_EWORKSPACE;
-    if (minmax_debug_ws())
+    // (a route query brings no workspace and takes no tag: everything else below is the launch's own arithmetic)
+    if (!rec && (ws_bytes < fp8q_minmax_workspace_bytes(C, inner) || !ws || ((uintptr_t)ws & 7))) return FP8Q_EWORKSPACE;
+    if (!rec && minmax_debug_ws())
         if (int rc = minmax_ws_check(ws, fp8q_minmax_workspace_bytes(C, inner), 0, st)) return rc;
     const int ns = minmax_nsplit(C, inner);
-    const unsigned tag = next_minmax_tag();
+    const unsigned tag = rec ? 0u : next_minmax_tag();
     const unsigned gx = ns > 1 ? (unsigned)ns + 1u : 1u;   // + the row's reducer block
     fa.status = (unsigned *)ws;
     fold_debug_env(fa);
@@ -201,12 +202,30 @@ static int minmax_impl(const float *x, int64_t C, int64_t inner, float *cur_min,
     for (int64_t c0 = 0; c0 < C; c0 += 65535) {   // ns > 1 implies C <= kTargetBlocks / 2: a single slab
         const int64_t cn = (C - c0) < 65535 ? (C - c0) : 65535;
         fa.packed = packed ? packed + 4 * c0 : nullptr;
-        dispatch<true, false>(C * inner * 4 >= kNtBytes, [&](auto NT) {
-            hipLaunchKernelGGL(k_minmax_partial<NT()>, dim3(gx, (unsigned)cn), dim3(kBlock), 0, st, x + c0 * inner, inner,
-                               ns, slots, tag, cur_min + c0, cur_max + c0, maxval_out ? maxval_out + c0 : nullptr, fa);
+        const bool nt = C * inner * 4 >= kNtBytes;
+        const auto fill = [&](fp8q_rows_route_info &r) {
+            r.kernel = FP8Q_ROWS_K_MINMAX_PARTIAL;
+            r.nontemporal = nt;
+            r.nsplit = ns;
+            r.grid_x = gx;
+            r.grid_y = cn;
+        };
+        const int rc = rows_emit(rec, fill, [&] {
+            dispatch<true, false>(nt, [&](auto NT) {
+                hipLaunchKernelGGL(k_minmax_partial<NT()>, dim3(gx, (unsigned)cn), dim3(kBlock), 0, st, x + c0 * inner, inner,
+                                   ns, slots, tag, cur_min + c0, cur_max + c0, maxval_out ? maxval_out + c0 : nullptr, fa);
+            });
         });
+        if (rc) return rc;
     }
-    return launch_rc();
+    return FP8Q_OK;
+}
+
+// fp8q_minmax_f32's route for fp8q_rows_route: minmax_impl with a record instead of a stream (overwrite fold, no workspace)
+int fp8q_minmax_plan(const float *x, int64_t C, int64_t inner, fp8q_rows_route_info *rec)
+{
+    float *rng = reinterpret_cast<float *>((uintptr_t)1 << 46);
+    return minmax_impl(x, C, inner, rng, rng, rng, nullptr, FP8Q_FOLD_CURRENT, 0.0, 1, nullptr, 0, nullptr, LinArgs(), rec);
 }
 
 int fp8q_minmax_f32(const float *x, int64_t C, int64_t inner, float *cur_min, float *cur_max,

@@ -398,12 +398,18 @@ const char *fp8q_strerror(int code)
 int fp8q_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, const float *maxval,
                       int64_t n_maxval, float mbits, int n_bits, int sign_bits, fp8q_stream_t stream)
 {
+    return fp8q_quantize_plan(x, y, C, inner, maxval, n_maxval, mbits, n_bits, sign_bits, (hipStream_t)stream, nullptr);
+}
+
+// fp8q_quantize_f32 itself; rec: record the route instead of launching (rows_emit, fp8q_rows.h)
+int fp8q_quantize_plan(const float *x, float *y, int64_t C, int64_t inner, const float *maxval, int64_t n_maxval,
+                       float mbits, int n_bits, int sign_bits, hipStream_t st, fp8q_rows_route_info *rec)
+{
     if (C < 0 || inner < 0 || (n_maxval != 1 && n_maxval != C)) return FP8Q_EINVAL;
     QFmt f;
     if (int rc = make_fmt(mbits, n_bits, sign_bits, &f)) return rc;
     if (C == 0 || inner == 0) return FP8Q_OK;   // empty tensor: nothing to do (pointers may be null)
     if (!x || !y || !maxval) return FP8Q_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
     const int per_channel = n_maxval != 1;
     if (!per_channel) {  // one row
         inner *= C;
@@ -414,14 +420,14 @@ int fp8q_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, const 
     if (per_channel && inner <= fp8q_direct_max_inner() && ((uintptr_t)x & 3) == 0 && ((uintptr_t)y & 3) == 0) {
         // short rows: G lanes per row, tables in LDS
         const FoldArgs nofold = {0, 1, 0.0f, 0.0f};
-        return fp8q_launch_rows_direct(kModeQuant, x, y, C, inner, maxval, nullptr, nullptr, nullptr, f, nofold, st);
+        return fp8q_launch_rows_direct(kModeQuant, x, y, C, inner, maxval, nullptr, nullptr, nullptr, f, nofold, st, rec);
     }
     if (C > 65535) {
         // very many long rows: one launch per 65535 rows (gridDim.y limit)
         for (int64_t c0 = 0; c0 < C; c0 += 65535) {
             const int64_t cn = (C - c0) < 65535 ? (C - c0) : 65535;
-            int rc = fp8q_quantize_f32(x + c0 * inner, y + c0 * inner, cn, inner, maxval + c0, cn,
-                                       mbits, n_bits, sign_bits, stream);
+            int rc = fp8q_quantize_plan(x + c0 * inner, y + c0 * inner, cn, inner, maxval + c0, cn,
+                                        mbits, n_bits, sign_bits, st, rec);
             if (rc) return rc;
         }
         return FP8Q_OK;
@@ -435,15 +441,54 @@ int fp8q_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, const 
     const RowGrid g = row_grid(C, inner, small_elems, [](bool nt, int64_t pieces) {
         return k1_blocks_env > 0 ? (int64_t)k1_blocks_env : k1_total_cap(nt, pieces);
     });
-    if (aligned) {
-        dispatch_k1(g, [&](auto NT, auto U) {
-            hipLaunchKernelGGL((k_quant_rows<NT(), U()>), dim3((unsigned)g.bx, (unsigned)C), dim3(kBlock), 0, st, x, y, inner,
-                               maxval, per_channel, f);
-        });
+    const auto fill = [&](fp8q_rows_route_info &r) {
+        r.kernel = aligned ? FP8Q_ROWS_K_QUANT_ROWS : FP8Q_ROWS_K_QUANT_SCALAR;
+        r.nontemporal = aligned && g.nt;      // (the scalar fallback has one instance)
+        r.small = aligned && !g.nt && g.small;
+        r.grid_x = aligned ? g.bx : g.bs;
+        r.grid_y = C;
+    };
+    return rows_emit(rec, fill, [&] {
+        if (aligned) {
+            dispatch_k1(g, [&](auto NT, auto U) {
+                hipLaunchKernelGGL((k_quant_rows<NT(), U()>), dim3((unsigned)g.bx, (unsigned)C), dim3(kBlock), 0, st, x, y, inner,
+                                   maxval, per_channel, f);
+            });
+        } else {
+            hipLaunchKernelGGL(k_quant_scalar, dim3((unsigned)g.bs, (unsigned)C), dim3(kBlock), 0, st, x, y, inner, maxval, per_channel, f);
+        }
+    });
+}
+
+// Which kernel of the row family a call of the three entries reaches: the entries' own code behind their argument checks
+// (fp8q_quantize_plan, fp8q_minmax_quantize_plan, fp8q_minmax_plan) run with a record instead of a stream, on made-up
+// addresses that have the caller's 16-byte phases and are never dereferenced.  Host arithmetic only.
+int fp8q_rows_route(int op, int64_t C, int64_t inner, int per_channel, float mbits, int n_bits, int sign_bits, int x_mod16,
+                    int y_mod16, int in_place, fp8q_rows_route_info *info)
+{
+    if (!info || op < FP8Q_ROWS_QUANTIZE || op > FP8Q_ROWS_MINMAX_QUANTIZE || C < 0 || inner < 0) return FP8Q_EINVAL;
+    if (x_mod16 < 0 || x_mod16 > 15 || y_mod16 < 0 || y_mod16 > 15) return FP8Q_EINVAL;
+    if (in_place && op != FP8Q_ROWS_MINMAX && y_mod16 != x_mod16) return FP8Q_EINVAL;
+    // far apart, far from null, and far from wrapping at any tensor the entries take
+    const float *x = reinterpret_cast<const float *>(((uintptr_t)1 << 44) + (uintptr_t)x_mod16);
+    float *y = in_place ? const_cast<float *>(x) : reinterpret_cast<float *>(((uintptr_t)1 << 45) + (uintptr_t)y_mod16);
+    float *rng = reinterpret_cast<float *>((uintptr_t)1 << 46);
+    fp8q_rows_route_info r = {};
+    r.kernel = -1;      // an empty tensor: nothing is launched
+    int rc;
+    if (op == FP8Q_ROWS_QUANTIZE) {
+        rc = fp8q_quantize_plan(x, y, C, inner, rng, per_channel ? C : 1, mbits, n_bits, sign_bits, nullptr, &r);
+    } else if (op == FP8Q_ROWS_MINMAX_QUANTIZE) {
+        rc = fp8q_minmax_quantize_plan(x, y, C, inner, rng, rng, rng, mbits, n_bits, sign_bits, nullptr, &r);
     } else {
-        hipLaunchKernelGGL(k_quant_scalar, dim3((unsigned)g.bs, (unsigned)C), dim3(kBlock), 0, st, x, y, inner, maxval, per_channel, f);
+        if (!per_channel) {   // the wrapper's view of a per-tensor estimator: one row
+            inner *= C;
+            C = C > 0 ? 1 : 0;
+        }
+        rc = fp8q_minmax_plan(x, C, inner, &r);
     }
-    return launch_rc();
+    if (rc == FP8Q_OK) *info = r;
+    return rc;
 }
 
 }  // extern "C"

@@ -96,17 +96,40 @@ inline FlatArgs flat_geometry(int64_t C, int64_t inner, int lut_stride)
     return a;
 }
 
+// The one launch site of a row launcher.  Every launcher of the family runs its geometry block and its dispatch down to this
+// call whoever asks: with rec == nullptr `launch` enqueues the kernel, otherwise `fill` writes the choices just made into
+// *rec (fp8q_rows_route: the first launch describes the call, `launches` counts the slabs) and nothing touches the device --
+// the pointers of a query are made-up addresses with the caller's 16-byte phases.
+template <class Fill, class Launch>
+inline int rows_emit(fp8q_rows_route_info *rec, Fill &&fill, Launch &&launch)
+{
+    if (rec) {
+        if (rec->launches++ == 0) fill(*rec);
+        return FP8Q_OK;
+    }
+    launch();
+    return launch_rc();
+}
+
 }  // namespace
 
 // The short-row launchers called from other units of the library: hidden, not part of the C ABI.  (C linkage because
 // FoldArgs has internal linkage -- every unit has its own copy of fp8q_common.h -- which a C++ signature would inherit.)
-// Each returns kNotFlat when the shape does not suit its kernel.
+// Each returns kNotFlat when the shape does not suit its kernel.  rec: record the route instead of launching (rows_emit).
 #define FP8Q_HIDDEN extern "C" __attribute__((visibility("hidden")))
 FP8Q_HIDDEN int64_t fp8q_direct_max_inner();
 FP8Q_HIDDEN int fp8q_launch_rows_direct(int mode, const float *x, float *y, int64_t C, int64_t inner, const float *maxval,
                                    float *row_min, float *row_max, float *maxval_out, const QFmt &f, const FoldArgs &fa,
-                                   hipStream_t st);
+                                   hipStream_t st, fp8q_rows_route_info *rec);
 FP8Q_HIDDEN int fp8q_launch_rows_reg(bool quant, const float *x, float *y, int64_t C, int64_t inner, float *row_min, float *row_max,
-                                float *maxval_out, const QFmt &f, const FoldArgs &fa, hipStream_t st);
+                                float *maxval_out, const QFmt &f, const FoldArgs &fa, hipStream_t st, fp8q_rows_route_info *rec);
 FP8Q_HIDDEN int fp8q_launch_rows_staged_mm(const float *x, int64_t C, int64_t inner, float *row_min, float *row_max,
-                                      float *maxval_out, const FoldArgs &fa, hipStream_t st);
+                                      float *maxval_out, const FoldArgs &fa, hipStream_t st, fp8q_rows_route_info *rec);
+// The three entries behind their argument checks (fp8q_quantize_f32, fp8q_minmax_quantize_f32, fp8q_minmax_f32 and its
+// packed / linspace variants): what fp8q_rows_route runs with rec set.
+FP8Q_HIDDEN int fp8q_quantize_plan(const float *x, float *y, int64_t C, int64_t inner, const float *maxval, int64_t n_maxval,
+                              float mbits, int n_bits, int sign_bits, hipStream_t st, fp8q_rows_route_info *rec);
+FP8Q_HIDDEN int fp8q_minmax_quantize_plan(const float *x, float *y, int64_t C, int64_t inner, float *row_min, float *row_max,
+                                     float *maxval_out, float mbits, int n_bits, int sign_bits, hipStream_t st,
+                                     fp8q_rows_route_info *rec);
+FP8Q_HIDDEN int fp8q_minmax_plan(const float *x, int64_t C, int64_t inner, fp8q_rows_route_info *rec);

@@ -790,7 +790,8 @@ static size_t flat_shmem(const FlatArgs &a, int64_t per_row) { return (size_t)kF
 // Launch k_rows_flat if the problem fits it; returns kNotFlat when the caller must use k_rows_direct
 // (pointers not 16-byte aligned, rows too short for per-row tables in LDS, in-place fused, ...).
 static int launch_rows_flat(int mode, const float *x, float *y, int64_t C, int64_t inner, const float *maxval,
-                            float *row_min, float *row_max, float *maxval_out, const QFmt &f, hipStream_t st)
+                            float *row_min, float *row_max, float *maxval_out, const QFmt &f, hipStream_t st,
+                            fp8q_rows_route_info *rec)
 {
     static const int flat_env = env_int("FP8Q_FLAT", 1);   // FP8Q_FLAT=0: round-1 row-tiled kernel everywhere (A/B)
     if (!flat_env || mode == kModeMinMax || inner < 4) return kNotFlat;
@@ -828,11 +829,20 @@ static int launch_rows_flat(int mode, const float *x, float *y, int64_t C, int64
             a.group = gs;   // log2(lanes per row) here
             a.nch = 1;
             const int64_t blocks = staged_grid ? balanced_blocks(a.nchunks, staged_grid) : a.nchunks;
-            dispatch<true, false>(nt, [&](auto NT) {
-                hipLaunchKernelGGL((k_rows_staged<NT()>), dim3((unsigned)blocks), dim3(kBlock), sh, st, x, y, row_min, row_max,
-                                   maxval_out, f, a);
+            const auto fill = [&](fp8q_rows_route_info &r) {
+                r.kernel = FP8Q_ROWS_K_ROWS_STAGED;
+                r.nontemporal = nt;
+                r.group = 1 << gs;
+                r.nch = 1;
+                r.grid_x = blocks;
+                r.grid_y = 1;
+            };
+            return rows_emit(rec, fill, [&] {
+                dispatch<true, false>(nt, [&](auto NT) {
+                    hipLaunchKernelGGL((k_rows_staged<NT()>), dim3((unsigned)blocks), dim3(kBlock), sh, st, x, y, row_min, row_max,
+                                       maxval_out, f, a);
+                });
             });
-            return launch_rc();
         }
     }
     a.nch = (int)nch;
@@ -849,13 +859,22 @@ static int launch_rows_flat(int mode, const float *x, float *y, int64_t C, int64
     int64_t blocks = cdiv(a.nchunks, a.nch);
     const int64_t grid_cap = grid_env ? grid_env : ((mode == kModeQuant && a.nchunks <= 16384) ? 1024 : 32768);
     if (blocks > grid_cap) blocks = grid_cap;
-    dispatch<kModeQuant, kModeFused>(mode, [&](auto MODE) {
-        dispatch<true, false>(nt, [&](auto NT) {
-            hipLaunchKernelGGL((k_rows_flat<MODE(), NT()>), dim3((unsigned)blocks), dim3(kBlock), flat_shmem(a, per_row), st, x, y,
-                               maxval, row_min, row_max, maxval_out, f, a);
+    const auto fill = [&](fp8q_rows_route_info &r) {
+        r.kernel = FP8Q_ROWS_K_ROWS_FLAT;
+        r.nontemporal = nt;
+        r.group = G;
+        r.nch = a.nch;
+        r.grid_x = blocks;
+        r.grid_y = 1;
+    };
+    return rows_emit(rec, fill, [&] {
+        dispatch<kModeQuant, kModeFused>(mode, [&](auto MODE) {
+            dispatch<true, false>(nt, [&](auto NT) {
+                hipLaunchKernelGGL((k_rows_flat<MODE(), NT()>), dim3((unsigned)blocks), dim3(kBlock), flat_shmem(a, per_row), st, x, y,
+                                   maxval, row_min, row_max, maxval_out, f, a);
+            });
         });
     });
-    return launch_rc();
 }
 
 // Storage codes of per-channel tensors with short rows through k_rows_flat (aligned 16 KiB chunks of the fp32 side,
@@ -892,7 +911,7 @@ __attribute__((visibility("hidden"))) int fp8q_codec_flat_launch(bool encode, co
 
 // k_rows_staged_mm for [C, inner]: rows of 4..256 elements, x 16-byte aligned; kNotFlat otherwise
 int fp8q_launch_rows_staged_mm(const float *x, int64_t C, int64_t inner, float *row_min, float *row_max, float *maxval_out,
-                          const FoldArgs &fa, hipStream_t st)
+                          const FoldArgs &fa, hipStream_t st, fp8q_rows_route_info *rec)
 {
     static const int staged_env = env_int("FP8Q_STAGED", 1);   // FP8Q_STAGED=0: row-tiled k_rows_direct<2> (A/B)
     if (!staged_env || inner < 4 || inner > kFlatFusedMaxInner || ((uintptr_t)x & 15) != 0) return kNotFlat;
@@ -903,20 +922,30 @@ int fp8q_launch_rows_staged_mm(const float *x, int64_t C, int64_t inner, float *
     // persistent-grid cap; 0 = one chunk per block (measured best: no stores to wait for)
     static const int grid_env = env_int("FP8Q_STAGED_MM_GRID", 0, 0);
     const int64_t blocks = grid_env ? balanced_blocks(a.nchunks, grid_env) : a.nchunks;
-    dispatch<true, false>(C * inner * 4 >= kNtBytes, [&](auto NT) {
-        hipLaunchKernelGGL((k_rows_staged_mm<NT()>), dim3((unsigned)blocks), dim3(kBlock), 0, st, x, row_min, row_max, maxval_out,
-                           fa, a);
+    const bool nt = C * inner * 4 >= kNtBytes;
+    const auto fill = [&](fp8q_rows_route_info &r) {
+        r.kernel = FP8Q_ROWS_K_ROWS_STAGED_MM;
+        r.nontemporal = nt;
+        r.group = 1 << gs;
+        r.nch = 1;
+        r.grid_x = blocks;
+        r.grid_y = 1;
+    };
+    return rows_emit(rec, fill, [&] {
+        dispatch<true, false>(nt, [&](auto NT) {
+            hipLaunchKernelGGL((k_rows_staged_mm<NT()>), dim3((unsigned)blocks), dim3(kBlock), 0, st, x, row_min, row_max, maxval_out,
+                               fa, a);
+        });
     });
-    return launch_rc();
 }
 
 // Launch k_rows_direct for [C, inner], inner <= kDirectMaxInner (any 4-byte aligned pointers).
 int fp8q_launch_rows_direct(int mode, const float *x, float *y, int64_t C, int64_t inner, const float *maxval,
                        float *row_min, float *row_max, float *maxval_out, const QFmt &f,
-                       const FoldArgs &fa, hipStream_t st)
+                       const FoldArgs &fa, hipStream_t st, fp8q_rows_route_info *rec)
 {
     {
-        const int rc = launch_rows_flat(mode, x, y, C, inner, maxval, row_min, row_max, maxval_out, f, st);
+        const int rc = launch_rows_flat(mode, x, y, C, inner, maxval, row_min, row_max, maxval_out, f, st, rec);
         if (rc != kNotFlat) return rc;
     }
     TileArgs a = {};
@@ -969,14 +998,24 @@ int fp8q_launch_rows_direct(int mode, const float *x, float *y, int64_t C, int64
         hipLaunchKernelGGL((k_rows_direct<MODE(), LUT(), NT()>), g, b, shmem, st, x, y, C, maxval, row_min, row_max,
                            maxval_out, f, a, fa);
     };
-    if (mode == kModeMinMax) {   // no tables, no stores: one instantiation
-        launch(Const<kModeMinMax>{}, Const<false>{}, Const<false>{});
-    } else {
-        dispatch<kModeQuant, kModeFused>(mode, [&](auto MODE) {
-            dispatch<true, false>(lut, [&](auto LUT) { dispatch<true, false>(nt, [&](auto NT) { launch(MODE, LUT, NT); }); });
-        });
-    }
-    return launch_rc();
+    const auto fill = [&](fp8q_rows_route_info &r) {
+        r.kernel = FP8Q_ROWS_K_ROWS_DIRECT;
+        r.nontemporal = mode != kModeMinMax && nt;      // (min/max has one instance)
+        r.lut = lut;
+        r.group = G;
+        r.rows_per_block = (int)R;
+        r.grid_x = blocks;
+        r.grid_y = 1;
+    };
+    return rows_emit(rec, fill, [&] {
+        if (mode == kModeMinMax) {   // no tables, no stores: one instantiation
+            launch(Const<kModeMinMax>{}, Const<false>{}, Const<false>{});
+        } else {
+            dispatch<kModeQuant, kModeFused>(mode, [&](auto MODE) {
+                dispatch<true, false>(lut, [&](auto LUT) { dispatch<true, false>(nt, [&](auto NT) { launch(MODE, LUT, NT); }); });
+            });
+        }
+    });
 }
 
 extern "C" {
@@ -987,6 +1026,15 @@ int fp8q_minmax_quantize_f32(const float *x, float *y, int64_t C, int64_t inner,
                              float *row_max, float *maxval_out, float mbits, int n_bits,
                              int sign_bits, fp8q_stream_t stream)
 {
+    return fp8q_minmax_quantize_plan(x, y, C, inner, row_min, row_max, maxval_out, mbits, n_bits, sign_bits, (hipStream_t)stream,
+                                     nullptr);
+}
+
+// fp8q_minmax_quantize_f32 itself; rec: record the route instead of launching (rows_emit, fp8q_rows.h)
+int fp8q_minmax_quantize_plan(const float *x, float *y, int64_t C, int64_t inner, float *row_min, float *row_max,
+                              float *maxval_out, float mbits, int n_bits, int sign_bits, hipStream_t st,
+                              fp8q_rows_route_info *rec)
+{
     if (C < 0 || inner < 0) return FP8Q_EINVAL;
     QFmt f;
     if (int rc = make_fmt(mbits, n_bits, sign_bits, &f)) return rc;
@@ -994,19 +1042,28 @@ int fp8q_minmax_quantize_f32(const float *x, float *y, int64_t C, int64_t inner,
     if (!x || !y) return FP8Q_EINVAL;
     if (inner > kDirectMaxInner) return FP8Q_ETOOLONG;
     if (((uintptr_t)x & 3) != 0 || ((uintptr_t)y & 3) != 0) return FP8Q_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
     static const bool small_fused = env_int("FP8Q_SMALL_FUSED", 1) != 0;   // =0: the general routes for small tensors too (A/B)
     const FoldArgs nofold = {0, 1, 0.0f, 0.0f};
     if (small_fused && C * inner <= kSmallFusedElems && inner <= kSmallFusedInner) {
-        dispatch<1, 2, 3, 4, 8>((int)cdiv(inner, 64), [&](auto EPL) {   // elements per lane: 5..8 take 8
-            hipLaunchKernelGGL(k_small_rows_fused<EPL()>, dim3((unsigned)cdiv(C, kBlock / 64)), dim3(kBlock), 0, st, x, y, C,
-                               (int)inner, row_min, row_max, maxval_out, f);
+        int epl = 0;
+        dispatch<1, 2, 3, 4, 8>((int)cdiv(inner, 64), [&](auto EPL) { epl = EPL(); });   // elements per lane: 5..8 take 8
+        const auto fill = [&](fp8q_rows_route_info &r) {
+            r.kernel = FP8Q_ROWS_K_SMALL_ROWS_FUSED;
+            r.lanes = 64;
+            r.slots = epl;
+            r.grid_x = cdiv(C, kBlock / 64);
+            r.grid_y = 1;
+        };
+        return rows_emit(rec, fill, [&] {
+            dispatch<1, 2, 3, 4, 8>(epl, [&](auto EPL) {
+                hipLaunchKernelGGL(k_small_rows_fused<EPL()>, dim3((unsigned)cdiv(C, kBlock / 64)), dim3(kBlock), 0, st, x, y, C,
+                                   (int)inner, row_min, row_max, maxval_out, f);
+            });
         });
-        return launch_rc();
     }
-    const int rc = fp8q_launch_rows_reg(true, x, y, C, inner, row_min, row_max, maxval_out, f, nofold, st);
+    const int rc = fp8q_launch_rows_reg(true, x, y, C, inner, row_min, row_max, maxval_out, f, nofold, st, rec);
     if (rc != kNotFlat) return rc;
-    return fp8q_launch_rows_direct(kModeFused, x, y, C, inner, nullptr, row_min, row_max, maxval_out, f, nofold, st);
+    return fp8q_launch_rows_direct(kModeFused, x, y, C, inner, nullptr, row_min, row_max, maxval_out, f, nofold, st, rec);
 }
 
 }  // extern "C"

@@ -121,7 +121,7 @@ k_rows_reg(const float *__restrict__ x, float *__restrict__ y, int64_t C, int in
 // k_rows_reg for [C, inner] if the rows suit it (128..8192 elements, a multiple of 4, 16-byte aligned, lanes well
 // filled); kNotFlat otherwise.  quant: fused min/max + quantize; else K2 (min/max + fold).
 int fp8q_launch_rows_reg(bool quant, const float *x, float *y, int64_t C, int64_t inner, float *row_min, float *row_max,
-                    float *maxval_out, const QFmt &f, const FoldArgs &fa, hipStream_t st)
+                    float *maxval_out, const QFmt &f, const FoldArgs &fa, hipStream_t st, fp8q_rows_route_info *rec)
 {
     static const int reg_env = env_int("FP8Q_FUSED_REG", 1);   // FP8Q_FUSED_REG=0: never (A/B against the row-tiled kernels)
     if (!reg_env || inner > 8192) return kNotFlat;
@@ -146,15 +146,24 @@ int fp8q_launch_rows_reg(bool quant, const float *x, float *y, int64_t C, int64_
     const bool nt = C * inner * 4 >= kNtBytes;
     const int64_t steps = cdiv(C, kBlock / reg_lanes);
     const int64_t grid = balanced_blocks(steps, 65536);
-    dispatch<16, 32, 64, 256>(reg_lanes, [&](auto LN) {
-        dispatch<2, 3, 4, 5, 6, 7, 8>(reg_ept, [&](auto E) {
-            dispatch<true, false>(nt, [&](auto NT) {
-                dispatch<true, false>(quant, [&](auto QUANT) {
-                    hipLaunchKernelGGL((k_rows_reg<LN(), E(), NT(), QUANT()>), dim3((unsigned)grid), dim3(kBlock), 0, st, x, y, C,
-                                       (int)inner, row_min, row_max, maxval_out, f, fa);
+    const auto fill = [&](fp8q_rows_route_info &r) {
+        r.kernel = FP8Q_ROWS_K_ROWS_REG;
+        r.nontemporal = nt;
+        r.lanes = reg_lanes;
+        r.slots = reg_ept;
+        r.grid_x = grid;
+        r.grid_y = 1;
+    };
+    return rows_emit(rec, fill, [&] {
+        dispatch<16, 32, 64, 256>(reg_lanes, [&](auto LN) {
+            dispatch<2, 3, 4, 5, 6, 7, 8>(reg_ept, [&](auto E) {
+                dispatch<true, false>(nt, [&](auto NT) {
+                    dispatch<true, false>(quant, [&](auto QUANT) {
+                        hipLaunchKernelGGL((k_rows_reg<LN(), E(), NT(), QUANT()>), dim3((unsigned)grid), dim3(kBlock), 0, st, x, y, C,
+                                           (int)inner, row_min, row_max, maxval_out, f, fa);
+                    });
                 });
             });
         });
     });
-    return launch_rc();
 }

@@ -37,6 +37,13 @@ class AffineRouteInfo(ctypes.Structure):
     _fields_ = [("kernel", _i), ("direct", _i), ("cpp", _i), ("launches", _i), ("grid_x", _i64), ("grid_y", _i64)]
 
 
+class RowsRouteInfo(ctypes.Structure):
+    """fp8q_rows_route_info (include/fp8q.h): the row kernel a quantize / min-max / fused call reaches and its launcher's choices"""
+    _fields_ = [("kernel", _i), ("nontemporal", _i), ("small", _i), ("lut", _i), ("lanes", _i), ("slots", _i), ("group", _i),
+                ("nch", _i), ("rows_per_block", _i), ("nsplit", _i), ("launches", _i), ("reserved", _i), ("grid_x", _i64),
+                ("grid_y", _i64)]
+
+
 class MxtRouteInfo(ctypes.Structure):
     """fp8q_mxt_route_info (include/fp8q.h): the kernel a transposed-MX call reaches and its tile"""
     _fields_ = [("kernel", _i), ("tile_rows", _i), ("tile_cols", _i), ("nontemporal", _i), ("code_store_bytes", _i),
@@ -62,6 +69,7 @@ SIGNATURES = {
     "fp8q_minmax_workspace_check": (_i, [_vp, ctypes.c_size_t, _i, _vp]),
     "fp8q_fused_max_inner": (_i64, []),
     "fp8q_minmax_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _f, _i, _i, _vp]),
+    "fp8q_rows_route": (_i, [_i, _i64, _i64, _i, _f, _i, _i, _i, _i, _i, ctypes.POINTER(RowsRouteInfo)]),
     "fp8q_mse_workspace_bytes": (ctypes.c_size_t, [_i64, _i64, _i64, _i]),
     "fp8q_mse_grid_f32": (_i, [_vp, _i64, _i64, _vp, _i64, ctypes.POINTER(_f), _i, _i, _i, _vp, _vp,
                                ctypes.c_size_t, _vp]),

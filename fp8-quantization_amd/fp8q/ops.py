@@ -701,6 +701,30 @@ def fused_max_inner():
     return int(lib().fp8q_fused_max_inner())
 
 
+ROWS_OPS = ("quantize", "minmax", "minmax_quantize")                 # FP8Q_ROWS_* (include/fp8q.h)
+ROWS_KERNELS = ("k_quant_rows", "k_quant_scalar", "k_rows_flat", "k_rows_direct", "k_rows_reg", "k_rows_staged",
+                "k_rows_staged_mm", "k_small_rows_fused", "k_minmax_partial")      # FP8Q_ROWS_K_*
+
+
+def rows_route(op, C, inner, per_channel=True, mbits=2, n_bits=8, sign_bits=1, x_mod16=0, y_mod16=0, in_place=False):
+    """The row kernel quantize / minmax / minmax_quantize (op, one of ROWS_OPS) reach for a [C, inner] float32 tensor of this
+    format whose x and y sit at these addresses modulo 16 (fp8q_rows_route, include/fp8q.h), as a dict: kernel (a name of
+    ROWS_KERNELS; None when nothing is launched), nontemporal, small, lut (bools), lanes, slots, group, nch, rows_per_block,
+    nsplit, launches, grid_x, grid_y (of the first launch); what does not apply to the kernel is 0.  in_place: y is x.
+    Host arithmetic only: needs no GPU.  Raises Fp8qError as the op's entry would for the shape."""
+    import ctypes
+    from ._lib import RowsRouteInfo
+    info = RowsRouteInfo()
+    check(lib().fp8q_rows_route(ROWS_OPS.index(op), int(C), int(inner), int(bool(per_channel)), float(mbits), int(n_bits),
+                                int(sign_bits), int(x_mod16), int(x_mod16 if in_place else y_mod16), int(bool(in_place)),
+                                ctypes.byref(info)), "fp8q_rows_route")
+    r = {name: int(getattr(info, name)) for name, _ in RowsRouteInfo._fields_ if name != "reserved"}
+    r["kernel"] = ROWS_KERNELS[info.kernel] if info.kernel >= 0 else None
+    for name in ("nontemporal", "small", "lut"):
+        r[name] = bool(r[name])
+    return r
+
+
 _pct_ws_bytes = {}
 
 

@@ -140,6 +140,62 @@ int fp8q_minmax_quantize_f32(const float *x, float *y, int64_t C, int64_t inner,
                              int sign_bits, fp8q_stream_t stream);
 
 /*
+ * Which kernel of the row family the three entries above launch: fp8q_quantize_f32 (FP8Q_ROWS_QUANTIZE), fp8q_minmax_f32 with
+ * its packed / linspace variants (FP8Q_ROWS_MINMAX) and fp8q_minmax_quantize_f32 (FP8Q_ROWS_MINMAX_QUANTIZE), for a [C, inner]
+ * tensor of a format, at the process's settings (the FP8Q_* tuning variables as the launchers read them).  Host arithmetic
+ * only: no launch, no device -- the entries' own code behind their argument checks, every launcher's geometry block and
+ * dispatch included, with a callback that records instead of launching, so that a test can assert the route before it trusts a
+ * shape.  per_channel: one range per row (n_maxval == C), else one for the tensor (the entries then see one row of C * inner
+ * elements; the fused entry is per channel always).  x_mod16 / y_mod16: the addresses of x and y modulo 16 (y is ignored for
+ * min/max); in_place: y == x (then y_mod16 must equal x_mod16).
+ *   kernel          FP8Q_ROWS_K_* below; -1 with launches == 0 for an empty tensor
+ *   nontemporal     the instance for tensors of 64 MiB and more (k_quant_scalar and the min/max k_rows_direct have one instance)
+ *   small           k_quant_rows: the U = 1 pieces (4 KiB per block) of a cache-sized per-tensor row
+ *   lut             k_rows_direct: per-row {s, 1/s} tables in LDS (rows of at least 2 * (pmax + 1) elements), else the exact scale
+ *   lanes, slots    k_rows_reg: lanes per row (16, 32, 64, 256) and 16-byte groups per lane (2..8); k_small_rows_fused: 64
+ *                   lanes and the elements per lane of its instance (1, 2, 3, 4, 8)
+ *   group           lanes per row of k_rows_flat's first pass and of k_rows_direct (1..64), of k_rows_staged and of
+ *                   k_rows_staged_mm (1..8 both: a chunk overlaps at least 18 rows of the at most 256 elements they take)
+ *   nch             chunks of 4096 elements per tile: k_rows_flat 1..4, the staged kernels 1
+ *   rows_per_block  k_rows_direct: R, the rows of one tile
+ *   nsplit          k_minmax_partial: streaming blocks per row (grid_x has the reducer block on top when nsplit > 1)
+ *   grid_x, grid_y  of the first launch
+ *   launches        one per slab of 65535 rows (k_quant_rows / k_quant_scalar / k_minmax_partial), 1 elsewhere
+ * Fields that do not apply to the kernel are 0.  Errors as the entry reports them for the shape: FP8Q_EINVAL (a negative size,
+ * an address that is not a multiple of 4 in the fused entry, C * inner == 0 for min/max, op or a phase out of range, info
+ * NULL), FP8Q_EUNSUPPORTED (the format), FP8Q_ETOOLONG (fused rows beyond fp8q_fused_max_inner()); `info` is written on
+ * FP8Q_OK only.
+ */
+#define FP8Q_ROWS_QUANTIZE 0
+#define FP8Q_ROWS_MINMAX 1
+#define FP8Q_ROWS_MINMAX_QUANTIZE 2
+#define FP8Q_ROWS_K_QUANT_ROWS 0       /* k_quant_rows: one row per blockIdx.y, 16-byte groups */
+#define FP8Q_ROWS_K_QUANT_SCALAR 1     /* k_quant_scalar: x and y not 16-byte co-aligned */
+#define FP8Q_ROWS_K_ROWS_FLAT 2        /* k_rows_flat: aligned 4096-element chunks, per-row tables in LDS; K1 or fused two-pass */
+#define FP8Q_ROWS_K_ROWS_DIRECT 3      /* k_rows_direct: row tiles; K1, fused or min/max */
+#define FP8Q_ROWS_K_ROWS_REG 4         /* k_rows_reg: the row in registers; fused or min/max */
+#define FP8Q_ROWS_K_ROWS_STAGED 5      /* k_rows_staged: fused, the chunk parked in LDS */
+#define FP8Q_ROWS_K_ROWS_STAGED_MM 6   /* k_rows_staged_mm: its min/max twin */
+#define FP8Q_ROWS_K_SMALL_ROWS_FUSED 7 /* k_small_rows_fused: a wave per row, tensors up to 16384 elements */
+#define FP8Q_ROWS_K_MINMAX_PARTIAL 8   /* k_minmax_partial: long rows, per tensor */
+typedef struct fp8q_rows_route_info {
+    int kernel;
+    int nontemporal;
+    int small;
+    int lut;
+    int lanes, slots;
+    int group;
+    int nch;
+    int rows_per_block;
+    int nsplit;
+    int launches;
+    int reserved;
+    int64_t grid_x, grid_y;
+} fp8q_rows_route_info;
+int fp8q_rows_route(int op, int64_t C, int64_t inner, int per_channel, float mbits, int n_bits, int sign_bits, int x_mod16,
+                    int y_mod16, int in_place, fp8q_rows_route_info *info);
+
+/*
  * K4 -- FP-MSE grid search accumulation.
  * Replaces the double loop of FP_MSE_Estimator.forward, quantization/range_estimators.py:337-347
  * (111 * |mbits| full quantizer passes -> one pass over x).

@@ -87,6 +87,21 @@ int main()
     int ok = 1;
     printf("libfp8q version %d\n", fp8q_version());
 
+    {   // the route query of the row kernels: host arithmetic, from the phases of the pointers the calls below pass
+        fp8q_rows_route_info ri;
+        const int xp = (int)((uintptr_t)dx & 15), yp = (int)((uintptr_t)dy & 15);
+        CK(fp8q_rows_route(FP8Q_ROWS_QUANTIZE, C, inner, 1, 2.0f, 8, 1, xp, yp, 0, &ri));
+        int good = ri.kernel == FP8Q_ROWS_K_ROWS_FLAT && !ri.nontemporal && ri.nch >= 1 && ri.launches == 1;
+        CK(fp8q_rows_route(FP8Q_ROWS_MINMAX_QUANTIZE, C, inner, 1, 2.0f, 8, 1, xp, yp, 0, &ri));
+        good &= ri.kernel == FP8Q_ROWS_K_ROWS_STAGED && ri.grid_x == (n / 4 + 1023) / 1024;
+        CK(fp8q_rows_route(FP8Q_ROWS_MINMAX, C, inner, 0, 2.0f, 8, 1, xp, 0, 0, &ri));
+        good &= ri.kernel == FP8Q_ROWS_K_MINMAX_PARTIAL && ri.nsplit >= 1 && ri.grid_y == 1;
+        good &= fp8q_rows_route(FP8Q_ROWS_MINMAX_QUANTIZE, C, fp8q_fused_max_inner() + 1, 1, 2.0f, 8, 1, 0, 0, 0, &ri) == FP8Q_ETOOLONG;
+        good &= fp8q_rows_route(FP8Q_ROWS_QUANTIZE, C, inner, 1, 0.0f, 16, 1, 0, 0, 0, &ri) == FP8Q_EUNSUPPORTED;
+        good &= fp8q_rows_route(7, C, inner, 1, 2.0f, 8, 1, 0, 0, 0, &ri) == FP8Q_EINVAL;
+        printf(good ? "ok   fp8q_rows_route (k_rows_flat, k_rows_staged, k_minmax_partial; error codes)\n" : "FAIL fp8q_rows_route\n");
+        ok &= good;
+    }
     for (int M = 2; M <= 4; ++M) {   // K1, per-channel fixed ranges
         CK(fp8q_quantize_f32(dx, dy, C, inner, dmv, C, (float)M, 8, 1, st));
         CK(hipStreamSynchronize(st));

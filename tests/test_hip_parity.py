@@ -332,15 +332,33 @@ def test_minmax_fold_modes_and_nan(ops, golden_dir):
     np.testing.assert_array_equal(mn.cpu().numpy()[[0, 2]], rmn[[0, 2]])
 
 
+def route(ops, op, t, M=2, sign=1, out=None, per_channel=True):
+    """ops.rows_route for the call about to be made on the tensor t (the phases of its real pointers)"""
+    C = t.shape[0]
+    return ops.rows_route(op, C, t.numel() // C, per_channel, M, 8, sign, x_mod16=t.data_ptr() % 16,
+                          y_mod16=(out.data_ptr() % 16) if out is not None else 0,
+                          in_place=out is not None and out.data_ptr() == t.data_ptr())
+
+
+SMALL, REG, STAGED, DIRECT, FLAT = "k_small_rows_fused", "k_rows_reg", "k_rows_staged", "k_rows_direct", "k_rows_flat"
+
+
 @pytest.mark.parametrize("shape", [(64, 3, 7, 7), (32, 1, 3, 3), (1000, 512), (512, 512, 3, 3), (7, 5),
                                    (3, 4099), (5, 16384), (130, 66), (2048, 3, 7, 7)])
 @pytest.mark.parametrize("M", [2, 3])
 def test_fused_minmax_quantize_bit_exact(ops, shape, M):
+    """(64,3,7,7), (32,1,3,3), (7,5) and (130,66) are tensors of at most 16384 elements: k_small_rows_fused; (1000,512) and
+    (512,4608) k_rows_reg; (3,4099) and (5,16384) k_rows_direct; (2048,147) k_rows_staged"""
+    inner = int(np.prod(shape[1:]))
+    want = {(64, 147): SMALL, (32, 9): SMALL, (7, 5): SMALL, (130, 66): SMALL, (1000, 512): REG, (512, 4608): REG,
+            (3, 4099): DIRECT, (5, 16384): DIRECT, (2048, 147): STAGED}[(shape[0], inner)]
     rng = np.random.RandomState(shape[0] + M)
     x = (rng.randn(*shape) * 0.1).astype(np.float32)
     if shape[0] > 4:
         x[2] = 0  # all-zero channel -> NaN channel
-    y, mn, mx, mv = ops.minmax_quantize(dev(x), M, 8, 1)
+    xd = dev(x)
+    assert route(ops, "minmax_quantize", xd, M, out=torch.empty_like(xd))["kernel"] == want
+    y, mn, mx, mv = ops.minmax_quantize(xd, M, 8, 1)
     rmn, rmx = oracle.c_minmax(x, True)
     rmv = oracle.c_absmax(rmn, rmx)
     np.testing.assert_array_equal(mn.cpu().numpy(), rmn)
@@ -365,7 +383,11 @@ def test_small_tensor_fused_route_bit_exact(ops, shape, M, sign):
         flat[4, 0] = -0.0
         flat[5] = np.abs(flat[5])          # one-sided row
         flat[6] = 1e-41                    # denormals only
-    y, mn, mx, mv = ops.minmax_quantize(dev(x), M, 8, sign)
+    xd = dev(x)
+    r = route(ops, "minmax_quantize", xd, M, sign, out=torch.empty_like(xd))
+    epl = -(-flat.shape[1] // 64)
+    assert (r["kernel"], r["slots"]) == ("k_small_rows_fused", epl if epl <= 4 else 8), r
+    y, mn, mx, mv = ops.minmax_quantize(xd, M, 8, sign)
     rmn, rmx = oracle.c_minmax(x, True)
     rmv = oracle.c_absmax(rmn, rmx)
     for got, ref, what in ((mn, rmn, "min"), (mx, rmx, "max"), (mv, rmv, "maxval")):
@@ -542,13 +564,27 @@ def test_per_channel_constants_fast_vs_libm(ops):
 
 @pytest.mark.parametrize("C,inner", [(1, 4), (3, 5), (1, 4097), (2, 2049), (29, 147), (57, 147), (4096, 4), (700, 21),
                                      (333, 36), (1000, 147), (9, 1023), (17, 1024), (5, 1025), (7, 2047),
-                                     (4, 1536), (100, 576), (31, 333)])
+                                     (4, 1536), (100, 576), (31, 333), (120, 147), (260, 64)])
 @pytest.mark.parametrize("M", [2, 3, 4])
 def test_flat_short_row_kernel_geometries(ops, C, inner, M):
     """k_rows_flat / k_rows_staged cut the tensor into aligned 4096-element chunks regardless of the rows: chunk borders
     inside rows, rows longer than a chunk, a partial last chunk, <= 3 tail scalars (C*inner % 4 != 0),
     16-byte groups that straddle two rows (inner % 4 != 0).  K1 (also in place) and the fused
-    min/max + quantize, bit-exact against the oracle."""
+    min/max + quantize, bit-exact against the oracle.
+
+    Which kernel each call reaches is asserted (ops.rows_route).  K1 is k_rows_flat from (29,147) on, except rows too short
+    for per-row tables -- (3,5), (4096,4), and (700,21) with E5M2's 33 entries: k_rows_direct -- and the rows of 2048 elements
+    and more, or the single row of (1,4): k_quant_rows.  The FUSED call reaches the chunk kernels at (1000,147), (120,147)
+    (k_rows_staged) and (260,64) (two-pass k_rows_flat with E5M2's tables, k_rows_staged with the smaller ones) only: the
+    eight tensors of at most 16384 elements with rows up to 512 -- (1,4), (3,5), (29,147), (57,147), (4096,4), (700,21),
+    (333,36), (31,333) -- take k_small_rows_fused, in place too; rows of a multiple of 4 from 128 on k_rows_reg; the rest, and
+    every in-place call above 16384 elements that k_rows_reg does not take, the row-tiled k_rows_direct."""
+    k1 = "k_quant_rows" if inner >= 2048 or C == 1 else "k_rows_direct" if inner < 8 or (inner == 21 and M == 2) else "k_rows_flat"
+    fused = {(1, 4): SMALL, (3, 5): SMALL, (29, 147): SMALL, (57, 147): SMALL, (4096, 4): SMALL, (700, 21): SMALL, (333, 36): SMALL,
+             (31, 333): SMALL, (1, 4097): DIRECT, (2, 2049): DIRECT, (9, 1023): DIRECT, (5, 1025): DIRECT, (7, 2047): DIRECT,
+             (17, 1024): REG, (4, 1536): REG, (100, 576): REG, (1000, 147): STAGED, (120, 147): STAGED,
+             (260, 64): FLAT if M == 2 else STAGED}[(C, inner)]
+    fused_ip = "k_rows_direct" if fused in ("k_rows_staged", "k_rows_flat") else fused
     rng = np.random.RandomState(C * 7 + inner + M)
     x = (rng.randn(C, inner) * np.exp(rng.uniform(-3, 3, (C, 1)))).astype(np.float32)
     x.reshape(-1)[:: 97] = 0.0
@@ -556,6 +592,11 @@ def test_flat_short_row_kernel_geometries(ops, C, inner, M):
     mv = oracle.c_absmax(mn, mx)
     ref = oracle.c_quantize(x, mv, M, 8, 1)
     xd = dev(x)
+    other = torch.empty_like(xd)
+    assert route(ops, "quantize", xd, M, out=other)["kernel"] == k1
+    assert route(ops, "quantize", xd, M, out=xd)["kernel"] == k1
+    assert route(ops, "minmax_quantize", xd, M, out=other)["kernel"] == fused
+    assert route(ops, "minmax_quantize", xd, M, out=xd)["kernel"] == fused_ip
     assert_bit_exact(ops.quantize(xd, dev(mv), M, 8, 1).cpu().numpy(), ref, f"K1 {C}x{inner} M={M}")
     y, gmn, gmx, gmv = ops.minmax_quantize(xd, M, 8, 1)
     np.testing.assert_array_equal(gmn.cpu().numpy(), mn)
@@ -566,7 +607,7 @@ def test_flat_short_row_kernel_geometries(ops, C, inner, M):
     ops.quantize(xi, dev(mv), M, 8, 1, out=xi)                 # in place
     assert_bit_exact(xi.cpu().numpy(), ref, f"K1 in place {C}x{inner} M={M}")
     xi = xd.clone()
-    ops.minmax_quantize(xi, M, 8, 1, out=xi)                   # in place: row-tiled kernel (rows owned whole)
+    ops.minmax_quantize(xi, M, 8, 1, out=xi)                   # in place: never a chunk kernel (rows owned whole)
     assert_bit_exact(xi.cpu().numpy(), ref, f"fused in place {C}x{inner} M={M}")
 
 
@@ -585,7 +626,10 @@ def test_staged_fused_short_rows_many_chunks(ops, C, inner, M):
     mn, mx = oracle.c_minmax(x, True)
     mv = oracle.c_absmax(mn, mx)
     ref = oracle.c_quantize(x, mv, M, 8, 1)
-    y, gmn, gmx, gmv = ops.minmax_quantize(dev(x), M, 8, 1)
+    xd = dev(x)
+    r = route(ops, "minmax_quantize", xd, M, out=torch.empty_like(xd))
+    assert r["kernel"] == "k_rows_staged" and r["grid_x"] < -(-(C * inner // 4) // 1024), r      # fewer blocks than chunks
+    y, gmn, gmx, gmv = ops.minmax_quantize(xd, M, 8, 1)
     np.testing.assert_array_equal(gmn.cpu().numpy(), mn)
     np.testing.assert_array_equal(gmx.cpu().numpy(), mx)
     np.testing.assert_array_equal(gmv.cpu().numpy(), mv)
@@ -593,16 +637,22 @@ def test_staged_fused_short_rows_many_chunks(ops, C, inner, M):
 
 
 @pytest.mark.parametrize("C,inner", [(2, 147), (29, 147), (70001, 147), (333, 255), (7001, 99), (50021, 41), (100003, 9),
-                                     (40000, 5), (77777, 4), (5, 250), (300007, 27), (28, 256)])
+                                     (40000, 5), (77777, 4), (5, 250), (300007, 27), (28, 256), (120, 147), (90, 131)])
 def test_staged_minmax_short_rows(ops, C, inner):
     """k_rows_staged_mm (per-channel min/max of rows <= 256 elements through aligned chunks parked in LDS): rows cut by
     chunk borders, several rows-per-pass geometries (1..8 lanes per row), tail scalars, NaN rows; overwrite, all-min/max
-    and EMA folds into a running estimate.  Equal to the oracle bit for bit."""
+    and EMA folds into a running estimate.  Equal to the oracle bit for bit.  (333,255), (5,250) and (28,256) are rows the
+    in-register kernel fills well and takes first: k_rows_reg; (120,147) and (90,131) are rows above 128 elements that it
+    fills badly and leaves to k_rows_staged_mm.)"""
     rng = np.random.RandomState(C % 977 + inner)
     x = rng.randn(C, inner).astype(np.float32)
     x[C // 2, inner // 2] = np.nan
     x[0] = 0.0
     rmn, rmx = oracle.c_minmax(x, True)
+    r = route(ops, "minmax", dev(x))
+    assert r["kernel"] == ("k_rows_reg" if inner >= 250 else "k_rows_staged_mm"), r
+    if r["kernel"] == "k_rows_staged_mm":
+        assert r["group"] == {147: 8, 131: 4, 99: 4, 41: 2}.get(inner, 1), r
     mn, mx, mv = ops.minmax(dev(x), True, want_maxval=True)
     np.testing.assert_array_equal(mn.cpu().numpy(), rmn)
     np.testing.assert_array_equal(mx.cpu().numpy(), rmx)
@@ -619,12 +669,17 @@ def test_staged_minmax_short_rows(ops, C, inner):
 
 @pytest.mark.parametrize("C,inner", [(9, 512), (33, 1024), (7, 1152), (5, 2048), (6, 2052), (3, 4608), (5, 8192),
                                      (2, 8196), (13, 576), (4, 260), (1, 1024), (257, 1280), (50, 128), (35, 192),
-                                     (19, 288), (70, 384), (3, 7168), (17, 124)])
+                                     (19, 288), (70, 384), (3, 7168), (17, 124), (33, 512), (64, 260), (130, 128), (90, 192),
+                                     (60, 288)])
 @pytest.mark.parametrize("M", [2, 4])
 def test_fused_rows_in_registers(ops, C, inner, M):
-    """k_rows_reg (rows of 257..8192 elements held in registers between the min/max and the quantize pass): one
+    """k_rows_reg (rows of 128..8192 elements held in registers between the min/max and the quantize pass): one
     wave per row and one block per row, full and partly filled lanes, rows that fall back to the row-tiled
-    kernel, NaN / all-zero rows, in place; bit-exact against the oracle."""
+    kernel ((6,2052), (2,8196)), NaN / all-zero rows, in place; bit-exact against the oracle.  Six shapes are tensors of at
+    most 16384 elements with rows up to 512 and take k_small_rows_fused instead -- (9,512), (4,260), (50,128), (35,192),
+    (19,288), (17,124); (33,512), (64,260), (130,128), (90,192), (60,288) are their rows in tensors above that limit."""
+    want = {(9, 512): SMALL, (4, 260): SMALL, (50, 128): SMALL, (35, 192): SMALL, (19, 288): SMALL, (17, 124): SMALL,
+            (6, 2052): DIRECT, (2, 8196): DIRECT}.get((C, inner), REG)
     rng = np.random.RandomState(C + inner + M)
     x = (rng.randn(C, inner) * np.exp(rng.uniform(-3, 3, (C, 1)))).astype(np.float32)
     if C > 2:
@@ -634,6 +689,12 @@ def test_fused_rows_in_registers(ops, C, inner, M):
     mv = oracle.c_absmax(mn, mx)
     ref = oracle.c_quantize(x, mv, M, 8, 1)
     xd = dev(x)
+    for out in (torch.empty_like(xd), xd):
+        r = route(ops, "minmax_quantize", xd, M, out=out)
+        assert r["kernel"] == want, r
+        if want == "k_rows_reg":
+            lanes = {512: 16, 260: 16, 128: 16, 192: 16, 288: 16, 384: 16, 576: 32, 1024: 32, 1152: 64, 1280: 64, 2048: 64}.get(inner, 256)
+            assert (r["lanes"], r["slots"]) == (lanes, -(-(inner // 4) // lanes)), r
     y, gmn, gmx, gmv = ops.minmax_quantize(xd, M, 8, 1)
     np.testing.assert_array_equal(gmn.cpu().numpy(), mn)
     np.testing.assert_array_equal(gmx.cpu().numpy(), mx)
@@ -653,6 +714,8 @@ def test_minmax_with_an_empty_split(ops, C, inner):
     for x in (np.abs(rng.randn(C, inner)).astype(np.float32) + 0.5, -np.abs(rng.randn(C, inner)).astype(np.float32) - 0.5,
               rng.randn(C, inner).astype(np.float32)):
         for pc in (True, False):
+            r = route(ops, "minmax", dev(x) if pc else dev(x).view(1, -1), per_channel=True)
+            assert r["kernel"] == "k_minmax_partial" and r["nsplit"] > 1, r          # a reducer block and several splits
             mn, mx = ops.minmax(dev(x), pc)
             rmn, rmx = oracle.c_minmax(x, pc)
             np.testing.assert_array_equal(mn.cpu().numpy(), rmn)
@@ -715,9 +778,14 @@ def test_fuzz_geometries_against_oracle(ops):
 @pytest.mark.parametrize("C,inner,M", [(1 << 17, 147, 2), (1 << 18, 147, 3), (30000, 1152, 2), (100000, 576, 2), (70001, 99, 3)])
 def test_flat_kernel_resident_grid_mid_size(ops, C, inner, M):
     """Cache-sized per-channel tensors (1024 < tiles, <= 16384 chunks) run k_rows_flat on a RESIDENT grid of 1024 blocks
-    that stride over the chunks (several tiles per block): every row band of the result against the oracle."""
+    that stride over the chunks (several tiles per block): every row band of the result against the oracle.  (The first four
+    tensors are 64 MiB and more: the nontemporal instance, four chunks per tile; (70001,99) the cached one, one per tile.)"""
     g = torch.Generator(device="cuda").manual_seed(C + inner)
     x = torch.randn(C, inner, device="cuda", generator=g) * (torch.rand(C, 1, device="cuda", generator=g) * 2 + 0.05)
+    r = route(ops, "quantize", x, M, out=torch.empty_like(x))
+    tiles = -(-(-(-(C * inner // 4) // 1024)) // r["nch"])
+    assert (r["kernel"], r["grid_x"]) == ("k_rows_flat", 1024) and tiles > 1024, r
+    assert (r["nontemporal"], r["nch"]) == ((True, 4) if C * inner * 4 >= (64 << 20) else (False, 1)), r
     mv = ops.minmax(x, True, want_maxval=True)[2]
     y = ops.quantize(x, mv, M, 8, 1)
     mvh = mv.cpu().numpy()

@@ -39,6 +39,23 @@ route with a row length that is no multiple of 4 AND a channel count that does n
   launch_codec_flat  k_rows_flat<En/Decode>    test_hip_codec_short_row_geometries stays below    no                    not in this
                                                64 MiB ((70001, 147) = 41 MB)                                            issue's list
 
+What ops.rows_route (fp8q_rows_route: the launchers' own decision code) shows of the row kernels' nontemporal instances, and
+which the cases here now assert before they compare (kernel, nontemporal, and the launcher's choices):
+  k_rows_flat<Quant, true>       test_fp32_rows_flat: resident grid of 1024 blocks, 2 and 4 chunks per tile; also the first four
+                                 shapes of test_hip_parity.py::test_flat_kernel_resident_grid_mid_size (77 MB and more)
+  k_rows_staged<true>            test_hip_parity.py::test_staged_fused_short_rows_many_chunks (route asserted there)
+  k_rows_flat<Fused, true>       was reached by nothing: the two-pass fused kernel needs rows of at most 256 elements whose staged
+                                 window plus tables exceed 36 KiB -- 129-entry tables (seven exponent bits) or, with E5M2, rows
+                                 of about 64 elements and fewer -- in a tensor of 64 MiB.  Added: test_fp32_fused_rows_flat
+                                 [275037, 61].  Its cached instance: tests/test_rows_routes_gpu.py
+  k_rows_staged_mm<true>, k_rows_reg<.., true, quant and K2>, k_rows_direct<Fused, lut, true>, k_minmax_partial<true>,
+  k_quant_rows<true, 4> per channel and per tensor: test_fp32_fused_rows, test_fp32_per_tensor (asserted)
+  k_rows_direct<Quant, .., true>, k_rows_direct<Fused, no tables, true>: reached by nothing above 64 MiB (rows shorter than
+                                 2 * (pmax + 1) elements, or pointers off a 16-byte boundary, at that size)
+  the slab loop of k_quant_rows (C > 65535 rows of 2048 elements and more: at least 0.5 GB): reached by nothing;
+                                 test_more_than_2_31_elements has two rows.  The query reports its launches by arithmetic
+                                 (tests/test_rows_routes_host.py)
+
 Also seen while auditing: tests/test_h16_kernels.py::test_streaming_sizes already crosses the half lane's threshold with
 [228263, 147] (quantize only), and tests/test_int_kernels.py::test_bulk_tensor crosses the INT lane's with [2^21, 3, 7, 7]
 (int_quantize, 8 bits); the cases below add the other ops, widths and shapes of those lanes.
@@ -597,7 +614,7 @@ def test_fp32_per_tensor(offset_out):
     """fp8q_quantize_f32, C == 1, nt.  n = 4097 pieces + 1029 elements (67.1 MB): pieces * C = 4097 > 4096 -> one 16 KiB
     piece per block (cap 65536, grid 4097); k_quant_rows<true, 4>: the partial last piece (257 groups + 1 scalar) has no block
     of its own.  offset_out: out= starts one element behind a 16-byte boundary, x on one -> not co-aligned ->
-    k_quant_scalar with the large regime's block cap (bs = min(cdiv(n, 256), 4 * 65536) = 65558 blocks)."""
+    k_quant_scalar with the large regime's block cap (bs = min(cdiv(n, 256), 4 * 65536) = 65557 blocks)."""
     ops = _ops()
     n = 4097 * 4096 + 1029
     _guard(n * 4)
@@ -609,12 +626,22 @@ def test_fp32_per_tensor(offset_out):
     if offset_out:
         out = torch.full((n + 1,), float("nan"), device="cuda")[1:]
         assert x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 4
+    r = _route(ops, "quantize", x, 3, out, per_channel=False)
+    assert (r["kernel"], r["nontemporal"]) == (("k_quant_scalar", False) if offset_out else ("k_quant_rows", True)), r
+    assert r["grid_x"] == (65557 if offset_out else 4097), r
     y = ops.quantize(x, mvd, 3, 8, 1, out=out)
     _check(y, want, "quantize vs oracle")
     del y, out
     sl = _row_slice((n,))
     outs = torch.full((sl.stop - sl.start + 1,), float("nan"), device="cuda")[1:] if offset_out else _out(x[sl])
     _check(ops.quantize(_below(x[sl]), mvd, 3, 8, 1, out=outs), want[sl], "slice through the small regime")
+
+
+def _route(ops, op, x, M, out=None, per_channel=True):
+    """ops.rows_route for the call about to be made on x: kernel and launcher choices from the real pointers' phases"""
+    C = x.shape[0] if per_channel and x.dim() > 1 else 1
+    return ops.rows_route(op, C, x.numel() // C, per_channel, M, 8, 1, x_mod16=x.data_ptr() % 16,
+                          y_mod16=(out.data_ptr() % 16) if out is not None else 0)
 
 
 def _rows_case(inner, seed, special):
@@ -635,9 +662,41 @@ def test_fp32_rows_flat(inner):
     mv = _row_ranges(C, inner)
     mvd = torch.from_numpy(mv).cuda()
     want = torch.from_numpy(oracle.c_quantize(_np(x), mv, 2, 8, 1))                    # E5M2
-    _check(ops.quantize(x, mvd, 2, 8, 1, out=_out(x)), want, "quantize vs oracle")
+    out = _out(x)
+    r = _route(ops, "quantize", x, 2, out)
+    assert (r["kernel"], r["nontemporal"], r["grid_x"], r["nch"]) == ("k_rows_flat", True, 1024, 2 if inner == 99 else 4), r
+    _check(ops.quantize(x, mvd, 2, 8, 1, out=out), want, "quantize vs oracle")
+    del out
     sl = _row_slice((C, inner))
     _check(ops.quantize(_below(x[sl]), mvd[sl], 2, 8, 1, out=_out(x[sl])), want[sl], "slice through the small regime")
+
+
+def test_fp32_fused_rows_flat():
+    """fp8q_minmax_quantize_f32 just above 64 MiB on rows too short for k_rows_staged: [275037, 61] (67.1 MB), E5M2.  68 table
+    rows per chunk x (33 entries + constants) next to the 18 KiB window exceed the 36 KiB a staged block may take ->
+    launch_rows_flat's two-pass k_rows_flat<kModeFused, true>: 4097 chunks, one per tile and block (the fused grid is not
+    the resident one), 4 lanes per row in the range pass, the last chunk ragged with one tail scalar; rows of 61 elements start
+    at every 4-byte phase, so nearly every row has a head patch."""
+    ops = _ops()
+    inner = 61
+    C, x = _rows_case(inner, 54, False)
+    xh = _np(x)
+    rmn, rmx = oracle.c_minmax(xh, True)
+    rmv = oracle.c_absmax(rmn, rmx)
+    want = torch.from_numpy(oracle.c_quantize(xh, rmv, 2, 8, 1))                       # E5M2
+    del xh
+    out = _out(x)
+    r = _route(ops, "minmax_quantize", x, 2, out)
+    assert (r["kernel"], r["nontemporal"], r["nch"], r["group"], r["grid_x"]) == ("k_rows_flat", True, 1, 4, 4097), r
+    y, mn, mx, mv = ops.minmax_quantize(x, 2, 8, 1, out=out)
+    for g, ref, name in ((mn, rmn, "min"), (mx, rmx, "max"), (mv, rmv, "maxval")):
+        _check(g, ref, f"minmax_quantize row {name} vs oracle")
+    _check(y, want, "minmax_quantize vs oracle")
+    del y, out
+    sl = _row_slice((C, inner))
+    ys, _, _, mvs = ops.minmax_quantize(_below(x[sl]), 2, 8, 1, out=_out(x[sl]))
+    _check(ys, want[sl], "slice through the small regime")
+    _check(mvs, rmv[sl], "maxval of a slice through the small regime")
 
 
 @pytest.mark.parametrize("inner", [388, 201, 8197])
@@ -650,7 +709,7 @@ def test_fp32_fused_rows(inner):
         is k_rows_staged<true>, which test_hip_parity.py::test_staged_fused_short_rows_many_chunks covers above 64 MiB.)
     [2047, 8197] (67.1 MB): > 8192 -> not rows_reg, > 256 -> not flat -> k_rows_direct<kModeFused, true, true>; min/max
         alone: > 2047 -> k_minmax_partial<true>, one block per row; quantize with those ranges: > 2047 -> k_quant_rows<true, 4>
-        per channel, grid (2, 2047) by the resident rule (pieces * C = 4094 <= 4096), rows at every 4-byte phase."""
+        per channel, grid (1, 2047) by the resident rule (pieces * C = 4094 <= 4096: 2048 blocks in all, one per row), rows at every 4-byte phase."""
     ops = _ops()
     C, x = _rows_case(inner, 53, False)
     assert inner <= ops.fused_max_inner()
@@ -660,8 +719,17 @@ def test_fp32_fused_rows(inner):
     want = torch.from_numpy(oracle.c_quantize(xh, rmv, 2, 8, 1))                       # E5M2
     del xh
     fused = inner != 201
+    r = _route(ops, "minmax", x, 2)
+    assert r["nontemporal"] and r["kernel"] == {388: "k_rows_reg", 201: "k_rows_staged_mm", 8197: "k_minmax_partial"}[inner], r
+    if inner == 388:
+        assert (r["lanes"], r["slots"]) == (16, 7), r
     if fused:
-        y, mn, mx, mv = ops.minmax_quantize(x, 2, 8, 1, out=_out(x))
+        out = _out(x)
+        r = _route(ops, "minmax_quantize", x, 2, out)
+        assert (r["kernel"], r["nontemporal"]) == ("k_rows_reg" if inner == 388 else "k_rows_direct", True), r
+        assert (r["lanes"], r["slots"], r["lut"]) == ((16, 7, False) if inner == 388 else (0, 0, True)), r
+        y, mn, mx, mv = ops.minmax_quantize(x, 2, 8, 1, out=out)
+        del out
         for g, r, name in ((mn, rmn, "min"), (mx, rmx, "max"), (mv, rmv, "maxval")):
             _check(g, r, f"minmax_quantize row {name} vs oracle")
         _check(y, want, "minmax_quantize vs oracle")
@@ -669,6 +737,8 @@ def test_fp32_fused_rows(inner):
     for g, r, name in zip(ops.minmax(x, True, want_maxval=True), (rmn, rmx, rmv), ("min", "max", "maxval")):
         _check(g, r, f"minmax row {name} vs oracle")
     if inner > 2047:
+        r = _route(ops, "quantize", x, 2, x)
+        assert (r["kernel"], r["nontemporal"], r["grid_x"], r["grid_y"]) == ("k_quant_rows", True, 1, 2047), r
         _check(ops.quantize(x, mv, 2, 8, 1, out=_out(x)), want, "quantize (long rows, per channel) vs oracle")
     sl = _row_slice((C, inner))
     if fused:
