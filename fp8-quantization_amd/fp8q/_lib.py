@@ -161,6 +161,13 @@ SIGNATURES = {
     "fp8q_ocp_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _f, _vp]),
     "fp8q_ocp_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _i64, _i, _f, _vp]),
     "fp8q_ocp_scale_f32": (_i, [_vp, _i64, _i, _f, _vp, _vp]),
+    "fp8q_ocpb_route": (_i, [_i64, _i64, _i, _i, _i, _i]),
+    "fp8q_ocpb_encode_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _i, _f, _vp]),
+    "fp8q_ocpb_encode_h16": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _i, _f, _vp]),
+    "fp8q_ocpb_decode_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _i, _vp]),
+    "fp8q_ocpb_decode_h16": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _i, _vp]),
+    "fp8q_ocpb_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _f, _vp]),
+    "fp8q_ocpb_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _i, _i, _f, _vp]),
     "fp8q_mx_encode_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp]),
     "fp8q_mx_encode_h16": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _vp]),
     "fp8q_mx_decode_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _vp]),

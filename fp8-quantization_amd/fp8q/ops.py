@@ -1638,6 +1638,131 @@ def ocp_quantize(x, maxval, fmt, eps=1e-8, out=None, out_dtype=None):
     return y
 
 
+# ---- hardware FP8 under a float32 scale per tile (csrc/fp8q_ocp_block.hip; the contract is in include/fp8q.h) ----
+OCP_BLOCK_TILES = ((1, 128), (128, 1), (128, 128))
+OCP_BLOCK_KERNELS = ("rows", "panel", "plain")                     # FP8Q_OCPB_* (include/fp8q.h)
+
+
+def _ocpb_tile(tile):
+    try:
+        t = tuple(tile)
+    except TypeError:
+        t = None
+    if t not in OCP_BLOCK_TILES or any(isinstance(v, bool) for v in t):
+        raise Fp8qError(f"tile must be (1, 128), (128, 1) or (128, 128), got {tile!r}")
+    return t
+
+
+def _ocpb_geometry(shape, tile):
+    """(R, K, scales shape) of values shaped `shape` under `tile`: (1, 128) tiles the last dimension of any tensor (viewed as
+    [-1, K]), the tiles that span rows need a matrix.  Told from the shape alone, so raised before the device check."""
+    tr, tk = tile
+    if len(shape) == 0:
+        raise Fp8qError("the tiles run along the last dimension: the tensor needs at least one")
+    if tr != 1 and len(shape) != 2:
+        raise Fp8qError(f"{tr}x{tk} tiles span rows: x must be 2-D, got {len(shape)}-D {tuple(shape)} (reshape it to [R, K] "
+                        f"first)")
+    lead, K = tuple(int(s) for s in shape[:-1]), int(shape[-1])
+    R = 1
+    for s in lead:
+        R *= s
+    if tr == 1:
+        return R, K, lead + (-(-K // tk),)
+    return R, K, (-(-R // tr), -(-K // tk))
+
+
+def ocp_block_route(R, K, tile, dtype, aligned16=True):
+    """The kernel ocp_block_encode / ocp_block_quantize reach for an [R, K] tensor of `dtype` under `tile` -- fp8q_ocpb_route,
+    the launchers' own rule, host arithmetic only (no GPU needed): "rows", "panel" or "plain".  aligned16: x and the output
+    start on 16 bytes."""
+    tr, tk = _ocpb_tile(tile)
+    if dtype not in _DT:
+        raise Fp8qError(f"dtype must be float32, float16 or bfloat16, got {dtype}")
+    rc = lib().fp8q_ocpb_route(int(R), int(K), tr, tk, _DT[dtype], int(bool(aligned16)))
+    if rc < 0:
+        check(rc, "fp8q_ocpb_route")
+    return OCP_BLOCK_KERNELS[rc]
+
+
+def ocp_block_encode(x, fmt, tile=(1, 128), eps=1e-8, out=None, scales_out=None):
+    """Block-scaled hardware FP8 operands of x: (codes, scales).  Every tile of `tile` = (1, 128), (128, 1) or (128, 128)
+    elements gets its own float32 scale = max(amax(|tile|), eps) / fmax, found in the same pass; its codes are byte for byte
+    ocp_encode(x[tile], amax, fmt, eps)'s.  codes: dtype `fmt`, x's shape and layout for every tile (nothing is transposed);
+    scales: float32 [ceil(R / tr), ceil(K / tk)], row-major.  (1, 128) takes a tensor of any rank and tiles its last
+    dimension (scales: x.shape[:-1] + (ceil(K / 128),)); the tiles that span rows need a 2-D x.  Edge tiles are short.  x
+    float32, or float16 / bfloat16 (widened exactly).  `out`: contiguous uint8 or `fmt`; `scales_out`: contiguous float32 of
+    the scales' shape.  One launch, x read once."""
+    f = _ocp_fmt(fmt)
+    tile = _ocpb_tile(tile)
+    if isinstance(x, torch.Tensor):
+        _ocpb_geometry(x.shape, tile)
+    _require(x, "x", _VALUES)
+    x = x.detach().contiguous()
+    R, K, sshape = _ocpb_geometry(x.shape, tile)
+    if out is not None and isinstance(out, torch.Tensor) and out.dtype == fmt:
+        out = out.view(torch.uint8)
+    codes = _out(out, x, torch.uint8)
+    if scales_out is None:
+        scales = torch.empty(sshape, dtype=torch.float32, device=x.device)
+    else:
+        _require(scales_out, "scales_out", like=x)
+        if tuple(scales_out.shape) != sshape or not scales_out.is_contiguous():
+            raise Fp8qError(f"scales_out must be a contiguous float32 tensor of shape {sshape}, got "
+                            f"{tuple(scales_out.shape)}")
+        scales = scales_out
+    if x.numel():
+        sfx, types = _lane(x.dtype)
+        _run("fp8q_ocpb_encode" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), *types, R, K, *tile, f,
+             float(eps))
+    return codes.view(fmt).view(x.shape), scales
+
+
+def ocp_block_decode(codes, scales, tile=(1, 128), out_dtype=None, out=None, fmt=None):
+    """Values of block-scaled hardware FP8 operands: value(code) * scale of the element's tile, one float32 multiplication.
+    codes: a CUDA tensor of dtype torch.float8_e4m3fn / torch.float8_e5m2, or uint8 with `fmt` naming the format; scales:
+    float32, shaped as ocp_block_encode returns them for codes.shape and `tile`.  float32 unless a float16 / bfloat16 `out` or
+    out_dtype asks for a half type (the float32 product rounded once).  One launch."""
+    dt = _decode_out_dtype(out, out_dtype)
+    tile = _ocpb_tile(tile)
+    if isinstance(codes, torch.Tensor):
+        _, _, sshape = _ocpb_geometry(codes.shape, tile)
+        if isinstance(scales, torch.Tensor) and tuple(scales.shape) != sshape:
+            raise Fp8qError(f"scales are {tuple(scales.shape)}, codes of shape {tuple(codes.shape)} under {tile} tiles have "
+                            f"{sshape}")
+    fmt = _codes_fmt(codes, fmt, _OCP_FMT, "float8_e4m3fn, float8_e5m2", "torch.float8_e4m3fn or torch.float8_e5m2")
+    f = _ocp_fmt(fmt)
+    _require(scales, "scales", like=codes)
+    codes = codes.contiguous().view(torch.uint8)
+    scales = scales.detach().contiguous()
+    R, K, _ = _ocpb_geometry(codes.shape, tile)
+    y = _out(out, codes, dt)
+    if codes.numel() == 0:
+        return y
+    sfx, types = _lane(dt)
+    _run("fp8q_ocpb_decode" + sfx, codes, codes.data_ptr(), scales.data_ptr(), y.data_ptr(), *types, R, K, *tile, f)
+    return y
+
+
+def ocp_block_quantize(x, fmt, tile=(1, 128), eps=1e-8, out_dtype=None, out=None):
+    """Fake-quantize the way a block-scaled FP8 matrix multiplication sees x: ocp_block_decode(*ocp_block_encode(x, fmt,
+    tile, eps), tile) bit for bit, in one launch, the scales never leaving the chip.  x float32 gives float32; x float16 /
+    bfloat16 gives float32 unless `out` or out_dtype=x.dtype ask for x's own dtype (the float32 result rounded once)."""
+    f = _ocp_fmt(fmt)
+    tile = _ocpb_tile(tile)
+    if isinstance(x, torch.Tensor):
+        _ocpb_geometry(x.shape, tile)
+    _require(x, "x", _VALUES)
+    dt = _quantize_out_dtype(x, out, out_dtype)
+    x = x.detach().contiguous()
+    R, K, _ = _ocpb_geometry(x.shape, tile)
+    y = _out(out, x, dt)
+    if x.numel() == 0:
+        return y
+    sfx, types = _lane(x.dtype, dt)
+    _run("fp8q_ocpb_quantize" + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, *tile, f, float(eps))
+    return y
+
+
 # ---- microscaling: blocks of 32 under an E8M0 scale byte (csrc/fp8q_mx.hip; the contract is in include/fp8q.h) ----
 MX_E2M3, MX_E3M2 = "e2m3", "e3m2"      # the 6-bit formats: torch has no dtype for them, so strings name them and codes are uint8
 _MX_FP6 = (MX_E2M3, MX_E3M2)

@@ -11,6 +11,9 @@ It follows the quantizer protocol (QuantizerBase), so QuantizationManager drives
 model zoo takes it as `method=OCPFP8Quantizer`; it is deliberately NOT a member of QMethods (the CLI's choices).  Forward
 only: there is no backward kernel, and a call that would need a gradient raises NotImplementedError.  The MSE and line-search
 estimators are not supported with it.  There is no CPU path.
+
+OCPBlockFP8Quantizer, below it, is the same format under a float32 scale per 1x128 / 128x1 / 128x128 tile
+(csrc/fp8q_ocp_block.hip): range-free, like MXQuantizer, because a tile's scale is found inside the quantizing pass.
 """
 import torch
 
@@ -114,3 +117,89 @@ class OCPFP8Quantizer(QuantizerBase):
     def extra_repr(self):
         name = "E4M3FN" if self.fmt == torch.float8_e4m3fn else "E5M2"
         return f"{super().extra_repr()}, fmt={name}, eps={self.eps}"
+
+
+class OCPBlockFP8Quantizer(QuantizerBase):
+    """The same formats under one float32 scale per TILE of (1, 128), (128, 1) or (128, 128) elements -- the operands of a
+    block-scaled FP8 matrix multiplication (csrc/fp8q_ocp_block.hip): 1x128 along the reduction dimension for activations,
+    128x128 for weights, 128x1 for the operand of a product that reduces over dim 0.  The scale of a tile is a function of
+    that tile's own largest element, found inside the quantizing pass: there is no range to estimate, calibrate, fix or learn,
+    and `range_free = True` tells QuantizationManager so, as on MXQuantizer.  flatten_rows=True views a tensor of more than
+    two dimensions as [shape[0], -1] first (a convolution weight); the tiles that span rows need a matrix after that.
+        forward(x) = decode(*encode(x)),   encode(x) = (codes, scales) of fp8q.ops.ocp_block_encode
+    Forward only, not a member of QMethods, no CPU path; the model zoo takes it as `method=OCPBlockFP8Quantizer`."""
+    range_free = True
+
+    def __init__(self, n_bits=8, fmt=torch.float8_e4m3fn, tile=(1, 128), eps=1e-8, keep_dtype=False, flatten_rows=False,
+                 per_channel=False, scale_domain=None, **kwargs):
+        if n_bits != 8:
+            raise ValueError(f"hardware FP8 has 8 bits, got n_bits={n_bits}")
+        if fmt not in _ops.OCP_FMAX:
+            raise ValueError(f"fmt must be torch.float8_e4m3fn or torch.float8_e5m2, got {fmt}")
+        try:
+            tile = _ops._ocpb_tile(tile)
+        except _ops.Fp8qError as e:
+            raise ValueError(str(e)) from None
+        if not (isinstance(eps, (int, float)) and not isinstance(eps, bool) and eps >= 0):
+            raise ValueError(f"eps must be a non-negative number, got {eps!r}")
+        # per_channel is the protocol's argument; the scales are per tile either way
+        super().__init__(n_bits=n_bits, per_channel=per_channel, **kwargs)
+        self.fmt = fmt
+        self.tile = tile
+        self.eps = eps
+        # float16 / bfloat16 inputs: False returns float32, True the input's dtype (the float32 value rounded once)
+        self.keep_dtype = keep_dtype
+        self.flatten_rows = flatten_rows
+
+    @property
+    def is_initialized(self):
+        return True
+
+    @property
+    def symmetric(self):
+        return True
+
+    @property
+    def fmax(self):
+        return _ops.OCP_FMAX[self.fmt]
+
+    def reset(self):
+        pass
+
+    def set_quant_range(self, x_min, x_max):
+        pass
+
+    def fix_ranges(self):
+        pass
+
+    def make_range_trainable(self):
+        raise NotImplementedError("OCPBlockFP8Quantizer is forward-only and has no range: nothing can be learned")
+
+    def _rows(self, t):
+        """t as the kernels cut it into tiles: of [shape[0], -1] with flatten_rows"""
+        if self.flatten_rows and t.dim() > 2:
+            return t.contiguous().view(t.shape[0], -1)
+        return t
+
+    def forward(self, x_float):
+        if torch.is_grad_enabled() and x_float.requires_grad:
+            raise NotImplementedError("OCPBlockFP8Quantizer is forward-only: there is no backward kernel for the hardware "
+                                      "FP8 lane (call it under torch.no_grad(), or on a detached tensor)")
+        out_dtype = x_float.dtype if (self.keep_dtype and x_float.dtype in _HALF) else None
+        y = _ops.ocp_block_quantize(self._rows(x_float), self.fmt, self.tile, self.eps, out_dtype=out_dtype)
+        return y.view(x_float.shape)
+
+    def encode(self, x_float):
+        """(codes, scales) of forward(x): codes of dtype `fmt` shaped like x (with flatten_rows: like its [shape[0], -1]
+        view), scales float32, one per tile (fp8q.ops.ocp_block_encode)"""
+        return _ops.ocp_block_encode(self._rows(x_float.detach()), self.fmt, self.tile, self.eps)
+
+    def decode(self, codes, scales, out_dtype=None):
+        """Values of encode()'s operands, float32 or out_dtype (float16 / bfloat16: the float32 value rounded once), shaped as
+        encode() saw them: decode(*encode(x)) == forward(x) bit for bit (after .view(x.shape) with flatten_rows)."""
+        return _ops.ocp_block_decode(codes, scales, self.tile, out_dtype=out_dtype, fmt=self.fmt)
+
+    def extra_repr(self):
+        name = "E4M3FN" if self.fmt == torch.float8_e4m3fn else "E5M2"
+        return f"{super().extra_repr()}, fmt={name}, tile={self.tile[0]}x{self.tile[1]}, eps={self.eps}, " \
+               f"flatten_rows={self.flatten_rows}"

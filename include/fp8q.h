@@ -951,6 +951,59 @@ int fp8q_ocp_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_
                           int64_t n_maxval, int fmt, float eps, fp8q_stream_t stream);
 int fp8q_ocp_scale_f32(const float *maxval, int64_t n, int fmt, float eps, float *scale, fp8q_stream_t stream);
 
+/* ---- hardware FP8 under one float32 scale per TILE: 1x128, 128x1 and 128x128 (csrc/fp8q_ocp_block.hip) ----------------------
+ * The operand form of block-scaled FP8 matrix multiplications: E4M3FN / E5M2 elements, a float32 scale per tile -- 1x128 along
+ * the reduction dimension for activations, 128x128 for weights, 128x1 for the operand of a product that reduces over dim 0
+ * (dW = dy^T . x).  The range of a tile is found inside the pass: there is nothing to calibrate, and x is read once.
+ * x is [R, K], K contiguous, float32 or a half type (widened exactly).  fmt is FP8Q_OCP_E4M3FN or FP8Q_OCP_E5M2.  The tile
+ * (tile_r, tile_k) is (1, 128), (128, 1) or (128, 128); anything else is FP8Q_EUNSUPPORTED.  Tile (i, j) covers the rows
+ * [tile_r i, min(tile_r i + tile_r, R)) and the columns [tile_k j, min(tile_k j + tile_k, K)): edge tiles are short, and no
+ * tile wraps.
+ *   amax = torch.amax(|x|) over the tile     a NaN anywhere in the tile gives NaN, an infinity gives inf
+ *   codes and scale of the tile              byte for byte what the per-tensor call above gives on that tile alone,
+ *                                            fp8q_ocp_encode_* on x[tile] with maxval = amax and the same eps, and its scale_out:
+ *                                            scale = max(amax, eps) / fmax, q = clamp(x / scale, -fmax, fmax), code = RNE(q),
+ *                                            every NaN stored as 0x7F
+ *   decode = value(code) * scale             one float32 multiplication; a NaN code is not multiplied; a half output rounds
+ *                                            that product once
+ *   quantize = decode(encode)                bit for bit, in one launch, the scales never leaving the chip
+ * What follows from these rules (nothing below is a special case of the code):
+ *   - an all-zero tile has scale = eps / fmax and zero codes;
+ *   - a tile with a NaN has a NaN scale and every code 0x7F;
+ *   - a tile with an infinity has scale = inf: its finite elements encode to +-0, its infinities to 0x7F (inf / inf), and
+ *     every element of it decodes to NaN (0 * inf).
+ * Layout: codes is [R, K] bytes in x's own layout for all three tiles (nothing is transposed); scales is float32
+ * [ceil(R / tile_r), ceil(K / tile_k)], row-major, in no library's swizzle.  Power-of-two (UE8M0) tile scales are the MX
+ * lane's business, not this one's.
+ * Routes.  fp8q_ocpb_route is host arithmetic only: it returns the kernel (FP8Q_OCPB_*) that encode and quantize reach for
+ * a shape, or the error they would report; aligned16: x and codes / y start on 16 bytes.
+ *   FP8Q_OCPB_ROWS   (1, 128) with K % 128 == 0 and aligned16: a flat run of whole tiles, half a wave per tile
+ *   FP8Q_OCPB_PANEL  (128, 1) and (128, 128) with K % 4 == 0 and aligned16: a 128 x 128 panel per workgroup, held in registers
+ *                    (x is read once); ragged R and K are its own edge panels
+ *   FP8Q_OCPB_PLAIN  anything else: one wave per tile, element by element, the same bytes
+ * Decode takes the codes by dwords where K % 4 == 0 and codes / y start on 16 bytes, element by element otherwise.
+ * Errors, all reported before the launch: FP8Q_EINVAL for null pointers, R or K <= 0 (or an R * K beyond int64, a grid beyond
+ * INT32_MAX), a value pointer off its element's alignment, scales off 4 bytes, a type that is not a half type on an _h16
+ * entry (y_type: nor FP8Q_DT_F32) or two different half types; FP8Q_EUNSUPPORTED for any other fmt or tile.  One launch per
+ * call, enqueue-only, no workspace.  FP8Q_VERSION is unchanged: the entries are additive.
+ */
+#define FP8Q_OCPB_ROWS 0
+#define FP8Q_OCPB_PANEL 1
+#define FP8Q_OCPB_PLAIN 2
+int fp8q_ocpb_route(int64_t R, int64_t K, int tile_r, int tile_k, int x_type, int aligned16);
+int fp8q_ocpb_encode_f32(const float *x, uint8_t *codes, float *scales, int64_t R, int64_t K, int tile_r, int tile_k, int fmt,
+                         float eps, fp8q_stream_t stream);
+int fp8q_ocpb_encode_h16(const void *x, uint8_t *codes, float *scales, int x_type, int64_t R, int64_t K, int tile_r, int tile_k,
+                         int fmt, float eps, fp8q_stream_t stream);
+int fp8q_ocpb_decode_f32(const uint8_t *codes, const float *scales, float *y, int64_t R, int64_t K, int tile_r, int tile_k,
+                         int fmt, fp8q_stream_t stream);
+int fp8q_ocpb_decode_h16(const uint8_t *codes, const float *scales, void *y, int y_type, int64_t R, int64_t K, int tile_r,
+                         int tile_k, int fmt, fp8q_stream_t stream);
+int fp8q_ocpb_quantize_f32(const float *x, float *y, int64_t R, int64_t K, int tile_r, int tile_k, int fmt, float eps,
+                           fp8q_stream_t stream);
+int fp8q_ocpb_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int tile_r, int tile_k,
+                           int fmt, float eps, fp8q_stream_t stream);
+
 /* ---- microscaling (MX): blocks of 32 under an E8M0 scale byte, elements in E4M3FN / E5M2 / E2M3 / E3M2 / E2M1 ----------------
  * (csrc/fp8q_mx.hip)  The operand forms of gfx950's scaled matrix instructions (v_mfma_scale_f32_*_f8f6f4), carried by
  * torch.float8_e8m0fnu and torch.float4_e2m1fn_x2 (the 6-bit formats have no torch dtype: plain bytes).  These entries make, read and fake-quantize such operands; nothing here performs the multiplication,
