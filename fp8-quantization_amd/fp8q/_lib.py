@@ -50,6 +50,11 @@ class MxtRouteInfo(ctypes.Structure):
                 ("reserved", _i)]
 
 
+class OcpbtRouteInfo(ctypes.Structure):
+    """fp8q_ocpbt_route_info (include/fp8q.h): the kernel a transposed tile-scaled FP8 call reaches and its code stores"""
+    _fields_ = [("kernel", _i), ("code_store_bytes", _i), ("nontemporal", _i), ("reserved", _i)]
+
+
 class TensorDesc(ctypes.Structure):
     """fp8q_tensor_desc (include/fp8q.h)"""
     _fields_ = [("x", _vp), ("y", _vp), ("maxval", _vp), ("C", _i64), ("inner", _i64), ("n_maxval", _i64),
@@ -168,6 +173,11 @@ SIGNATURES = {
     "fp8q_ocpb_decode_h16": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _i, _vp]),
     "fp8q_ocpb_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _f, _vp]),
     "fp8q_ocpb_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _i, _i, _f, _vp]),
+    "fp8q_ocpbt_route": (_i, [_i64, _i64, _i, _i, _i, _i, ctypes.POINTER(OcpbtRouteInfo)]),
+    "fp8q_ocpbt_encode_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _i, _f, _vp]),
+    "fp8q_ocpbt_encode_h16": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _i, _f, _vp]),
+    "fp8q_ocpbt_encode_both_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _f, _vp]),
+    "fp8q_ocpbt_encode_both_h16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i, _i, _i, _f, _vp]),
     "fp8q_mx_encode_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp]),
     "fp8q_mx_encode_h16": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _vp]),
     "fp8q_mx_decode_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _vp]),

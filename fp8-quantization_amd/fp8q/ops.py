@@ -1763,6 +1763,124 @@ def ocp_block_quantize(x, fmt, tile=(1, 128), eps=1e-8, out_dtype=None, out=None
     return y
 
 
+# ---- the same operands transposed: those of x.t(), from x as it lies (csrc/fp8q_ocp_block_t.hip) ----
+OCP_BLOCK_T_TILES = ((1, 128), (128, 128))
+OCP_BLOCK_T_KERNELS = ("panel", "plain")                            # FP8Q_OCPBT_* (include/fp8q.h)
+
+
+def _ocpbt_tile(tile):
+    t = _ocpb_tile(tile)
+    if t not in OCP_BLOCK_T_TILES:
+        raise Fp8qError(f"tile {t} has no transposed operands: they would be x's (1, 128) quantization with transposed codes, "
+                        f"the operand of no product (the transposed tiles are (1, 128) and (128, 128); fake-quantization "
+                        f"under column tiles is ocp_block_quantize(x, tile=(128, 1)))")
+    return t
+
+
+def _ocpbt_geometry(x, tile):
+    """(R, K, row-wise scales shape, transposed scales shape) of a 2-D x; told from the shape alone, so raised before the
+    device check"""
+    if not isinstance(x, torch.Tensor):
+        raise Fp8qError("x must be a CUDA(HIP) tensor: the FP8 engine has no CPU path")
+    if x.dim() != 2:
+        raise Fp8qError(f"the transposed operands are those of a matrix: x must be 2-D, got {x.dim()}-D {tuple(x.shape)} "
+                        f"(reshape it to [R, K] first: the tiles are cut from that view's transpose)")
+    R, K = int(x.shape[0]), int(x.shape[1])
+    nR, nK = -(-R // 128), -(-K // 128)
+    if tile == (1, 128):
+        return R, K, (R, nK), (K, nR)
+    return R, K, (nR, nK), (nK, nR)
+
+
+def _ocpbt_buffer(out, name, dtypes, numel=None, shape=None):
+    """the caller's `out`-style argument, checked from its metadata alone (before the device check): one of `dtypes`,
+    contiguous, of `numel` elements (codes) or exactly `shape` (scales)"""
+    if out is None:
+        return
+    want = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+    if not isinstance(out, torch.Tensor) or out.dtype not in dtypes:
+        raise Fp8qError(f"{name} must be a {want} tensor, got {out.dtype if isinstance(out, torch.Tensor) else type(out)}")
+    if shape is not None and tuple(out.shape) != tuple(shape):
+        raise Fp8qError(f"{name} must be a contiguous {want} tensor of shape {tuple(shape)}, got {tuple(out.shape)}")
+    if (numel is not None and out.numel() != numel) or not out.is_contiguous():
+        raise Fp8qError(f"{name} must be a contiguous tensor of {numel if numel is not None else out.numel()} elements "
+                        f"(got {tuple(out.shape)}, contiguous={out.is_contiguous()})")
+
+
+def _ocpbt_take(out, name, shape, dtype, like):
+    """a fresh tensor of `dtype` shaped `shape`, or the caller's (checked by _ocpbt_buffer) once it is on `like`'s device;
+    codes as their uint8 view"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    _require(out, name, out.dtype, like)
+    return out.view(torch.uint8) if dtype == torch.uint8 else out
+
+
+def ocp_block_t_route(R, K, tile, dtype, aligned16=True):
+    """The kernel ocp_block_encode_t / ocp_block_encode_both reach for an [R, K] tensor of `dtype` under `tile` --
+    fp8q_ocpbt_route, the launchers' own rule, host arithmetic only (no GPU needed).  aligned16: every tensor of the call
+    starts on 16 bytes.  A dict: kernel "panel" or "plain", code_store_bytes (16, 4 or 1: the width of the transposed code
+    stores), nontemporal."""
+    from ._lib import OcpbtRouteInfo
+    import ctypes
+    tr, tk = _ocpbt_tile(tile)
+    if dtype not in _DT:
+        raise Fp8qError(f"dtype must be float32, float16 or bfloat16, got {dtype}")
+    info = OcpbtRouteInfo()
+    check(lib().fp8q_ocpbt_route(int(R), int(K), tr, tk, _DT[dtype], int(bool(aligned16)), ctypes.byref(info)),
+          "fp8q_ocpbt_route")
+    return {"kernel": OCP_BLOCK_T_KERNELS[info.kernel], "code_store_bytes": info.code_store_bytes,
+            "nontemporal": bool(info.nontemporal)}
+
+
+def ocp_block_encode_t(x, fmt, tile=(1, 128), eps=1e-8, out=None, scales_out=None):
+    """Block-scaled hardware FP8 operands of x.t() made from x as it lies: (codes_t, scales_t), byte for byte
+    ocp_block_encode(x.t().contiguous(), fmt, tile, eps) -- the operands of a product that reduces over dim 0 of x -- in one
+    launch that reads x once and makes no transposed copy.  x: 2-D [R, K] (reshape anything else), float32 / float16 /
+    bfloat16.  tile: (1, 128) or (128, 128).  codes_t: dtype `fmt`, [K, R]; scales_t: float32 [K, ceil(R / 128)] for
+    (1, 128), [ceil(K / 128), ceil(R / 128)] for (128, 128).  ocp_block_decode(codes_t, scales_t, tile) gives the values of
+    x.t().  `out`: contiguous uint8 or `fmt` of R * K elements; `scales_out`: contiguous float32 of the scales' shape."""
+    f = _ocp_fmt(fmt)
+    tile = _ocpbt_tile(tile)
+    R, K, _, stshape = _ocpbt_geometry(x, tile)
+    _ocpbt_buffer(out, "out", (torch.uint8, fmt), numel=R * K)
+    _ocpbt_buffer(scales_out, "scales_out", (torch.float32,), shape=stshape)
+    _require(x, "x", _VALUES)
+    x = x.detach().contiguous()
+    codes_t = _ocpbt_take(out, "out", (K, R), torch.uint8, x)
+    scales_t = _ocpbt_take(scales_out, "scales_out", stshape, torch.float32, x)
+    if x.numel():
+        sfx, types = _lane(x.dtype)
+        _run("fp8q_ocpbt_encode" + sfx, x, x.data_ptr(), codes_t.data_ptr(), scales_t.data_ptr(), *types, R, K, *tile, f,
+             float(eps))
+    return codes_t.view(fmt).view(K, R), scales_t
+
+
+def ocp_block_encode_both(x, fmt, tile=(1, 128), eps=1e-8, out=None, scales_out=None, out_t=None, scales_out_t=None):
+    """Both orientations of x's block-scaled operands from ONE read of x: (codes, scales, codes_t, scales_t) =
+    ocp_block_encode(x, fmt, tile, eps) + ocp_block_encode_t(x, fmt, tile, eps), byte for byte, in one launch.  (1, 128): two
+    quantizations (row tiles and column tiles have their own scales); (128, 128): one, stored twice -- codes_t == codes.t()
+    and scales_t == scales.t().  x: 2-D.  out / scales_out / out_t / scales_out_t: as in ocp_block_encode_t."""
+    f = _ocp_fmt(fmt)
+    tile = _ocpbt_tile(tile)
+    R, K, sshape, stshape = _ocpbt_geometry(x, tile)
+    _ocpbt_buffer(out, "out", (torch.uint8, fmt), numel=R * K)
+    _ocpbt_buffer(scales_out, "scales_out", (torch.float32,), shape=sshape)
+    _ocpbt_buffer(out_t, "out_t", (torch.uint8, fmt), numel=R * K)
+    _ocpbt_buffer(scales_out_t, "scales_out_t", (torch.float32,), shape=stshape)
+    _require(x, "x", _VALUES)
+    x = x.detach().contiguous()
+    codes = _ocpbt_take(out, "out", (R, K), torch.uint8, x)
+    scales = _ocpbt_take(scales_out, "scales_out", sshape, torch.float32, x)
+    codes_t = _ocpbt_take(out_t, "out_t", (K, R), torch.uint8, x)
+    scales_t = _ocpbt_take(scales_out_t, "scales_out_t", stshape, torch.float32, x)
+    if x.numel():
+        sfx, types = _lane(x.dtype)
+        _run("fp8q_ocpbt_encode_both" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), codes_t.data_ptr(),
+             scales_t.data_ptr(), *types, R, K, *tile, f, float(eps))
+    return codes.view(fmt).view(R, K), scales, codes_t.view(fmt).view(K, R), scales_t
+
+
 # ---- microscaling: blocks of 32 under an E8M0 scale byte (csrc/fp8q_mx.hip; the contract is in include/fp8q.h) ----
 MX_E2M3, MX_E3M2 = "e2m3", "e3m2"      # the 6-bit formats: torch has no dtype for them, so strings name them and codes are uint8
 _MX_FP6 = (MX_E2M3, MX_E3M2)

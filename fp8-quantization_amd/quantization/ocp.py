@@ -199,6 +199,23 @@ class OCPBlockFP8Quantizer(QuantizerBase):
         encode() saw them: decode(*encode(x)) == forward(x) bit for bit (after .view(x.shape) with flatten_rows)."""
         return _ops.ocp_block_decode(codes, scales, self.tile, out_dtype=out_dtype, fmt=self.fmt)
 
+    def _transposable(self):
+        if self.tile not in _ops.OCP_BLOCK_T_TILES:
+            raise ValueError(f"a quantizer with tile={self.tile} has no transposed operands: they are made under (1, 128) or "
+                             f"(128, 128) tiles (fp8q.ops.ocp_block_encode_t)")
+
+    def encode_t(self, x_float):
+        """(codes_t, scales_t): the operands of the transpose of the matrix encode() sees -- encode(x.t().contiguous()) byte
+        for byte, from x as it lies (fp8q.ops.ocp_block_encode_t).  x must be a matrix (after flatten_rows);
+        decode(codes_t, scales_t) gives the transpose's values.  ValueError for a quantizer built with tile=(128, 1)."""
+        self._transposable()
+        return _ops.ocp_block_encode_t(self._rows(x_float.detach()), self.fmt, self.tile, self.eps)
+
+    def encode_both(self, x_float):
+        """(codes, scales, codes_t, scales_t) = encode(x) + encode_t(x) from one read of x (fp8q.ops.ocp_block_encode_both)"""
+        self._transposable()
+        return _ops.ocp_block_encode_both(self._rows(x_float.detach()), self.fmt, self.tile, self.eps)
+
     def extra_repr(self):
         name = "E4M3FN" if self.fmt == torch.float8_e4m3fn else "E5M2"
         return f"{super().extra_repr()}, fmt={name}, tile={self.tile[0]}x{self.tile[1]}, eps={self.eps}, " \

@@ -1004,6 +1004,56 @@ int fp8q_ocpb_quantize_f32(const float *x, float *y, int64_t R, int64_t K, int t
 int fp8q_ocpb_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int tile_r, int tile_k,
                            int fmt, float eps, fp8q_stream_t stream);
 
+/* ---- the same operands TRANSPOSED: those of x^T, made from x as it lies (csrc/fp8q_ocp_block_t.hip) -------------------------
+ * A block-scaled FP8 product takes both operands with the reduction dimension contiguous.  The backward products reduce over
+ * dim 0 of x -- dx = dy . W over W's rows, dW = dy^T . x over the tokens -- so they need the 1x128 operands of x^T and dy^T
+ * and the 128x128 operand of W^T, laid out [K, R].  x is [R, K], K contiguous, float32 or a half type (widened exactly).
+ * Contract, by reference: the transposed operands of x are, byte for byte, the operands of the contiguous [K, R] tensor x^T
+ * under the tile-scaled contract above, same fmt, tile and eps.  codes_t is [K, R] bytes; scales_t is float32, row-major,
+ * [K, ceil(R / 128)] for (1, 128) -- column c of x is cut into the tiles of rows [128 i, min(128 i + 128, R)) -- and
+ * [ceil(K / 128), ceil(R / 128)] for (128, 128).  fp8q_ocpb_decode_* reads them as the [K, R] operands they are (it gives the
+ * values of x^T); there is no transposing decode and no transposed quantize: fake-quantization in x's own layout under the
+ * transposed (1, 128) tiles is fp8q_ocpb_quantize_* with the tile (128, 1).
+ *   fp8q_ocpbt_encode_*       writes codes_t and scales_t
+ *   fp8q_ocpbt_encode_both_*  writes codes / scales, equal to fp8q_ocpb_encode_*'s, and codes_t / scales_t, equal to
+ *                             fp8q_ocpbt_encode_*'s, from one read of x.  (1, 128): two quantizations, row tiles and column
+ *                             tiles have their own scales.  (128, 128): one quantization stored twice, codes_t and scales_t
+ *                             are the transposes of codes and scales
+ * The tile is (1, 128) or (128, 128).  (128, 1) is FP8Q_EUNSUPPORTED here, like every other tile: its result would be x's
+ * 1x128 quantization with transposed codes, the operand of no product.  The special tiles (all zero, a NaN, an infinity)
+ * follow from the contract above, as there.
+ * fp8q_ocpbt_route is host arithmetic only and is the launchers' own rule: aligned16 says whether EVERY pointer of the call
+ * starts on 16 bytes.
+ *   FP8Q_OCPBT_PANEL  K % 4 == 0 and aligned16: a 128 x 128 panel per workgroup, held in registers (x is read once), the
+ *                     transposed codes turned in LDS and stored along R in words of code_store_bytes
+ *   FP8Q_OCPBT_PLAIN  anything else: one wave per tile, element by element, the same bytes (encode_both at (1, 128) reads x
+ *                     twice there)
+ * Errors, all reported before the launch: FP8Q_EINVAL for null pointers (the route: a null info), R or K <= 0 (or an R * K
+ * beyond int64, a grid beyond INT32_MAX), a value pointer off its element's alignment, scales or scales_t off 4 bytes, a type
+ * that is not a half type on an _h16 entry; FP8Q_EUNSUPPORTED for any other fmt or tile.  One launch per call, enqueue-only,
+ * nothing read back, no workspace.
+ * Names: these entries are fp8q_ocpbt_*: the set of fp8q_ocpb_* entries is the lane's seven.  FP8Q_VERSION is unchanged: the
+ * entries are additive.
+ */
+#define FP8Q_OCPBT_PANEL 0
+#define FP8Q_OCPBT_PLAIN 1
+typedef struct fp8q_ocpbt_route_info {
+    int kernel;             /* FP8Q_OCPBT_PANEL or FP8Q_OCPBT_PLAIN */
+    int code_store_bytes;   /* bytes per store of transposed codes on the panel route: 16 where R % 16 == 0, 4 where R % 4 == 0,
+                               else 1; 1 on the plain route */
+    int nontemporal;        /* the panel kernel's nontemporal variant (R * K * 4 bytes from 64 MiB) */
+    int reserved;
+} fp8q_ocpbt_route_info;
+int fp8q_ocpbt_route(int64_t R, int64_t K, int tile_r, int tile_k, int x_type, int aligned16, fp8q_ocpbt_route_info *info);
+int fp8q_ocpbt_encode_f32(const float *x, uint8_t *codes_t, float *scales_t, int64_t R, int64_t K, int tile_r, int tile_k,
+                          int fmt, float eps, fp8q_stream_t stream);
+int fp8q_ocpbt_encode_h16(const void *x, uint8_t *codes_t, float *scales_t, int x_type, int64_t R, int64_t K, int tile_r,
+                          int tile_k, int fmt, float eps, fp8q_stream_t stream);
+int fp8q_ocpbt_encode_both_f32(const float *x, uint8_t *codes, float *scales, uint8_t *codes_t, float *scales_t, int64_t R,
+                               int64_t K, int tile_r, int tile_k, int fmt, float eps, fp8q_stream_t stream);
+int fp8q_ocpbt_encode_both_h16(const void *x, uint8_t *codes, float *scales, uint8_t *codes_t, float *scales_t, int x_type,
+                               int64_t R, int64_t K, int tile_r, int tile_k, int fmt, float eps, fp8q_stream_t stream);
+
 /* ---- microscaling (MX): blocks of 32 under an E8M0 scale byte, elements in E4M3FN / E5M2 / E2M3 / E3M2 / E2M1 ----------------
  * (csrc/fp8q_mx.hip)  The operand forms of gfx950's scaled matrix instructions (v_mfma_scale_f32_*_f8f6f4), carried by
  * torch.float8_e8m0fnu and torch.float4_e2m1fn_x2 (the 6-bit formats have no torch dtype: plain bytes).  These entries make, read and fake-quantize such operands; nothing here performs the multiplication,
