@@ -50,10 +50,10 @@ def _same(got, want, what):
                              f"{g.flatten()[bad[:5]].tolist()} != {w.flatten()[bad[:5]].tolist()}"
 
 
-def _oracle(x, maxval, fmt, per_channel):
+def _oracle(x, maxval, fmt, per_channel, eps=EPS):
     """(codes, scale, values) of the contract on the CPU; x float32 (a half input: x.float())"""
     fmax = FMAX[fmt]
-    scale = torch.max(maxval.float(), torch.tensor(EPS)) / fmax
+    scale = torch.max(maxval.float(), torch.tensor(eps, dtype=torch.float32)) / fmax
     s = scale.view([-1] + [1] * (x.dim() - 1)) if per_channel else scale
     q = torch.clamp(x / s, -fmax, fmax)
     codes = torch.where(torch.isnan(q), torch.tensor(0x7F, dtype=torch.uint8), q.to(fmt).view(torch.uint8)).view(fmt)
@@ -86,19 +86,19 @@ def _case(shape, per_channel, fmt, seed=0):
     return x.reshape(shape).contiguous(), maxval
 
 
-def _check_lane(x, maxval, fmt, per_channel, what):
+def _check_lane(x, maxval, fmt, per_channel, what, eps=EPS):
     """every entry point on one tensor (x on the CPU, float32 or half) against the oracle of x.float()"""
     from fp8q import ops
-    ref_c, ref_s, ref_y = _oracle(x.float(), maxval, fmt, per_channel)
+    ref_c, ref_s, ref_y = _oracle(x.float(), maxval, fmt, per_channel, eps)
     xd, md = x.cuda(), maxval.cuda()
-    codes, scale = ops.ocp_encode(xd, md, fmt, eps=EPS)
+    codes, scale = ops.ocp_encode(xd, md, fmt, eps=eps)
     assert codes.dtype == fmt and codes.shape == x.shape and scale.dtype == torch.float32
     _same(codes, ref_c, f"{what}: codes")
     _same(scale, ref_s, f"{what}: scale_out")
-    _same(ops.ocp_scale(md, fmt, EPS), ref_s, f"{what}: ocp_scale")
+    _same(ops.ocp_scale(md, fmt, eps), ref_s, f"{what}: ocp_scale")
     outs = [torch.float32] if x.dtype == torch.float32 else [torch.float32, x.dtype]
     for dt in outs:
-        y = ops.ocp_quantize(xd, md, fmt, eps=EPS, out_dtype=dt)
+        y = ops.ocp_quantize(xd, md, fmt, eps=eps, out_dtype=dt)
         assert y.dtype == dt and y.shape == x.shape
         _same(y, ref_y.to(dt), f"{what}: quantize -> {dt}")
         d = ops.ocp_decode(codes, scale, out_dtype=dt)
@@ -167,6 +167,29 @@ def test_every_midpoint_of_the_grid(fmt):
     for r in range(2):
         _check_lane(x[r].contiguous(), maxval[r:r + 1], fmt, False, f"midpoints row {r} per tensor")
         _check_lane(x[r].contiguous().bfloat16(), maxval[r:r + 1], fmt, False, f"midpoints row {r} bfloat16")
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=_ids)
+@pytest.mark.parametrize("fmt", FMTS, ids=_ids)
+def test_midpoints_under_a_subnormal_scale_and_a_huge_range(fmt, dtype):
+    """the grid, its midpoints and their float32 neighbours times the scale, clamped to the range, under maxval = 1e-37 (the
+    scale is subnormal and 1 / scale overflows: ocp_scale_pair stores a NaN reciprocal and every element is divided) and
+    3e38 (a reciprocal near the bottom of the normal range), beside an ordinary row per channel, and each alone per tensor.
+    eps = 1e-40, below both, or the default 1e-8 would be the range."""
+    eps = 1e-40
+    grid = _finite_grid(fmt)
+    mid = (grid[:-1] + grid[1:]) / 2
+    inf = torch.tensor(float("inf"))
+    v = torch.cat([mid, torch.nextafter(mid, inf), torch.nextafter(mid, -inf), grid])
+    maxval = torch.tensor([1e-37, 3.0, 3e38])
+    scale = maxval / FMAX[fmt]
+    assert 0 < scale[0].item() < 2.0 ** -126 and torch.isinf(1.0 / scale[0]) and torch.isfinite(1.0 / scale[2])
+    x = torch.stack([torch.clamp(v * s, -m, m) for s, m in zip(scale, maxval)]).contiguous().to(dtype)
+    assert (x[0] != 0).sum().item() > 300 and torch.isfinite(x).all()      # (bfloat16 under E5M2 keeps 354 of 985 above 0)
+    codes, got = _check_lane(x, maxval, fmt, True, "per channel", eps=eps)
+    assert torch.equal(got.cpu().view(torch.int32), scale.view(torch.int32))
+    for r in (0, 2):
+        _check_lane(x[r].contiguous(), maxval[r:r + 1], fmt, False, f"row {r} per tensor", eps=eps)
 
 
 @pytest.mark.parametrize("fmt", FMTS, ids=_ids)
