@@ -83,9 +83,10 @@ k_codec_rows(const float *__restrict__ x, uint8_t *__restrict__ codes, float *__
 
 extern "C" {
 
-static int codec_launch(bool encode, const float *x, uint8_t *codes, float *y, int64_t C, int64_t inner,
-                        const float *maxval, int64_t n_maxval, float mbits, int n_bits, int sign_bits,
-                        fp8q_stream_t stream)
+// fp8q_encode_u8 / fp8q_decode_u8 themselves; rec: record the route instead of launching (route_emit, fp8q_common.h)
+static int codec_plan(bool encode, const float *x, uint8_t *codes, float *y, int64_t C, int64_t inner,
+                      const float *maxval, int64_t n_maxval, float mbits, int n_bits, int sign_bits,
+                      hipStream_t st, fp8q_codec_route_info *rec)
 {
     if (C < 0 || inner < 0 || (n_maxval != 1 && n_maxval != C)) return FP8Q_EINVAL;
     if (n_bits > 8) return FP8Q_EUNSUPPORTED;   // a code is one byte (include/fp8q.h)
@@ -99,45 +100,69 @@ static int codec_launch(bool encode, const float *x, uint8_t *codes, float *y, i
         inner *= C;
         C = 1;
     }
-    if (per_channel && inner < 2048) {   // short rows (weights): aligned chunks with per-row tables, not a block per row
+    if (per_channel) {   // short rows (weights): aligned chunks with per-row tables, not a block per row -- if the shape fits
         const int rc = fp8q_codec_flat_launch(encode, encode ? (const void *)x : (const void *)codes,
-                                              encode ? (void *)codes : (void *)y, C, inner, maxval, f, n_bits,
-                                              (hipStream_t)stream);
+                                              encode ? (void *)codes : (void *)y, C, inner, maxval, f, n_bits, st, rec);
         if (rc != FP8Q_CODEC_NOT_FLAT) return rc;
     }
+    const bool nt = C * inner * 4 >= kNtBytes;
     for (int64_t c0 = 0; c0 < C; c0 += 65535) {
         const int64_t cn = (C - c0) < 65535 ? (C - c0) : 65535;
-        const int64_t bx = balanced_blocks(cdiv(cdiv(inner, 16), kBlock), kTargetBlocks / cn);   // 4096 elements per block and step
+        const int64_t pieces = cdiv(cdiv(inner, 16), kBlock);   // 4096 elements per block and step
+        const int64_t bx = balanced_blocks(pieces, kTargetBlocks / cn);
         const dim3 g((unsigned)bx, (unsigned)cn), b(kBlock);
-        const bool nt = C * inner * 4 >= kNtBytes;
         const float *mvp = maxval + (per_channel ? c0 : 0);
-        if (encode && nt)
-            hipLaunchKernelGGL((k_codec_rows<true, true>), g, b, 0, (hipStream_t)stream, x + c0 * inner,
-                               codes + c0 * inner, (float *)nullptr, inner, mvp, per_channel, f, n_bits);
-        else if (encode)
-            hipLaunchKernelGGL((k_codec_rows<true, false>), g, b, 0, (hipStream_t)stream, x + c0 * inner,
-                               codes + c0 * inner, (float *)nullptr, inner, mvp, per_channel, f, n_bits);
-        else if (nt)
-            hipLaunchKernelGGL((k_codec_rows<false, true>), g, b, 0, (hipStream_t)stream, (const float *)nullptr,
-                               codes + c0 * inner, y + c0 * inner, inner, mvp, per_channel, f, n_bits);
-        else
-            hipLaunchKernelGGL((k_codec_rows<false, false>), g, b, 0, (hipStream_t)stream, (const float *)nullptr,
-                               codes + c0 * inner, y + c0 * inner, inner, mvp, per_channel, f, n_bits);
+        const float *xs = encode ? x + c0 * inner : nullptr;
+        float *ys = encode ? nullptr : y + c0 * inner;
+        const auto fill = [&](fp8q_codec_route_info &r) {
+            r.kernel = FP8Q_CODEC_K_CODEC_ROWS;
+            r.nontemporal = nt;
+            r.grid_x = bx;
+            r.grid_y = cn;
+            r.steps = cdiv(pieces, bx);
+        };
+        const int rc = route_emit(rec, fill, [&] {
+            dispatch<true, false>(encode, [&](auto ENC) {
+                dispatch<true, false>(nt, [&](auto NT) {
+                    hipLaunchKernelGGL((k_codec_rows<ENC(), NT()>), g, b, 0, st, xs, codes + c0 * inner, ys, inner, mvp, per_channel,
+                                       f, n_bits);
+                });
+            });
+        });
+        if (rc) return rc;
     }
-    return launch_rc();
+    return FP8Q_OK;
+}
+
+// Which kernel fp8q_encode_u8 / fp8q_decode_u8 launch: codec_plan itself with a record instead of a stream, on made-up
+// addresses that have the caller's 16-byte phases and are never dereferenced.  Host arithmetic only.
+int fp8q_codec_route(int encode, int64_t C, int64_t inner, int64_t n_maxval, float mbits, int n_bits, int sign_bits,
+                     int fp_mod16, int code_mod16, fp8q_codec_route_info *info)
+{
+    if (!info || fp_mod16 < 0 || fp_mod16 > 15 || (fp_mod16 & 3) != 0 || code_mod16 < 0 || code_mod16 > 15) return FP8Q_EINVAL;
+    // far apart, far from null, and far from wrapping at any tensor the entries take
+    float *fp = reinterpret_cast<float *>(((uintptr_t)1 << 44) + (uintptr_t)fp_mod16);
+    uint8_t *cp = reinterpret_cast<uint8_t *>(((uintptr_t)1 << 45) + (uintptr_t)code_mod16);
+    const float *mv = reinterpret_cast<const float *>((uintptr_t)1 << 46);
+    fp8q_codec_route_info r = {};
+    r.kernel = -1;      // an empty tensor: nothing is launched
+    const int rc = codec_plan(encode != 0, encode ? fp : nullptr, cp, encode ? nullptr : fp, C, inner, mv, n_maxval, mbits,
+                              n_bits, sign_bits, nullptr, &r);
+    if (rc == FP8Q_OK) *info = r;
+    return rc;
 }
 
 int fp8q_encode_u8(const float *x, uint8_t *codes, int64_t C, int64_t inner, const float *maxval,
                    int64_t n_maxval, float mbits, int n_bits, int sign_bits, fp8q_stream_t stream)
 {
-    return codec_launch(true, x, codes, nullptr, C, inner, maxval, n_maxval, mbits, n_bits, sign_bits, stream);
+    return codec_plan(true, x, codes, nullptr, C, inner, maxval, n_maxval, mbits, n_bits, sign_bits, (hipStream_t)stream, nullptr);
 }
 
 int fp8q_decode_u8(const uint8_t *codes, float *y, int64_t C, int64_t inner, const float *maxval,
                    int64_t n_maxval, float mbits, int n_bits, int sign_bits, fp8q_stream_t stream)
 {
-    return codec_launch(false, nullptr, const_cast<uint8_t *>(codes), y, C, inner, maxval, n_maxval, mbits,
-                        n_bits, sign_bits, stream);
+    return codec_plan(false, nullptr, const_cast<uint8_t *>(codes), y, C, inner, maxval, n_maxval, mbits, n_bits, sign_bits,
+                      (hipStream_t)stream, nullptr);
 }
 
 }  // extern "C"

@@ -21,8 +21,9 @@ using namespace fp8q;
 
 // short-row path of the storage codec: lives with k_rows_flat in fp8q_rows.hip, called from fp8q_codec.hip
 constexpr int FP8Q_CODEC_NOT_FLAT = -1000;
+// rec: record the route instead of launching (route_emit below; fp8q_codec_route)
 int fp8q_codec_flat_launch(bool encode, const void *in, void *out, int64_t C, int64_t inner, const float *maxval,
-                           const QFmt &f, int n_bits, hipStream_t st);
+                           const QFmt &f, int n_bits, hipStream_t st, fp8q_codec_route_info *rec);
 
 namespace {
 
@@ -331,5 +332,20 @@ inline int launch_rc() { return hip_rc(hipGetLastError()); }
 
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// The one launch site of a launcher that a route query can ask (fp8q_rows_route, fp8q_codec_route).  The launcher runs its
+// geometry block and its dispatch down to this call whoever asks: with rec == nullptr `launch` enqueues the kernel, otherwise
+// `fill` writes the choices just made into *rec (the first launch describes the call, `launches` counts the slabs) and nothing
+// touches the device -- the pointers of a query are made-up addresses with the caller's 16-byte phases.
+template <class Rec, class Fill, class Launch>
+inline int route_emit(Rec *rec, Fill &&fill, Launch &&launch)
+{
+    if (rec) {
+        if (rec->launches++ == 0) fill(*rec);
+        return FP8Q_OK;
+    }
+    launch();
+    return launch_rc();
+}
 
 }  // namespace

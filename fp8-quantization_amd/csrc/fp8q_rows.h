@@ -96,19 +96,11 @@ inline FlatArgs flat_geometry(int64_t C, int64_t inner, int lut_stride)
     return a;
 }
 
-// The one launch site of a row launcher.  Every launcher of the family runs its geometry block and its dispatch down to this
-// call whoever asks: with rec == nullptr `launch` enqueues the kernel, otherwise `fill` writes the choices just made into
-// *rec (fp8q_rows_route: the first launch describes the call, `launches` counts the slabs) and nothing touches the device --
-// the pointers of a query are made-up addresses with the caller's 16-byte phases.
+// The one launch site of a row launcher: route_emit (fp8q_common.h) on the row family's record.
 template <class Fill, class Launch>
 inline int rows_emit(fp8q_rows_route_info *rec, Fill &&fill, Launch &&launch)
 {
-    if (rec) {
-        if (rec->launches++ == 0) fill(*rec);
-        return FP8Q_OK;
-    }
-    launch();
-    return launch_rc();
+    return route_emit(rec, fill, launch);
 }
 
 }  // namespace

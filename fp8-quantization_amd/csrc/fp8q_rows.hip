@@ -881,9 +881,10 @@ static int launch_rows_flat(int mode, const float *x, float *y, int64_t C, int64
 // per-row tables in LDS): the row-per-block codec kernel spends a 256-thread block, a double-precision constant
 // evaluation and a 33-entry table on every 147-element filter.  kNotFlat when the shape does not fit.
 // Used by fp8q_codec.hip (same library, not part of the C ABI).
+// rec: record the route instead of launching (route_emit; what fp8q_codec_route asks).
 __attribute__((visibility("hidden"))) int fp8q_codec_flat_launch(bool encode, const void *in, void *out, int64_t C,
                                                                  int64_t inner, const float *maxval, const QFmt &f,
-                                                                 int n_bits, hipStream_t st)
+                                                                 int n_bits, hipStream_t st, fp8q_codec_route_info *rec)
 {
     const void *fp = encode ? in : (const void *)out;       // the fp32 side
     const void *cp = encode ? (const void *)out : in;       // the code side
@@ -895,18 +896,29 @@ __attribute__((visibility("hidden"))) int fp8q_codec_flat_launch(bool encode, co
     if (nch < 1) return kNotFlat;
     a.nch = (int)nch;
     a.group = 1;
-    int64_t blocks = cdiv(a.nchunks, nch);
+    const int64_t tiles = cdiv(a.nchunks, nch);
+    int64_t blocks = tiles;
     if (blocks > 32768) blocks = 32768;
     const bool nt = C * inner * 4 >= kNtBytes;
     const float *xf = (const float *)in;    // encode: fp32 in; decode: the codes, reinterpreted inside the kernel
     float *yf = (float *)out;               // decode: fp32 out; encode: the codes
-    dispatch<kModeEncode, kModeDecode>(encode ? kModeEncode : kModeDecode, [&](auto MODE) {
-        dispatch<true, false>(nt, [&](auto NT) {
-            hipLaunchKernelGGL((k_rows_flat<MODE(), NT()>), dim3((unsigned)blocks), dim3(kBlock), flat_shmem(a, per_row), st, xf, yf,
-                               maxval, nullptr, nullptr, nullptr, f, a);
+    const auto fill = [&](fp8q_codec_route_info &r) {
+        r.kernel = FP8Q_CODEC_K_ROWS_FLAT;
+        r.nontemporal = nt;
+        r.nch = a.nch;
+        r.wide = encode && ((uintptr_t)cp & 15) == 0;   // (a chunk's codes start a multiple of 4096 bytes behind the base)
+        r.grid_x = blocks;
+        r.grid_y = 1;
+        r.steps = cdiv(tiles, blocks);
+    };
+    return route_emit(rec, fill, [&] {
+        dispatch<kModeEncode, kModeDecode>(encode ? kModeEncode : kModeDecode, [&](auto MODE) {
+            dispatch<true, false>(nt, [&](auto NT) {
+                hipLaunchKernelGGL((k_rows_flat<MODE(), NT()>), dim3((unsigned)blocks), dim3(kBlock), flat_shmem(a, per_row), st, xf, yf,
+                                   maxval, nullptr, nullptr, nullptr, f, a);
+            });
         });
     });
-    return launch_rc();
 }
 
 // k_rows_staged_mm for [C, inner]: rows of 4..256 elements, x 16-byte aligned; kNotFlat otherwise

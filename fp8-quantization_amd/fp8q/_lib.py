@@ -44,6 +44,12 @@ class RowsRouteInfo(ctypes.Structure):
                 ("grid_y", _i64)]
 
 
+class CodecRouteInfo(ctypes.Structure):
+    """fp8q_codec_route_info (include/fp8q.h): the kernel a storage-code encode / decode reaches and its launcher's choices"""
+    _fields_ = [("kernel", _i), ("nontemporal", _i), ("nch", _i), ("wide", _i), ("launches", _i), ("reserved", _i),
+                ("grid_x", _i64), ("grid_y", _i64), ("steps", _i64)]
+
+
 class MxtRouteInfo(ctypes.Structure):
     """fp8q_mxt_route_info (include/fp8q.h): the kernel a transposed-MX call reaches and its tile"""
     _fields_ = [("kernel", _i), ("tile_rows", _i), ("tile_cols", _i), ("nontemporal", _i), ("code_store_bytes", _i),
@@ -115,6 +121,7 @@ SIGNATURES = {
                                                _i, ctypes.c_double, _i, _vp, ctypes.c_size_t, _vp]),
     "fp8q_encode_u8": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _f, _i, _i, _vp]),
     "fp8q_decode_u8": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _f, _i, _i, _vp]),
+    "fp8q_codec_route": (_i, [_i, _i64, _i64, _i64, _f, _i, _i, _i, _i, ctypes.POINTER(CodecRouteInfo)]),
     "fp8q_multi_quantize_f32": (_i, [ctypes.POINTER(TensorDesc), _i, _vp]),
     "fp8q_multi_minmax_quantize_f32": (_i, [ctypes.POINTER(TensorDesc), ctypes.POINTER(_vp), _i, _vp]),
     "fp8q_multi_encode_u8": (_i, [ctypes.POINTER(TensorDesc), _i, _vp]),

@@ -1539,6 +1539,26 @@ def decode(codes, maxval, mbits, n_bits=8, sign_bits=1, out=None, out_dtype=None
     return y
 
 
+CODEC_KERNELS = ("k_rows_flat", "k_codec_rows")                      # FP8Q_CODEC_K_* (include/fp8q.h)
+
+
+def codec_route(encode, C, inner, per_channel=True, mbits=2, n_bits=8, sign_bits=1, fp_mod16=0, code_mod16=0):
+    """The kernel encode (encode true) / decode reach for a [C, inner] float32 tensor of this format whose float32 side and
+    codes sit at these addresses modulo 16 (fp8q_codec_route, include/fp8q.h), as a dict: kernel (a name of CODEC_KERNELS; None
+    when nothing is launched), nontemporal, wide (bools), nch, launches, grid_x, grid_y (of the first launch), steps; what does
+    not apply to the kernel is 0.  Host arithmetic only: needs no GPU.  Raises Fp8qError as the entry would for the shape."""
+    import ctypes
+    from ._lib import CodecRouteInfo
+    info = CodecRouteInfo()
+    check(lib().fp8q_codec_route(int(bool(encode)), int(C), int(inner), int(C) if per_channel else 1, float(mbits), int(n_bits),
+                                 int(sign_bits), int(fp_mod16), int(code_mod16), ctypes.byref(info)), "fp8q_codec_route")
+    r = {name: int(getattr(info, name)) for name, _ in CodecRouteInfo._fields_ if name != "reserved"}
+    r["kernel"] = CODEC_KERNELS[info.kernel] if info.kernel >= 0 else None
+    for name in ("nontemporal", "wide"):
+        r[name] = bool(r[name])
+    return r
+
+
 # ---- hardware FP8: OCP E4M3FN / E5M2 (csrc/fp8q_ocp.hip; the contract is in include/fp8q.h) ----
 _OCP_FMT = {torch.float8_e4m3fn: 0, torch.float8_e5m2: 1}          # FP8Q_OCP_* (include/fp8q.h)
 OCP_FMAX = {torch.float8_e4m3fn: 448.0, torch.float8_e5m2: 57344.0}

@@ -484,11 +484,48 @@ int fp8q_affine_act_minmax_packed_f32(const float *x, const float *residual, int
  *                   same ambiguity: it emits either, depending on which side x came from)
  * n_bits <= 8 and at least one exponent bit (FP8Q_EUNSUPPORTED otherwise).  The format has no NaN: NaN inputs and degenerate channels (maxval 0/inf/NaN, whose
  * K1 output is NaN) encode as 0.  HBM traffic: 5 B / element each.
+ * fp8q_decode_u8 expects codes below 2^n_bits: what a byte with a bit at or above n_bits decodes to is not defined.
  */
 int fp8q_encode_u8(const float *x, uint8_t *codes, int64_t C, int64_t inner, const float *maxval,
                    int64_t n_maxval, float mbits, int n_bits, int sign_bits, fp8q_stream_t stream);
 int fp8q_decode_u8(const uint8_t *codes, float *y, int64_t C, int64_t inner, const float *maxval,
                    int64_t n_maxval, float mbits, int n_bits, int sign_bits, fp8q_stream_t stream);
+
+/*
+ * Which kernel fp8q_encode_u8 (encode != 0) or fp8q_decode_u8 (encode == 0) launches for a [C, inner] tensor of a format, at
+ * the process's settings.  Host arithmetic only: no launch, no device -- the entries' own code behind their argument checks,
+ * the launchers' geometry and dispatch included, with a callback that records instead of launching, so that a test can assert
+ * the route before it trusts a shape.  n_maxval: C (one range per row) or 1 (one for the tensor: the entries then see one row
+ * of C * inner elements).  fp_mod16 / code_mod16: the addresses of the float32 side (x or y; a multiple of 4) and of the codes
+ * modulo 16.
+ *   kernel          FP8Q_CODEC_K_* below; -1 with launches == 0 for an empty tensor
+ *   nontemporal     the instance for tensors of 64 MiB and more
+ *   nch             k_rows_flat: chunks of 4096 elements per tile, 1..4
+ *   wide            k_rows_flat, encode: the codes start on a 16-byte boundary, four groups of a lane leave as one 16-byte store
+ *                   (else as dwords)
+ *   grid_x, grid_y  of the first launch
+ *   launches        k_codec_rows: one per slab of 65535 rows; k_rows_flat: 1
+ *   steps           k_codec_rows: grid-stride steps of a block over its row's 4096-element pieces, ceil(pieces / grid_x);
+ *                   k_rows_flat: tiles a block walks (more than 1 beyond 32768 tiles)
+ * k_codec_rows picks its vector width per row from the row's own addresses: 16-byte float32 accesses need that side 16-byte
+ * aligned and the codes 4-byte aligned (encode: 16-byte aligned, else every element goes alone); otherwise scalar.
+ * Fields that do not apply to the kernel are 0.  Errors as the entries report them for the shape and format: FP8Q_EINVAL (a
+ * negative size, n_maxval neither 1 nor C, n_bits < 2, sign_bits not 0 or 1, a NaN mbits; here also a phase out of range or info NULL),
+ * FP8Q_EUNSUPPORTED (n_bits > 8, no exponent bit, more than seven); `info` is written on FP8Q_OK only.
+ */
+#define FP8Q_CODEC_K_ROWS_FLAT 0    /* k_rows_flat: per-channel rows of 4..2047 elements whose tables fit, fp32 side 16-byte and codes 4-byte aligned */
+#define FP8Q_CODEC_K_CODEC_ROWS 1   /* k_codec_rows: one row per blockIdx.y; everything else */
+typedef struct fp8q_codec_route_info {
+    int kernel;
+    int nontemporal;
+    int nch;
+    int wide;
+    int launches;
+    int reserved;
+    int64_t grid_x, grid_y, steps;
+} fp8q_codec_route_info;
+int fp8q_codec_route(int encode, int64_t C, int64_t inner, int64_t n_maxval, float mbits, int n_bits, int sign_bits,
+                     int fp_mod16, int code_mod16, fp8q_codec_route_info *info);
 
 /*
  * Multi-tensor K1 -- all weight tensors of a model in one launch: the reference quantizes

@@ -210,6 +210,21 @@ int main()
     {
         uint8_t *codes = (uint8_t *)malloc(n), *rcodes = (uint8_t *)malloc(n), *dcodes;
         CK(hipMalloc((void **)&dcodes, n));
+        {   // the codec's route query, from the phases of the pointers the two calls below pass
+            fp8q_codec_route_info ci;
+            bool good = true;
+            for (int enc = 1; enc >= 0; --enc) {
+                CK(fp8q_codec_route(enc, C, inner, C, 2.0f, 8, 1, (int)((uintptr_t)(enc ? dx : dy) & 15), (int)((uintptr_t)dcodes & 15), &ci));
+                good &= ci.kernel == FP8Q_CODEC_K_ROWS_FLAT && ci.launches == 1 && ci.nch >= 1 && ci.wide == enc && !ci.nontemporal;
+            }
+            CK(fp8q_codec_route(1, C, inner, 1, 2.0f, 8, 1, 0, 0, &ci));
+            good &= ci.kernel == FP8Q_CODEC_K_CODEC_ROWS && ci.grid_y == 1 && ci.steps >= 1;
+            good &= fp8q_codec_route(1, C, inner, C, 2.0f, 9, 1, 0, 0, &ci) == FP8Q_EUNSUPPORTED;
+            good &= fp8q_codec_route(1, C, inner, C, 7.0f, 8, 1, 0, 0, &ci) == FP8Q_EUNSUPPORTED;
+            good &= fp8q_codec_route(1, C, inner, C + 1, 2.0f, 8, 1, 0, 0, &ci) == FP8Q_EINVAL;
+            printf(good ? "ok   fp8q_codec_route (k_rows_flat both ways, k_codec_rows per tensor; error codes)\n" : "FAIL fp8q_codec_route\n");
+            ok &= good;
+        }
         CK(fp8q_encode_u8(dx, dcodes, C, inner, dmv, C, 2.0f, 8, 1, st));
         CK(fp8q_decode_u8(dcodes, dy, C, inner, dmv, C, 2.0f, 8, 1, st));
         CK(hipStreamSynchronize(st));

@@ -15,7 +15,7 @@ border and chunk border.  A helper, not a test module; numpy only (and the host-
 """
 import numpy as np
 
-from epilogue_cases import edge_index, edge_slots, edge_values, is_plain, ranges
+from epilogue_cases import edge_index, edge_slots, edge_values, is_plain, ranges, ties
 
 E5M2, E4M3, E7 = (2, 8, 1), (3, 8, 1), (1, 8, 0)
 NARROW = (7, 8, 1)          # no exponent bit: two table entries, the smallest tables
@@ -348,3 +348,21 @@ def case_input(shape, fmt, op, seed=0, nan=False):
     # what the special rows overwrote is no longer an edge value of the case
     ok = xf[pos].view(np.int32) == val.view(np.int32)
     return dict(x=x, maxval=None, ranges=rr, pos=pos[ok], idx=idx[ok], val=val[ok], kinds=kinds, planted=planted)
+
+
+def tie_cloud(fmt, C, inner, seed):
+    """rows filled with values within a few ulp of the rounding ties of their own range, for ranges whose bias is no integer (the
+    grid step is then no power of two and its reciprocal is inexact): where a quotient formed with the reciprocal lands on the
+    other side of the tie than the division does.  Every binade of epilogue_cases.ties, the first one included."""
+    rng = np.random.RandomState(seed)
+    R = [0.7361, 2.5, 0.0123, 1.37, 0.3333, 57.1, 1e-3, 9.9]
+    mv = np.array([R[r % len(R)] for r in range(C)], np.float32)
+    x = np.empty((C, inner), np.float32)
+    for r in range(C):
+        t = np.array([v for _, _, v, _ in ties(fmt[0], float(mv[r]), fmt[2], fmt[1])], np.float64)
+        t = t[t <= float(mv[r])]
+        first = np.array([v for p, _, v, _ in ties(fmt[0], float(mv[r]), fmt[2], fmt[1]) if p == 1], np.float64)
+        t = np.concatenate([t, np.resize(first, t.size)])        # half of the picks from the first binade
+        pick = t[rng.randint(0, t.size, inner)] * (1.0 + rng.randint(-6, 7, inner) * 2.0 ** -24)
+        x[r] = (pick * rng.choice([-1.0, 1.0] if fmt[2] else [1.0], inner)).astype(np.float32)
+    return x, mv

@@ -77,9 +77,6 @@ def test_roundtrip_on_non_geometric_scale_tables():
     assert worst >= 1                        # the fixture does exercise the caveat
 
 
-pytestmark_gpu = pytest.mark.gpu
-
-
 def dev(a, dtype=np.float32):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
 
@@ -186,7 +183,10 @@ def test_bucketed_weight_exchange_with_codes_on_the_wire_single_process():
 def test_hip_codec_short_row_geometries():
     """Per-channel tensors with short rows take the chunked kernel (k_rows_flat encode / decode modes): odd row
     lengths whose rows straddle 16-byte groups and 16 KiB chunks, a ragged tail, tiles of several chunks, every
-    format with an exponent bit, unsigned, NaN / inf / -0 inputs -- codes and decoded values equal to the oracle's."""
+    format with an exponent bit, unsigned, NaN / inf / -0 inputs -- codes and decoded values equal to the oracle's.
+    Which kernel a shape reaches is asserted elsewhere: tests/test_codec_routes_host.py and tests/test_codec_routes_gpu.py run
+    every route of ops.codec_route with edge values on every border (rows of 4..6 elements, (40000,5) and (77777,4) among these,
+    take k_codec_rows: no format's tables fit next to a chunk)."""
     import fp8q
     ops = fp8q.ops
     rng = np.random.RandomState(21)

@@ -151,25 +151,6 @@ def test_minmax_reaches_its_kernel_and_folds_like_the_oracle(ops, key, want):
     assert not ws.cpu().numpy().any(), key
 
 
-def _tie_cloud(fmt, C, inner, seed):
-    """rows filled with values within a few ulp of the rounding ties of their own range, for ranges whose bias is no integer (the
-    grid step is then no power of two and its reciprocal is inexact): where a quotient formed with the reciprocal lands on the
-    other side of the tie than the division does.  Every binade of epilogue_cases.ties, the first one included."""
-    import epilogue_cases as ec
-    rng = np.random.RandomState(seed)
-    R = [0.7361, 2.5, 0.0123, 1.37, 0.3333, 57.1, 1e-3, 9.9]
-    mv = np.array([R[r % len(R)] for r in range(C)], np.float32)
-    x = np.empty((C, inner), np.float32)
-    for r in range(C):
-        t = np.array([v for _, _, v, _ in ec.ties(fmt[0], float(mv[r]), fmt[2], fmt[1])], np.float64)
-        t = t[t <= float(mv[r])]
-        first = np.array([v for p, _, v, _ in ec.ties(fmt[0], float(mv[r]), fmt[2], fmt[1]) if p == 1], np.float64)
-        t = np.concatenate([t, np.resize(first, t.size)])        # half of the picks from the first binade
-        pick = t[rng.randint(0, t.size, inner)] * (1.0 + rng.randint(-6, 7, inner) * 2.0 ** -24)
-        x[r] = (pick * rng.choice([-1.0, 1.0] if fmt[2] else [1.0], inner)).astype(np.float32)
-    return x, mv
-
-
 # (format, C, inner, x / y phase, in place) -> kernel and, for k_rows_direct, whether it is the instance with tables
 TIE_CASES = [
     (rc.E5M2, 120, 147, 0, False, "k_rows_flat", False), (rc.E4M3, 120, 147, 0, False, "k_rows_flat", False),
@@ -190,7 +171,7 @@ def test_values_next_to_ties_take_the_exact_quotient(ops, fmt, C, inner, xp, ip,
     close to a tie (quant_group, quant_one), and the kernel without tables must divide in its first binade as in every other.
     (With two mantissa bits the reciprocal quotient never differs from the division on these values: the E4M3 and seven-exponent-
     bit cases are the ones that tell.)"""
-    xh, mvh = _tie_cloud(fmt, C, inner, C + inner)
+    xh, mvh = rc.tie_cloud(fmt, C, inner, C + inner)
     n = C * inner
     xbuf, x, xoff = _window(n, xp)
     x.copy_(torch.from_numpy(xh.reshape(-1)))
