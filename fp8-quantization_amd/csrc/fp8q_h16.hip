@@ -282,25 +282,23 @@ k_h16_minmax_part(const uint16_t *__restrict__ x, int64_t inner, int nsplit, uns
 // ---------------------------------------------------------------------------------------------
 constexpr int kRowsMmMaxInner = 2048;   // k_h16_minmax_rows up to here
 
-template <class T, bool YF32, bool PC>
-void quant_launch_u(int u, bool nt, dim3 g, size_t shmem, hipStream_t st, const uint16_t *x, void *y, const float *maxval,
-                    const QFmt &f, const H16Args &a)
-{
-    if (u == 1)
-        hipLaunchKernelGGL((k_h16_quant<T, YF32, PC, 1, false>), g, dim3(kBlock), shmem, st, x, y, maxval, f, a);
-    else if (nt)
-        hipLaunchKernelGGL((k_h16_quant<T, YF32, PC, 4, true>), g, dim3(kBlock), shmem, st, x, y, maxval, f, a);
-    else
-        hipLaunchKernelGGL((k_h16_quant<T, YF32, PC, 4, false>), g, dim3(kBlock), shmem, st, x, y, maxval, f, a);
-}
-
-template <class T, bool YF32>
-int quant_launch(const uint16_t *x, void *y, int64_t C, int64_t inner, const float *maxval, bool pc, const QFmt &f,
-                 hipStream_t st)
-{
+// What a K1 call launches: every decision of the launcher, taken once from the shape, the format and x's 16-byte phase.
+// quant_launch consumes it; fp8q_h16_route reports it.
+struct QuantPlan {
+    int kernel;       // FP8Q_H16_K_QUANT / FP8Q_H16_K_QUANT_ROWS
+    int u;            // k_h16_quant: 16-byte groups in flight per lane (1, 4)
+    bool nt;          // the nontemporal instance (U = 4 only)
     H16Args a;
+    size_t shmem;
+    int64_t grid_x;
+};
+
+QuantPlan quant_plan(uintptr_t x, int64_t C, int64_t inner, bool pc, const QFmt &f)
+{
+    QuantPlan p = {};
+    H16Args &a = p.a;
     a.n = C * inner;
-    a.head = ((16 - ((uintptr_t)x & 15)) & 15) >> 1;
+    a.head = ((16 - (x & 15)) & 15) >> 1;
     if (a.head > a.n) a.head = a.n;
     a.ng = (a.n - a.head) >> 3;
     a.inner = pc ? inner : a.n;
@@ -313,21 +311,44 @@ int quant_launch(const uint16_t *x, void *y, int64_t C, int64_t inner, const flo
     if (pc) {
         if (u == 4 && rows_of(4) * per_row > kH16LdsBudget) u = 1;
         if (inner < 8 || rows_of(1) * per_row > kH16LdsBudget) {
-            hipLaunchKernelGGL((k_h16_quant_rows<T, YF32>), dim3((unsigned)cdiv(C, kBlock)), dim3(kBlock), 0, st, x, y, C, inner,
-                               maxval, f);
-            return launch_rc();
+            p.kernel = FP8Q_H16_K_QUANT_ROWS;
+            p.grid_x = cdiv(C, kBlock);
+            return p;
         }
     }
+    p.kernel = FP8Q_H16_K_QUANT;
+    p.u = u;
     a.nc_max = (int)rows_of(u);
     a.magic = (pc && inner < kBlock * 8 * u) ? magic_of((int)inner) : 0u;
-    const size_t shmem = (size_t)a.nc_max * per_row;
-    const int64_t nblocks = a.ng > 0 ? cdiv(a.ng, (int64_t)kBlock * u) : 1;
-    const bool nt = a.n * 2 >= kNtBytes;
-    const dim3 g((unsigned)nblocks);
-    if (pc)
-        quant_launch_u<T, YF32, true>(u, nt, g, shmem, st, x, y, maxval, f, a);
+    p.shmem = (size_t)a.nc_max * per_row;
+    p.grid_x = a.ng > 0 ? cdiv(a.ng, (int64_t)kBlock * u) : 1;
+    p.nt = u == 4 && a.n * 2 >= kNtBytes;   // (U = 1 has no nontemporal instance: 2^20 groups come long before 64 MiB)
+    return p;
+}
+
+template <class T, bool YF32, bool PC>
+void quant_launch_u(const QuantPlan &p, hipStream_t st, const uint16_t *x, void *y, const float *maxval, const QFmt &f)
+{
+    const dim3 g((unsigned)p.grid_x);
+    if (p.u == 1)
+        hipLaunchKernelGGL((k_h16_quant<T, YF32, PC, 1, false>), g, dim3(kBlock), p.shmem, st, x, y, maxval, f, p.a);
+    else if (p.nt)
+        hipLaunchKernelGGL((k_h16_quant<T, YF32, PC, 4, true>), g, dim3(kBlock), p.shmem, st, x, y, maxval, f, p.a);
     else
-        quant_launch_u<T, YF32, false>(u, nt, g, shmem, st, x, y, maxval, f, a);
+        hipLaunchKernelGGL((k_h16_quant<T, YF32, PC, 4, false>), g, dim3(kBlock), p.shmem, st, x, y, maxval, f, p.a);
+}
+
+template <class T, bool YF32>
+int quant_launch(const uint16_t *x, void *y, int64_t C, int64_t inner, const float *maxval, bool pc, const QFmt &f,
+                 hipStream_t st)
+{
+    const QuantPlan p = quant_plan((uintptr_t)x, C, inner, pc, f);
+    if (p.kernel == FP8Q_H16_K_QUANT_ROWS)
+        hipLaunchKernelGGL((k_h16_quant_rows<T, YF32>), dim3((unsigned)p.grid_x), dim3(kBlock), 0, st, x, y, C, inner, maxval, f);
+    else if (pc)
+        quant_launch_u<T, YF32, true>(p, st, x, y, maxval, f);
+    else
+        quant_launch_u<T, YF32, false>(p, st, x, y, maxval, f);
     return launch_rc();
 }
 
@@ -364,39 +385,67 @@ int minmax_h16_nsplit(int64_t C, int64_t inner)
     return (int)(ns < 1 ? 1 : ns);
 }
 
+// What a min/max call launches, from the shape alone (need_ws: the entry with a workspace, whose long rows may be split).
+// minmax_launch consumes it; fp8q_h16_route reports it.
+struct MinmaxPlan {
+    int kernel;        // FP8Q_H16_K_MINMAX_ROWS / FP8Q_H16_K_MINMAX_PART
+    int gs;            // k_h16_minmax_rows: 2^gs lanes per row
+    int ns;            // k_h16_minmax_part: streaming blocks per row
+    bool nt;
+    unsigned gx;
+    int64_t gy;        // of the first launch
+    int launches;      // slabs of 65535 rows
+};
+
+constexpr int64_t kMmSlabRows = 65535;   // gridDim.y
+
+MinmaxPlan minmax_plan(int64_t C, int64_t inner, bool need_ws)
+{
+    MinmaxPlan p = {};
+    p.launches = 1;
+    if (C > 1 && inner <= kRowsMmMaxInner) {
+        p.kernel = FP8Q_H16_K_MINMAX_ROWS;
+        while (p.gs < 6 && (32 << p.gs) < inner) ++p.gs;   // up to four 16-byte accesses per lane
+        p.gx = (unsigned)cdiv(C, kBlock >> p.gs);
+        p.gy = 1;
+        return p;
+    }
+    p.kernel = FP8Q_H16_K_MINMAX_PART;
+    p.ns = need_ws ? minmax_h16_nsplit(C, inner) : 1;
+    p.gx = p.ns > 1 ? (unsigned)p.ns + 1u : 1u;   // + the row's reducer block
+    p.gy = C < kMmSlabRows ? C : kMmSlabRows;
+    p.nt = C * inner * 2 >= kNtBytes;
+    p.launches = (int)cdiv(C, kMmSlabRows);   // ns > 1 implies C <= kTargetBlocks / 2: a single slab
+    return p;
+}
+
 template <class T>
 int minmax_launch(const uint16_t *x, int64_t C, int64_t inner, float *cur_min, float *cur_max, float *maxval_out, FoldArgs fa,
                   void *ws, size_t ws_bytes, bool need_ws, hipStream_t st)
 {
-    if (C > 1 && inner <= kRowsMmMaxInner) {
-        int gs = 0;
-        while (gs < 6 && (32 << gs) < inner) ++gs;   // up to four 16-byte accesses per lane
-        const int rpb = kBlock >> gs;
-        hipLaunchKernelGGL(k_h16_minmax_rows<T>, dim3((unsigned)cdiv(C, rpb)), dim3(kBlock), 0, st, x, C, (int)inner, gs, cur_min,
-                           cur_max, maxval_out, fa);
+    const MinmaxPlan p = minmax_plan(C, inner, need_ws);
+    if (p.kernel == FP8Q_H16_K_MINMAX_ROWS) {
+        hipLaunchKernelGGL(k_h16_minmax_rows<T>, dim3(p.gx), dim3(kBlock), 0, st, x, C, (int)inner, p.gs, cur_min, cur_max,
+                           maxval_out, fa);
         return launch_rc();
     }
-    int ns = 1;
     unsigned long long *slots = nullptr;
     if (need_ws) {
         if (!ws || ws_bytes < fp8q_minmax_workspace_bytes(C, inner) || ((uintptr_t)ws & 7)) return FP8Q_EWORKSPACE;
-        ns = minmax_h16_nsplit(C, inner);
         fa.status = (unsigned *)ws;
         fold_debug_env(fa);
         slots = (unsigned long long *)((char *)ws + kMinmaxWsHeader);
     }
     const unsigned tag = next_minmax_tag();
-    const unsigned gx = ns > 1 ? (unsigned)ns + 1u : 1u;   // + the row's reducer block
-    const bool nt = C * inner * 2 >= kNtBytes;
-    for (int64_t c0 = 0; c0 < C; c0 += 65535) {   // ns > 1 implies C <= kTargetBlocks / 2: a single slab
-        const int64_t cn = (C - c0) < 65535 ? (C - c0) : 65535;
-        const dim3 g(gx, (unsigned)cn);
-        if (nt)
-            hipLaunchKernelGGL((k_h16_minmax_part<T, true>), g, dim3(kBlock), 0, st, x + c0 * inner, inner, ns, slots, tag,
+    for (int64_t c0 = 0; c0 < C; c0 += kMmSlabRows) {
+        const int64_t cn = (C - c0) < kMmSlabRows ? (C - c0) : kMmSlabRows;
+        const dim3 g(p.gx, (unsigned)cn);
+        if (p.nt)
+            hipLaunchKernelGGL((k_h16_minmax_part<T, true>), g, dim3(kBlock), 0, st, x + c0 * inner, inner, p.ns, slots, tag,
                                cur_min ? cur_min + c0 : nullptr, cur_max ? cur_max + c0 : nullptr,
                                maxval_out ? maxval_out + c0 : nullptr, fa);
         else
-            hipLaunchKernelGGL((k_h16_minmax_part<T, false>), g, dim3(kBlock), 0, st, x + c0 * inner, inner, ns, slots, tag,
+            hipLaunchKernelGGL((k_h16_minmax_part<T, false>), g, dim3(kBlock), 0, st, x + c0 * inner, inner, p.ns, slots, tag,
                                cur_min ? cur_min + c0 : nullptr, cur_max ? cur_max + c0 : nullptr,
                                maxval_out ? maxval_out + c0 : nullptr, fa);
         if (int rc = launch_rc()) return rc;
@@ -412,9 +461,82 @@ int minmax_dispatch(const void *x, int x_type, int64_t C, int64_t inner, float *
     return minmax_launch<BF16>(xs, C, inner, cur_min, cur_max, maxval_out, fa, ws, ws_bytes, need_ws, st);
 }
 
+// the shape checks of fp8q_minmax_h16 and of the fused entry behind quant_check (shared with fp8q_h16_route)
+int minmax_check(const void *x, int64_t C, int64_t inner)
+{
+    if (!x || C <= 0 || inner <= 0 || ((uintptr_t)x & 1)) return FP8Q_EINVAL;
+    if (C > INT64_MAX / inner) return FP8Q_EINVAL;
+    return FP8Q_OK;
+}
+
+int fused_check(int64_t inner) { return inner > fp8q_fused_max_inner() ? FP8Q_ETOOLONG : FP8Q_OK; }
+
+void report(const QuantPlan &p, fp8q_h16_launch_info &r)
+{
+    r.kernel = p.kernel;
+    r.launches = 1;
+    r.grid_x = p.grid_x;
+    r.grid_y = 1;
+    if (p.kernel != FP8Q_H16_K_QUANT) return;
+    r.u = p.u;
+    r.nontemporal = p.nt;
+    r.head = p.a.head;
+    r.groups = p.a.ng;
+    r.tail = p.a.n - p.a.head - 8 * p.a.ng;
+    r.rows_per_chunk = p.a.nc_max;
+    r.lds_bytes = (int64_t)p.shmem;
+}
+
+void report(const MinmaxPlan &p, fp8q_h16_launch_info &r)
+{
+    r.kernel = p.kernel;
+    r.launches = p.launches;
+    r.grid_x = p.gx;
+    r.grid_y = p.gy;
+    if (p.kernel == FP8Q_H16_K_MINMAX_ROWS) {
+        r.lanes = 1 << p.gs;
+    } else {
+        r.nsplit = p.ns;
+        r.nontemporal = p.nt;
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+// Which kernels the three entries below launch: their argument checks and their launchers' plans (quant_plan, minmax_plan) on
+// made-up addresses that have the caller's 16-byte phase and are never dereferenced.  Host arithmetic only.
+int fp8q_h16_route(int op, int64_t C, int64_t inner, int per_channel, float mbits, int n_bits, int sign_bits, int x_mod16,
+                   int y_type, fp8q_h16_route_info *info)
+{
+    if (!info || op < FP8Q_ROWS_QUANTIZE || op > FP8Q_ROWS_MINMAX_QUANTIZE || x_mod16 < 0 || x_mod16 > 15) return FP8Q_EINVAL;
+    if (y_type != FP8Q_DT_F32 && !half_type(y_type)) return FP8Q_EINVAL;
+    if (op == FP8Q_ROWS_MINMAX_QUANTIZE && !per_channel) return FP8Q_EINVAL;
+    const void *x = reinterpret_cast<const void *>(((uintptr_t)1 << 44) + (uintptr_t)x_mod16);
+    void *y = reinterpret_cast<void *>((uintptr_t)1 << 45);
+    const int x_type = half_type(y_type) ? y_type : FP8Q_DT_F16;   // (the route is the same for both half types)
+    fp8q_h16_route_info r = {};
+    QFmt f;
+    if (op == FP8Q_ROWS_MINMAX) {
+        if (!per_channel && C > 0 && inner > 0) {   // the wrapper's view of a per-tensor estimator: one row
+            if (C > INT64_MAX / inner) return FP8Q_EINVAL;
+            inner *= C;
+            C = 1;
+        }
+        if (int rc = minmax_check(x, C, inner)) return rc;
+        report(minmax_plan(C, inner, true), r.launch[r.n_launches++]);
+    } else {
+        if (int rc = quant_check(x, y, x_type, y_type, C, inner, per_channel != 0, mbits, n_bits, sign_bits, &f)) return rc;
+        if (op == FP8Q_ROWS_MINMAX_QUANTIZE) {
+            if (int rc = fused_check(inner)) return rc;
+            report(minmax_plan(C, inner, false), r.launch[r.n_launches++]);
+        }
+        report(quant_plan((uintptr_t)x, C, inner, per_channel != 0, f), r.launch[r.n_launches++]);
+    }
+    *info = r;
+    return FP8Q_OK;
+}
 
 int fp8q_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t C, int64_t inner, const float *maxval,
                       int64_t n_maxval, float mbits, int n_bits, int sign_bits, fp8q_stream_t stream)
@@ -429,9 +551,8 @@ int fp8q_minmax_h16(const void *x, int x_type, int64_t C, int64_t inner, float *
                     int fold_mode, double momentum, int first, void *ws, size_t ws_bytes, fp8q_stream_t stream)
 {
     if (!half_type(x_type)) return FP8Q_EINVAL;
-    if (!x || !cur_min || !cur_max || C <= 0 || inner <= 0 || fold_mode < 0 || fold_mode > 2 || ((uintptr_t)x & 1))
-        return FP8Q_EINVAL;
-    if (C > INT64_MAX / inner) return FP8Q_EINVAL;
+    if (!cur_min || !cur_max || fold_mode < 0 || fold_mode > 2) return FP8Q_EINVAL;
+    if (int rc = minmax_check(x, C, inner)) return rc;
     FoldArgs fa;
     fa.mode = fold_mode;
     fa.first = first != 0;
@@ -446,7 +567,7 @@ int fp8q_minmax_quantize_h16(const void *x, void *y, int x_type, int y_type, int
     QFmt f;
     if (int rc = quant_check(x, y, x_type, y_type, C, inner, true, mbits, n_bits, sign_bits, &f)) return rc;
     if (!maxval_out) return FP8Q_EINVAL;   // carries the ranges from the scan to K1
-    if (inner > fp8q_fused_max_inner()) return FP8Q_ETOOLONG;
+    if (int rc = fused_check(inner)) return rc;
     FoldArgs fa;
     fa.mode = FP8Q_FOLD_CURRENT;
     fa.first = 1;

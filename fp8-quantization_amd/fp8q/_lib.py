@@ -50,6 +50,18 @@ class CodecRouteInfo(ctypes.Structure):
                 ("grid_x", _i64), ("grid_y", _i64), ("steps", _i64)]
 
 
+class H16LaunchInfo(ctypes.Structure):
+    """fp8q_h16_launch_info (include/fp8q.h): one kernel of a half-lane call and its launcher's choices"""
+    _fields_ = [("kernel", _i), ("u", _i), ("nontemporal", _i), ("lanes", _i), ("nsplit", _i), ("rows_per_chunk", _i),
+                ("launches", _i), ("reserved", _i), ("head", _i64), ("groups", _i64), ("tail", _i64), ("lds_bytes", _i64),
+                ("grid_x", _i64), ("grid_y", _i64)]
+
+
+class H16RouteInfo(ctypes.Structure):
+    """fp8q_h16_route_info (include/fp8q.h): the kernels a half-lane quantize / min-max / fused call launches, in order"""
+    _fields_ = [("n_launches", _i), ("reserved", _i), ("launch", H16LaunchInfo * 2)]
+
+
 class MxtRouteInfo(ctypes.Structure):
     """fp8q_mxt_route_info (include/fp8q.h): the kernel a transposed-MX call reaches and its tile"""
     _fields_ = [("kernel", _i), ("tile_rows", _i), ("tile_cols", _i), ("nontemporal", _i), ("code_store_bytes", _i),
@@ -147,6 +159,7 @@ SIGNATURES = {
     "fp8q_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _i64, _f, _i, _i, _vp]),
     "fp8q_minmax_h16": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, _i, ctypes.c_double, _i, _vp, ctypes.c_size_t, _vp]),
     "fp8q_minmax_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp, _f, _i, _i, _vp]),
+    "fp8q_h16_route": (_i, [_i, _i64, _i64, _i, _f, _i, _i, _i, _i, ctypes.POINTER(H16RouteInfo)]),
     "fp8q_int_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _i64, _vp, _i, _i, _f, _vp]),
     "fp8q_int_range_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "fp8q_int_minmax_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp,

@@ -725,6 +725,34 @@ def rows_route(op, C, inner, per_channel=True, mbits=2, n_bits=8, sign_bits=1, x
     return r
 
 
+H16_KERNELS = ("k_h16_quant", "k_h16_quant_rows", "k_h16_minmax_rows", "k_h16_minmax_part")      # FP8Q_H16_K_*
+
+
+def h16_route(op, C, inner, per_channel=True, mbits=2, n_bits=8, sign_bits=1, x_mod16=0, y_dtype=torch.float32):
+    """The kernels quantize / minmax / minmax_quantize (op, one of ROWS_OPS) launch for a [C, inner] float16 / bfloat16 tensor
+    whose x sits at this address modulo 16 (fp8q_h16_route, include/fp8q.h); y_dtype: float32 or x's own dtype (both half
+    types take the same route).  A dict of the call's LAST kernel -- K1 for quantize and minmax_quantize, the scan for minmax:
+    kernel (a name of H16_KERNELS), u, nontemporal (bool), head, groups, tail, rows_per_chunk, lds_bytes, lanes, nsplit, grid_x,
+    grid_y, launches; what does not apply to the kernel is 0 -- plus "stages": the same dict for every kernel of the call in
+    launch order (minmax_quantize: the scan, then K1).  Host arithmetic only: needs no GPU.  Raises Fp8qError as the op's
+    entry would for the shape."""
+    import ctypes
+    from ._lib import H16LaunchInfo, H16RouteInfo
+    info = H16RouteInfo()
+    check(lib().fp8q_h16_route(ROWS_OPS.index(op), int(C), int(inner), int(bool(per_channel)), float(mbits), int(n_bits),
+                               int(sign_bits), int(x_mod16), _DT[y_dtype], ctypes.byref(info)), "fp8q_h16_route")
+    stages = []
+    for k in range(info.n_launches):
+        li = info.launch[k]
+        d = {name: int(getattr(li, name)) for name, _ in H16LaunchInfo._fields_ if name != "reserved"}
+        d["kernel"] = H16_KERNELS[li.kernel]
+        d["nontemporal"] = bool(d["nontemporal"])
+        stages.append(d)
+    r = dict(stages[-1])
+    r["stages"] = stages
+    return r
+
+
 _pct_ws_bytes = {}
 
 

@@ -767,6 +767,51 @@ int fp8q_minmax_quantize_h16(const void *x, void *y, int x_type, int y_type, int
                              fp8q_stream_t stream);
 
 /*
+ * Which kernels of the half lane a call reaches, and what its launcher chooses: the launchers' own plan code on host
+ * arithmetic alone -- nothing is launched, no GPU is needed.  op: FP8Q_ROWS_QUANTIZE / _MINMAX / _MINMAX_QUANTIZE (the three
+ * entries above; per_channel = 0: a per-tensor K1, for min/max the wrapper's one row [1, C * inner]; the fused entry is per
+ * channel only).  x_mod16: x's address modulo 16 (even); y_type: FP8Q_DT_F32 or a half type (then x's own).  Both half types
+ * take the same route.  info->n_launches kernels are described in launch order (two for the fused entry: the scan, then K1):
+ *   kernel          FP8Q_H16_K_* below
+ *   u, nontemporal  k_h16_quant: 16-byte groups in flight per lane (1 or 4; 4 from 2^20 groups on, unless the tables of a
+ *                   chunk's rows would outgrow 40 KiB of LDS) and the instance for tensors of 64 MiB and more, which
+ *                   exists for u = 4 only; k_h16_minmax_part: its nontemporal instance
+ *   head, groups, tail   k_h16_quant: the scalars in front of x's first 16-byte boundary, the 16-byte groups, the scalars behind
+ *   rows_per_chunk, lds_bytes   k_h16_quant: the rows a chunk of 2048 * u elements can overlap, and the bytes of their
+ *                   constants and tables ((16 + 8 (pmax + 1)) each)
+ *   lanes           k_h16_minmax_rows: lanes per row (1, 2, .. 64)
+ *   nsplit          k_h16_minmax_part: streaming blocks per row (grid_x has the reducer block on top when nsplit > 1)
+ *   grid_x, grid_y  of the first launch of this kernel
+ *   launches        k_h16_minmax_part: one per slab of 65535 rows; 1 elsewhere
+ * Fields that do not apply to the kernel are 0.  Errors as the entry reports them for the shape (FP8Q_EINVAL, FP8Q_EUNSUPPORTED,
+ * FP8Q_ETOOLONG), FP8Q_EINVAL also for op, x_mod16 or y_type out of range and for info NULL; `info` is written on FP8Q_OK only.
+ */
+#define FP8Q_H16_K_QUANT 0         /* k_h16_quant: the flat range in chunks, per-row tables in LDS */
+#define FP8Q_H16_K_QUANT_ROWS 1    /* k_h16_quant_rows: thread = row, no table */
+#define FP8Q_H16_K_MINMAX_ROWS 2   /* k_h16_minmax_rows: per-channel rows up to 2048 elements */
+#define FP8Q_H16_K_MINMAX_PART 3   /* k_h16_minmax_part: long rows, per tensor */
+typedef struct fp8q_h16_launch_info {
+    int kernel;
+    int u;
+    int nontemporal;
+    int lanes;
+    int nsplit;
+    int rows_per_chunk;
+    int launches;
+    int reserved;
+    int64_t head, groups, tail;
+    int64_t lds_bytes;
+    int64_t grid_x, grid_y;
+} fp8q_h16_launch_info;
+typedef struct fp8q_h16_route_info {
+    int n_launches;
+    int reserved;
+    fp8q_h16_launch_info launch[2];
+} fp8q_h16_route_info;
+int fp8q_h16_route(int op, int64_t C, int64_t inner, int per_channel, float mbits, int n_bits, int sign_bits, int x_mod16,
+                   int y_type, fp8q_h16_route_info *info);
+
+/*
  * The uniform (INT) quantizers on IEEE fp16 and bfloat16 tensors (csrc/fp8q_inth16.hip): fp8q_int_quantize_f32,
  * fp8q_int_range_quantize_f32 and fp8q_int_minmax_quantize_f32 with half x -- the argument lists of the _f32 twins, with
  * x_type / y_type (FP8Q_DT_*) behind x and y as in fp8q_quantize_h16.  Arithmetic contract:
