@@ -456,8 +456,9 @@ k_h16_int_decode(const void *__restrict__ codes, uint16_t *__restrict__ y, IntAr
 template <class T, int W, bool PC>
 void int_launch_k(bool encode, const void *in, void *out, const IntArgs &a, hipStream_t st)
 {
-    const dim3 g((unsigned)cdiv(a.n, kIntChunk)), b(kBlock);
-    const size_t shmem = (size_t)a.nc_max * sizeof(float4);
+    const IntPlan p = int_plan(a, false, 2);     // (these kernels have no nontemporal instance either)
+    const dim3 g(p.grid_x), b(kBlock);
+    const size_t shmem = p.lds_bytes;
     // elements in front of the 16-byte boundary of the side that is loaded 16 bytes at a time (a chunk starts a multiple of
     // 4096 elements behind it, so every chunk has that phase)
     const int lead = (int)((16 - ((uintptr_t)in & 15)) & 15);

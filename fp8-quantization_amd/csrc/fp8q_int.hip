@@ -257,7 +257,7 @@ int int_quant_launch(bool range, const float *x, float *y, int64_t C, int64_t in
 {
     const bool pc = a.C > 1;
     int_geometry(a, C, inner, pc);
-    const bool vec = (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+    const bool vec = int_vec16(x, y);
     if (range && pc) FP8Q_INT_LAUNCH(vec, x, y, a, st, k_int_quant, true, true);
     else if (range) FP8Q_INT_LAUNCH(vec, x, y, a, st, k_int_quant, true, false);
     else if (pc) FP8Q_INT_LAUNCH(vec, x, y, a, st, k_int_quant, false, true);
@@ -274,6 +274,38 @@ int fp8q_int_sign_launch(const float *xmin, int64_t C, unsigned char *sflag, hip
 }
 
 extern "C" {
+
+// What a chunked launch would be made with: the entry points' own steps -- int_check_x, int_geometry, int_sign_inline,
+// int_vec16, int_plan (fp8q_intq.h) -- on made-up addresses that have the caller's 16-byte phases and are never
+// dereferenced.  Host arithmetic only.
+int fp8q_chunk_route(int64_t C, int64_t inner, int64_t n_range, int elem_bytes, int in_mod16, int out_mod16, int symmetric,
+                     int sets_range, fp8q_chunk_route_info *info)
+{
+    if (!info || (elem_bytes != 4 && elem_bytes != 2) || in_mod16 < 0 || in_mod16 > 15 || out_mod16 < 0 || out_mod16 > 15)
+        return FP8Q_EINVAL;
+    const void *in = reinterpret_cast<const void *>(((uintptr_t)1 << 44) + (uintptr_t)in_mod16);
+    const void *out = reinterpret_cast<const void *>(((uintptr_t)1 << 45) + (uintptr_t)out_mod16);
+    if (int rc = int_check_x(in, out, C, inner, n_range)) return rc;
+    IntArgs a = {};
+    a.C = n_range;
+    a.symmetric = symmetric != 0;
+    const bool pc = a.C > 1;
+    int_geometry(a, C, inner, pc);
+    const IntPlan p = int_plan(a, int_vec16(in, out), elem_bytes);
+    fp8q_chunk_route_info r = {};
+    r.per_channel = pc;
+    r.rows_per_chunk = a.nc_max;
+    r.two_row = pc && a.inner >= kIntChunk;
+    r.vec = p.vec;
+    r.nontemporal = p.nt;
+    r.sign_prepass = sets_range && !int_sign_inline(a.symmetric, a.C);
+    r.magic = a.magic;
+    r.grid_x = p.grid_x;
+    r.lds_bytes = (int64_t)p.lds_bytes;
+    r.last_chunk = a.n - (int64_t)(p.grid_x - 1) * kIntChunk;
+    *info = r;
+    return FP8Q_OK;
+}
 
 int fp8q_int_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, const float *delta,
                           const float *zero_float, int64_t n_delta, const unsigned char *signed_flag, int n_bits,

@@ -177,7 +177,7 @@ int codec_launch(int mode, const void *in, void *out, int64_t C, int64_t inner, 
     const bool pc = n_delta > 1;
     int_geometry(a, C, inner, pc);
     // both sides on their vector word: 16 bytes, or (decode) a group's 4 W bytes of codes
-    const bool vec = mode == kDecode ? ((pout & 15) == 0 && (pin & (uintptr_t)(4 * W - 1)) == 0) : ((pin | pout) & 15) == 0;
+    const bool vec = mode == kDecode ? ((pout & 15) == 0 && (pin & (uintptr_t)(4 * W - 1)) == 0) : int_vec16(in, out);
     if (mode == kLevel) {
         if (pc) FP8Q_INT_LAUNCH(vec, in, out, a, st, k_int_level, true);
         else FP8Q_INT_LAUNCH(vec, in, out, a, st, k_int_level, false);

@@ -95,10 +95,11 @@ k_inth16_quant(const uint16_t *x, void *y, IntArgs a, int h)
 template <class T, bool YF32, bool RANGE, bool PC>
 void quant_launch_nt(const uint16_t *x, void *y, const IntArgs &a, hipStream_t st)
 {
-    const dim3 g((unsigned)cdiv(a.n, kIntChunk)), b(kBlock);
-    const size_t shmem = (size_t)a.nc_max * sizeof(float4);
+    const IntPlan p = int_plan(a, false, 2);
+    const dim3 g(p.grid_x), b(kBlock);
+    const size_t shmem = p.lds_bytes;
     const int h = (int)(((16 - ((uintptr_t)x & 15)) & 15) >> 1);   // elements in front of x's 16-byte boundary
-    if (a.n * 2 >= kNtBytes)
+    if (p.nt)
         hipLaunchKernelGGL((k_inth16_quant<T, YF32, RANGE, PC, true>), g, b, shmem, st, x, y, a, h);
     else
         hipLaunchKernelGGL((k_inth16_quant<T, YF32, RANGE, PC, false>), g, b, shmem, st, x, y, a, h);

@@ -5,7 +5,9 @@
 // chunked kernels (k_int_quant, k_inth16_quant, k_int_level, k_int_encode, k_int_decode): one aligned 4096-element chunk
 // per block, its prologue (sign, grid ends, the channel constants in LDS, the channel of an element by magic division),
 // the fp32 -> fp32 streaming loop, and the host side of their launch -- int_fixed_args(): the argument block of every
-// fixed-range entry point -- and pack_codes / code_at, the dwords of 1- and 2-byte codes.  Internal linkage, as fp8q_common.h.
+// fixed-range entry point, int_geometry() / int_sign_inline() / int_vec16() / int_plan(): the launch decisions, which the launches
+// consume and fp8q_chunk_route (fp8q_int.hip) reports -- and pack_codes / code_at, the dwords of 1- and 2-byte codes.  Internal
+// linkage, as fp8q_common.h.
 #pragma once
 #include "fp8q_common.h"
 
@@ -348,23 +350,48 @@ inline void int_geometry(IntArgs &a, int64_t C, int64_t inner, bool pc)
     a.nc_max = pc ? (int)(kIntChunk / inner + 2 < C ? kIntChunk / inner + 2 : C) : 1;
 }
 
-// RANGE launches of the symmetric per-channel case: the sign first when the blocks cannot fold it themselves
+// RANGE launches of the symmetric per-channel case: the blocks fold the sign themselves up to kSignInline entries
+inline bool int_sign_inline(int symmetric, int64_t C) { return !(symmetric && C > kSignInline); }
+
+// ... and the sign first when they cannot
 inline int int_sign_prepass(IntArgs &a, hipStream_t st)
 {
-    a.sign_inline = !(a.symmetric && a.C > kSignInline);
+    a.sign_inline = int_sign_inline(a.symmetric, a.C);
     if (a.sign_inline) return FP8Q_OK;
     return fp8q_int_sign_launch(a.a, a.C, a.sflag, st);
+}
+
+// both sides of a launch on a 16-byte boundary: what the VEC instances of the fp32 kernels need
+inline bool int_vec16(const void *in, const void *out) { return (((uintptr_t)in | (uintptr_t)out) & 15) == 0; }
+
+// What a chunked launch is made with, from int_geometry()'s block: one block per chunk, nc_max float4 of dynamic LDS, the
+// nontemporal instance from kNtBytes of the streamed tensor (elem_bytes per element: 4, or 2 on fp16 / bf16 tensors, whose
+// kernels walk from the 16-byte boundary and have no VEC instance).  FP8Q_INT_LAUNCH and the half launchers consume it;
+// fp8q_chunk_route reports it.
+struct IntPlan {
+    unsigned grid_x;
+    size_t lds_bytes;
+    bool vec, nt;
+};
+
+inline IntPlan int_plan(const IntArgs &a, bool vec, int elem_bytes)
+{
+    IntPlan p;
+    p.grid_x = (unsigned)cdiv(a.n, kIntChunk);
+    p.lds_bytes = (size_t)a.nc_max * sizeof(float4);
+    p.vec = vec && elem_bytes == 4;
+    p.nt = a.n * elem_bytes >= kNtBytes;
+    return p;
 }
 
 // One block per chunk of K<..., VEC, NT>(in, out, a).  vec: both sides on their vector word; NT from the tensor's size.
 #define FP8Q_INT_LAUNCH(vec, in, out, a, st, K, ...)                                                                   \
     do {                                                                                                              \
-        const dim3 g_((unsigned)cdiv((a).n, kIntChunk)), b_(kBlock);                                                  \
-        const size_t shmem_ = (size_t)(a).nc_max * sizeof(float4);                                                    \
-        const bool nt_ = (a).n * 4 >= kNtBytes;                                                                       \
-        if ((vec) && nt_) hipLaunchKernelGGL((K<__VA_ARGS__, true, true>), g_, b_, shmem_, st, in, out, a);          \
-        else if (vec) hipLaunchKernelGGL((K<__VA_ARGS__, true, false>), g_, b_, shmem_, st, in, out, a);             \
-        else hipLaunchKernelGGL((K<__VA_ARGS__, false, false>), g_, b_, shmem_, st, in, out, a);                     \
+        const IntPlan p_ = int_plan(a, vec, 4);                                                                       \
+        const dim3 g_(p_.grid_x), b_(kBlock);                                                                         \
+        if (p_.vec && p_.nt) hipLaunchKernelGGL((K<__VA_ARGS__, true, true>), g_, b_, p_.lds_bytes, st, in, out, a);  \
+        else if (p_.vec) hipLaunchKernelGGL((K<__VA_ARGS__, true, false>), g_, b_, p_.lds_bytes, st, in, out, a);     \
+        else hipLaunchKernelGGL((K<__VA_ARGS__, false, false>), g_, b_, p_.lds_bytes, st, in, out, a);                \
     } while (0)
 
 }  // namespace

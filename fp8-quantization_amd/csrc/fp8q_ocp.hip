@@ -163,7 +163,7 @@ k_ocp_scale(const float *__restrict__ maxval, float *__restrict__ scale, int64_t
 template <int MODE, int F, class IN, class OUT>
 void launch_io(const void *in, void *out, const IntArgs &a, bool pc, hipStream_t st)
 {
-    const bool vec = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
+    const bool vec = int_vec16(in, out);
     if (pc) FP8Q_INT_LAUNCH(vec, in, out, a, st, k_ocp, MODE, F, IN, OUT, true);
     else FP8Q_INT_LAUNCH(vec, in, out, a, st, k_ocp, MODE, F, IN, OUT, false);
 }

@@ -50,6 +50,13 @@ class CodecRouteInfo(ctypes.Structure):
                 ("grid_x", _i64), ("grid_y", _i64), ("steps", _i64)]
 
 
+class ChunkRouteInfo(ctypes.Structure):
+    """fp8q_chunk_route_info (include/fp8q.h): the launch geometry of a chunked INT / hardware-FP8 kernel"""
+    _fields_ = [("per_channel", _i), ("rows_per_chunk", _i), ("two_row", _i), ("vec", _i), ("nontemporal", _i),
+                ("sign_prepass", _i), ("magic", ctypes.c_uint32), ("reserved", _i), ("grid_x", _i64), ("lds_bytes", _i64),
+                ("last_chunk", _i64)]
+
+
 class H16LaunchInfo(ctypes.Structure):
     """fp8q_h16_launch_info (include/fp8q.h): one kernel of a half-lane call and its launcher's choices"""
     _fields_ = [("kernel", _i), ("u", _i), ("nontemporal", _i), ("lanes", _i), ("nsplit", _i), ("rows_per_chunk", _i),
@@ -134,6 +141,7 @@ SIGNATURES = {
     "fp8q_encode_u8": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _f, _i, _i, _vp]),
     "fp8q_decode_u8": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _f, _i, _i, _vp]),
     "fp8q_codec_route": (_i, [_i, _i64, _i64, _i64, _f, _i, _i, _i, _i, ctypes.POINTER(CodecRouteInfo)]),
+    "fp8q_chunk_route": (_i, [_i64, _i64, _i64, _i, _i, _i, _i, _i, ctypes.POINTER(ChunkRouteInfo)]),
     "fp8q_multi_quantize_f32": (_i, [ctypes.POINTER(TensorDesc), _i, _vp]),
     "fp8q_multi_minmax_quantize_f32": (_i, [ctypes.POINTER(TensorDesc), ctypes.POINTER(_vp), _i, _vp]),
     "fp8q_multi_encode_u8": (_i, [ctypes.POINTER(TensorDesc), _i, _vp]),

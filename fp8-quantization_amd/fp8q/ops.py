@@ -1587,6 +1587,24 @@ def codec_route(encode, C, inner, per_channel=True, mbits=2, n_bits=8, sign_bits
     return r
 
 
+def chunk_route(C, inner, per_channel=True, elem_bytes=4, in_mod16=0, out_mod16=0, symmetric=False, sets_range=False):
+    """The launch geometry of the chunked kernels -- the INT quantizers and codes, the hardware FP8 lane -- for a [C, inner]
+    tensor of elem_bytes per element (4; 2: the INT kernels on half tensors) whose input and output sit at these addresses
+    modulo 16 (fp8q_chunk_route, include/fp8q.h), as a dict: grid_x, rows_per_chunk, lds_bytes, magic, last_chunk (ints),
+    per_channel, two_row, vec, nontemporal, sign_prepass (bools).  Host arithmetic only: needs no GPU.  Raises Fp8qError as
+    the entries would for the shape."""
+    import ctypes
+    from ._lib import ChunkRouteInfo
+    info = ChunkRouteInfo()
+    check(lib().fp8q_chunk_route(int(C), int(inner), int(C) if per_channel else 1, int(elem_bytes), int(in_mod16),
+                                 int(out_mod16), int(bool(symmetric)), int(bool(sets_range)), ctypes.byref(info)),
+          "fp8q_chunk_route")
+    r = {name: int(getattr(info, name)) for name, _ in ChunkRouteInfo._fields_ if name != "reserved"}
+    for name in ("per_channel", "two_row", "vec", "nontemporal", "sign_prepass"):
+        r[name] = bool(r[name])
+    return r
+
+
 # ---- hardware FP8: OCP E4M3FN / E5M2 (csrc/fp8q_ocp.hip; the contract is in include/fp8q.h) ----
 _OCP_FMT = {torch.float8_e4m3fn: 0, torch.float8_e5m2: 1}          # FP8Q_OCP_* (include/fp8q.h)
 OCP_FMAX = {torch.float8_e4m3fn: 448.0, torch.float8_e5m2: 57344.0}

@@ -528,6 +528,47 @@ int fp8q_codec_route(int encode, int64_t C, int64_t inner, int64_t n_maxval, flo
                      int fp_mod16, int code_mod16, fp8q_codec_route_info *info);
 
 /*
+ * The launch geometry of the chunked kernels: the INT quantizers (fp8q_int_quantize_* / fp8q_int_range_quantize_*), the INT
+ * codes (fp8q_int_to_integer_f32, fp8q_int_encode*, fp8q_int_decode*) and the hardware FP8 lane (fp8q_ocp_*), which all give
+ * one aligned 4096-element chunk to a block and keep the constants of the rows overlapping it in dynamic LDS.  Host arithmetic
+ * only: no launch, no device -- the entries' own argument check, geometry, sign rule and launch plan, so that a test can
+ * assert the route before it trusts a shape.
+ *   C, inner, n_range   the tensor and its range vector, as the entries take them (n_range: 1 or C)
+ *   elem_bytes          of the streamed value tensor: 4, or 2 for the INT kernels on fp16 / bf16 tensors
+ *   in_mod16, out_mod16 the addresses of the launch's input and output modulo 16 (fp8q_int_decode's VEC instance is content
+ *                       with codes on a multiple of 4 bytes, 8 for 2-byte codes: pass 0 for such an address)
+ *   symmetric, sets_range   the quantizer's kind, and whether the launch sets the range (fp8q_int_range_quantize_*)
+ * Reported:
+ *   grid_x          blocks: chunks of the tensor
+ *   per_channel     n_range > 1; per tensor the kernels see one row
+ *   rows_per_chunk  LDS entries of a block: min(4096 / inner + 2, C), 1 per tensor
+ *   lds_bytes       16 * rows_per_chunk of dynamic LDS (above 64 KiB when inner == 1 and C > 4096)
+ *   magic           the multiplier that finds an element's row: floor(2^32 / inner) + 1; 0 when inner == 1 or per tensor
+ *   two_row         inner >= 4096: a chunk overlaps at most two rows and no division is made
+ *   vec             the 16-byte instance: both addresses 16-byte aligned, elem_bytes == 4 (the half kernels walk from x's own
+ *                   16-byte boundary instead)
+ *   nontemporal     the instance for tensors of 64 MiB and more (fp8q_int_encode_h16 / fp8q_int_decode_h16 have none)
+ *   sign_prepass    a range-setting symmetric launch of more than 2048 rows: k_int_sign folds the sign first; otherwise every
+ *                   block folds it itself
+ *   last_chunk      elements of the last chunk, 1..4096
+ * Errors as the entries report them for the shape: FP8Q_EINVAL (a size <= 0, n_range neither 1 nor C, a per-channel row or a
+ * chunk count beyond 32 bits; here also elem_bytes, a phase out of range or info NULL); `info` is written on FP8Q_OK only.
+ */
+typedef struct fp8q_chunk_route_info {
+    int per_channel;
+    int rows_per_chunk;
+    int two_row;
+    int vec;
+    int nontemporal;
+    int sign_prepass;
+    uint32_t magic;
+    int reserved;
+    int64_t grid_x, lds_bytes, last_chunk;
+} fp8q_chunk_route_info;
+int fp8q_chunk_route(int64_t C, int64_t inner, int64_t n_range, int elem_bytes, int in_mod16, int out_mod16, int symmetric,
+                     int sets_range, fp8q_chunk_route_info *info);
+
+/*
  * Multi-tensor K1 -- all weight tensors of a model in one launch: the reference quantizes
  * each layer's weight in that layer's forward (hijacker.py:70-108 -> quantize_weights), 21 tiny launches
  * for ResNet-18; with fixed ranges they are independent and can be enqueued together.
