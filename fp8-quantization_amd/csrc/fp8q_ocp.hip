@@ -47,6 +47,12 @@
 // HBM traffic per element: encode / decode 5 B (3 B on half tensors), quantize 8 B (4 B half to half).
 // Shared with fp8q_mx.hip through fp8q_io.h: the launch modes, the Io* element policies, Fp8Fmt (the conversion instructions)
 // and io_dispatch(), the (mode, in_type, out_type) ladder that ocp_launch ends in.
+//
+// SR (the fp8q_ocpsr_* entries; include/fp8q.h states the draw and the rounding): code = RNE(SR(q, r)) with q by the IEEE
+// division for every element (fp8q_ocpq.h says why) and r the 16-bit draw of the element's flat index offset + e.  A chunk
+// starts on a multiple of 4096 and offset is a multiple of 8, so an encoding lane's 16 elements are two whole Philox calls
+// and a quantizing lane's aligned group of 4 is half a call; the scalar tail and the unaligned route take one call per
+// element.  SR = false is the kernel as it was: its argument block is IntArgs, nothing of the draw is compiled in.
 #include "fp8q_common.h"
 #include "fp8q_intq.h"
 #include "fp8q_io.h"
@@ -73,11 +79,19 @@ struct ScaleGiven {
     __device__ __forceinline__ float4 operator()(int64_t row, bool) const { return make_float4(a.a[row], 0.0f, 0.0f, 0.0f); }
 };
 
+// the SR kernels' argument block: IntArgs and the call's seed and offset
+struct OcpSrArgs : IntArgs {
+    MxSr sr;
+};
+template <bool SR>
+using OcpArgs = std::conditional_t<SR, OcpSrArgs, IntArgs>;
+
 // IntArgs as this lane reads it: a = maxval (decode: scale), delta_out = scale_out or null, eps, the chunk geometry
-template <int MODE, int F, class IN, class OUT, bool PC, bool VEC, bool NT>
+template <int MODE, int F, class IN, class OUT, bool SR, bool PC, bool VEC, bool NT>
 __global__ void __launch_bounds__(kBlock)
-k_ocp(const void *__restrict__ in, void *__restrict__ out, IntArgs a)
+k_ocp(const void *__restrict__ in, void *__restrict__ out, OcpArgs<SR> a)
 {
+    static_assert(!SR || MODE != kDecode, "decode rounds nothing");
     typedef typename IN::elem in_t;
     typedef typename OUT::elem out_t;
     extern __shared__ float4 kc[];
@@ -97,11 +111,21 @@ k_ocp(const void *__restrict__ in, void *__restrict__ out, IntArgs a)
             float v[16];
             IN::template load16<NT>(x + c.e0 + off, v);
             uint32_t w[4];
+            uint32_t r[SR ? 16 : 1];
+            if constexpr (SR) {
+                const uint64_t i0 = a.sr.offset + (uint64_t)(c.e0 + off);       // a multiple of 8
+                uint32_t d[8];
+                mx_draw8(a.sr, i0, d);
+                mx_draw8(a.sr, i0 + 8u, d + 4);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) mx_split4(d + 2 * g, r + 4 * g);
+            }
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const float4 k[4] = {c.at<PC>(off + 4 * g), c.at<PC>(off + 4 * g + 1), c.at<PC>(off + 4 * g + 2),
                                      c.at<PC>(off + 4 * g + 3)};
-                w[g] = code4<F>(v + 4 * g, k);
+                if constexpr (SR) w[g] = code4_sr<F>(v + 4 * g, k, r + 4 * g);
+                else w[g] = code4<F>(v + 4 * g, k);
             }
             stv<NT>(reinterpret_cast<u4v *>(y + c.e0 + off), u4v{w[0], w[1], w[2], w[3]});
         }
@@ -114,7 +138,13 @@ k_ocp(const void *__restrict__ in, void *__restrict__ out, IntArgs a)
         const int ngroups = (int)((c.e1 - c.e0) >> 2);
         auto group = [&](const float *v, uint32_t w, int off) {
             const float4 k[4] = {c.at<PC>(off), c.at<PC>(off + 1), c.at<PC>(off + 2), c.at<PC>(off + 3)};
-            if constexpr (MODE == kQuant) w = code4<F>(v, k);
+            if constexpr (MODE == kQuant && SR) {
+                uint32_t r[4];
+                sr_draws4(a.sr, a.sr.offset + (uint64_t)(c.e0 + off), r);
+                w = code4_sr<F>(v, k, r);
+            } else if constexpr (MODE == kQuant) {
+                w = code4<F>(v, k);
+            }
             float r[4];
             value4<F>(w, k, r);
             OUT::template store4<NT>(y + c.e0 + off, r);
@@ -145,6 +175,7 @@ k_ocp(const void *__restrict__ in, void *__restrict__ out, IntArgs a)
         const float4 k = c.at<PC>((int)(e - c.e0));
         uint32_t code;
         if constexpr (MODE == kDecode) code = x[e];
+        else if constexpr (SR) code = code1_sr<F>(IN::load1(x + e), k, mx_draw1(a.sr, a.sr.offset + (uint64_t)e));
         else code = code1<F>(IN::load1(x + e), k);
         if constexpr (MODE == kEncode) y[e] = (uint8_t)code;
         else OUT::store1(y + e, value_at<F, 0>(code, k.x));
@@ -160,18 +191,19 @@ k_ocp_scale(const float *__restrict__ maxval, float *__restrict__ scale, int64_t
     if (i < n) scale[i] = t_max(maxval[i], eps) / OcpFmt<F>::fmax;
 }
 
-template <int MODE, int F, class IN, class OUT>
-void launch_io(const void *in, void *out, const IntArgs &a, bool pc, hipStream_t st)
+template <int MODE, int F, class IN, class OUT, bool SR>
+void launch_io(const void *in, void *out, const OcpArgs<SR> &a, bool pc, hipStream_t st)
 {
     const bool vec = int_vec16(in, out);
-    if (pc) FP8Q_INT_LAUNCH(vec, in, out, a, st, k_ocp, MODE, F, IN, OUT, true);
-    else FP8Q_INT_LAUNCH(vec, in, out, a, st, k_ocp, MODE, F, IN, OUT, false);
+    if (pc) FP8Q_INT_LAUNCH(vec, in, out, a, st, k_ocp, MODE, F, IN, OUT, SR, true);
+    else FP8Q_INT_LAUNCH(vec, in, out, a, st, k_ocp, MODE, F, IN, OUT, SR, false);
 }
 
 // Argument checks (everything is reported before the launch) and the one launch.  in_type / out_type: FP8Q_DT_* of the value
-// side(s), -1 for the side that holds codes.  range: maxval, or decode's scale.
+// side(s), -1 for the side that holds codes.  range: maxval, or decode's scale.  sr: the seed and offset of a
+// stochastic-rounding entry (encode, quantize), null for round to nearest even.
 int ocp_launch(int mode, const void *in, void *out, int in_type, int out_type, int64_t C, int64_t inner, const float *range,
-               int64_t n_range, int fmt, float eps, float *scale_out, hipStream_t st)
+               int64_t n_range, int fmt, float eps, float *scale_out, hipStream_t st, const MxSr *sr = nullptr)
 {
     if (int rc = int_check_x(in, out, C, inner, n_range)) return rc;
     if (!range) return FP8Q_EINVAL;
@@ -179,19 +211,32 @@ int ocp_launch(int mode, const void *in, void *out, int in_type, int out_type, i
     if (value_side_misaligned(in, in_type) || value_side_misaligned(out, out_type) || ((uintptr_t)range & 3) ||
         ((uintptr_t)scale_out & 3))
         return FP8Q_EINVAL;
+    if (sr && (sr->offset & 7u)) return FP8Q_EINVAL;
     const bool pc = n_range > 1;
-    IntArgs a = {};
+    OcpSrArgs a = {};
     a.a = range;
     a.eps = eps;
     a.delta_out = scale_out;
     a.C = n_range;
+    if (sr) a.sr = *sr;
     int_geometry(a, C, inner, pc);
     io_dispatch(mode, in_type, out_type, [&](auto m, auto ti, auto to) {
         constexpr int MODE = decltype(m)::value;
         typedef decltype(ti) IN;
         typedef decltype(to) OUT;
-        if (fmt == FP8Q_OCP_E4M3FN) launch_io<MODE, FP8Q_OCP_E4M3FN, IN, OUT>(in, out, a, pc, st);
-        else launch_io<MODE, FP8Q_OCP_E5M2, IN, OUT>(in, out, a, pc, st);
+        auto go = [&](auto sr_on) {
+            constexpr bool SR = decltype(sr_on)::value;
+            const OcpArgs<SR> &as = a;          // (the round-to-nearest-even kernels take the IntArgs part)
+            if (fmt == FP8Q_OCP_E4M3FN) launch_io<MODE, FP8Q_OCP_E4M3FN, IN, OUT, SR>(in, out, as, pc, st);
+            else launch_io<MODE, FP8Q_OCP_E5M2, IN, OUT, SR>(in, out, as, pc, st);
+        };
+        if constexpr (MODE != kDecode) {
+            if (sr) {
+                go(std::true_type{});
+                return;
+            }
+        }
+        go(std::false_type{});
     });
     return launch_rc();
 }
@@ -238,6 +283,39 @@ int fp8q_ocp_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_
 {
     if (int rc = check_types(x_type, y_type)) return rc;
     return ocp_launch(kQuant, x, y, x_type, y_type, C, inner, maxval, n_maxval, fmt, eps, nullptr, (hipStream_t)stream);
+}
+
+int fp8q_ocpsr_encode_f32(const float *x, uint8_t *codes, int64_t C, int64_t inner, const float *maxval, int64_t n_maxval,
+                          int fmt, float eps, float *scale_out, uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    const MxSr sr = mx_sr_args(seed, offset);
+    return ocp_launch(kEncode, x, codes, FP8Q_DT_F32, -1, C, inner, maxval, n_maxval, fmt, eps, scale_out, (hipStream_t)stream,
+                      &sr);
+}
+
+int fp8q_ocpsr_encode_h16(const void *x, uint8_t *codes, int x_type, int64_t C, int64_t inner, const float *maxval,
+                          int64_t n_maxval, int fmt, float eps, float *scale_out, uint64_t seed, uint64_t offset,
+                          fp8q_stream_t stream)
+{
+    if (!half_type(x_type)) return FP8Q_EINVAL;
+    const MxSr sr = mx_sr_args(seed, offset);
+    return ocp_launch(kEncode, x, codes, x_type, -1, C, inner, maxval, n_maxval, fmt, eps, scale_out, (hipStream_t)stream, &sr);
+}
+
+int fp8q_ocpsr_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, const float *maxval, int64_t n_maxval, int fmt,
+                            float eps, uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    const MxSr sr = mx_sr_args(seed, offset);
+    return ocp_launch(kQuant, x, y, FP8Q_DT_F32, FP8Q_DT_F32, C, inner, maxval, n_maxval, fmt, eps, nullptr,
+                      (hipStream_t)stream, &sr);
+}
+
+int fp8q_ocpsr_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t C, int64_t inner, const float *maxval,
+                            int64_t n_maxval, int fmt, float eps, uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    if (int rc = check_types(x_type, y_type)) return rc;
+    const MxSr sr = mx_sr_args(seed, offset);
+    return ocp_launch(kQuant, x, y, x_type, y_type, C, inner, maxval, n_maxval, fmt, eps, nullptr, (hipStream_t)stream, &sr);
 }
 
 int fp8q_ocp_scale_f32(const float *maxval, int64_t n, int fmt, float eps, float *scale, fp8q_stream_t stream)

@@ -42,6 +42,13 @@
 // anything else goes element by element.
 // NT: nontemporal loads and stores from 64 MiB of values (kNtBytes), the sibling kernels' rule.  One launch per call, nothing
 // read back, no allocation, no workspace.
+//
+// SR, the trailing template parameter of the three encoding kernels (the fp8q_ocpbsr_* entries; include/fp8q.h states the draw
+// and the rounding): code = RNE(SR(q, r)), q by the IEEE division for every element (fp8q_ocpq.h says why), r the draw of the
+// element's flat index offset + row K + col in x.  A lane's group of 4 columns starts on a multiple of 4 on the rows and panel
+// routes (K % 4 == 0), so it is half a Philox call, drawn where the group is converted -- nothing of it is live across the
+// range reduction; the plain route takes one call per element.  SR = false is the kernel as it was, argument block included.
+// Registers, scratch (none) and occupancy of both: profiles/ocp_sr_resources.txt.
 #include "fp8q_common.h"
 #include "fp8q_io.h"
 #include "fp8q_mxq.h"       // abs_bits, umax4, umax_xor: the MX lane's integer maxima
@@ -66,6 +73,13 @@ struct OcpbArgs {
     float eps;
 };
 
+// the SR kernels' argument block: OcpbArgs and the call's seed and offset
+struct OcpbSrArgs : OcpbArgs {
+    MxSr sr;
+};
+template <bool SR>
+using OcpbArgsOf = std::conditional_t<SR, OcpbSrArgs, OcpbArgs>;
+
 __device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
 template <int STEP>
@@ -75,9 +89,9 @@ __device__ __forceinline__ uint32_t umax_shfl(uint32_t m)
 }
 
 // ---- 1x128 tiles of a flat run of whole tiles ----
-template <int MODE, int F, class IN, class OUT, bool NT>
+template <int MODE, int F, class IN, class OUT, bool NT, bool SR>
 __global__ void __launch_bounds__(kBlock)
-k_ocpb_rows(const void *__restrict__ in, void *__restrict__ out, OcpbArgs a)
+k_ocpb_rows(const void *__restrict__ in, void *__restrict__ out, OcpbArgsOf<SR> a)
 {
     typedef typename IN::elem in_t;
     typedef typename OUT::elem out_t;
@@ -106,9 +120,11 @@ k_ocpb_rows(const void *__restrict__ in, void *__restrict__ out, OcpbArgs a)
         m = umax_shfl<16>(m);
         const float4 k = ocp_scale_pair<F>(__uint_as_float(m), a.eps);
         const float4 k4[4] = {k, k, k, k};
-        const uint32_t w = code4<F>(v[u], k4);
-        sc[u] = k.x;
         const int64_t e = base + u * 256 + 4 * lane;
+        uint32_t w;
+        if constexpr (SR) w = code4_sr_at<F>(a.sr, v[u], k4, e);
+        else w = code4<F>(v[u], k4);
+        sc[u] = k.x;
         if constexpr (MODE == kEncode) {
             if (live[u]) stv<NT>(reinterpret_cast<uint32_t *>(y + e), w);
         } else {
@@ -131,9 +147,9 @@ k_ocpb_rows(const void *__restrict__ in, void *__restrict__ out, OcpbArgs a)
 }
 
 // ---- 128x1 and 128x128 tiles: a panel of 128 x 128 per workgroup, in registers ----
-template <int MODE, int F, class IN, class OUT, int TILE, bool NT>
+template <int MODE, int F, class IN, class OUT, int TILE, bool NT, bool SR>
 __global__ void __launch_bounds__(kBlock)
-k_ocpb_panel(const void *__restrict__ in, void *__restrict__ out, OcpbArgs a)
+k_ocpb_panel(const void *__restrict__ in, void *__restrict__ out, OcpbArgsOf<SR> a)
 {
     typedef typename IN::elem in_t;
     typedef typename OUT::elem out_t;
@@ -196,7 +212,9 @@ k_ocpb_panel(const void *__restrict__ in, void *__restrict__ out, OcpbArgs a)
 #pragma unroll
     for (int i = 0; i < kPanelLoads; ++i) {
         const int64_t row = r0 + 8 * i;
-        const uint32_t w = code4<F>(v[i], k4);
+        uint32_t w;
+        if constexpr (SR) w = code4_sr_at<F>(a.sr, v[i], k4, row * a.K + c);
+        else w = code4<F>(v[i], k4);
         if constexpr (MODE == kEncode) {
             if (col_live && row < a.R) stv<NT>(reinterpret_cast<uint32_t *>(y + row * a.K + c), w);
         } else {
@@ -208,9 +226,9 @@ k_ocpb_panel(const void *__restrict__ in, void *__restrict__ out, OcpbArgs a)
 }
 
 // ---- the general route: one wave per tile, element by element ----
-template <int MODE, int F, class IN, class OUT>
+template <int MODE, int F, class IN, class OUT, bool SR>
 __global__ void __launch_bounds__(kBlock)
-k_ocpb_plain(const void *__restrict__ in, void *__restrict__ out, OcpbArgs a)
+k_ocpb_plain(const void *__restrict__ in, void *__restrict__ out, OcpbArgsOf<SR> a)
 {
     typedef typename IN::elem in_t;
     typedef typename OUT::elem out_t;
@@ -239,7 +257,9 @@ k_ocpb_plain(const void *__restrict__ in, void *__restrict__ out, OcpbArgs a)
     for (int e = lane; e < n; e += 64) {
         const int i = e / wd, j = e - i * wd;
         const int64_t at = (r0 + i) * a.K + c0 + j;
-        const uint32_t code = code1<F>(IN::load1(x + at), k);
+        uint32_t code;
+        if constexpr (SR) code = code1_sr<F>(IN::load1(x + at), k, mx_draw1(a.sr, a.sr.offset + (uint64_t)at));
+        else code = code1<F>(IN::load1(x + at), k);
         if constexpr (MODE == kEncode) y[at] = (uint8_t)code;
         else OUT::store1(y + at, value_at<F, 0>(code, k.x));
     }
@@ -327,19 +347,22 @@ int ocpb_route(int64_t R, int64_t K, int tr, int tk, int x_type, int aligned16)
 }
 
 // Argument checks (everything is reported before the launch) and the one launch.  in_type / out_type: FP8Q_DT_* of the value
-// side(s), -1 for the side that holds codes.  scales: encode's output, decode's input, null for quantize.
+// side(s), -1 for the side that holds codes.  scales: encode's output, decode's input, null for quantize.  sr: the seed and
+// offset of a stochastic-rounding entry (encode, quantize), null for round to nearest even.
 int ocpb_launch(int mode, const void *in, void *out, float *scales, int in_type, int out_type, int64_t R, int64_t K, int tr,
-                int tk, int fmt, float eps, hipStream_t st)
+                int tk, int fmt, float eps, hipStream_t st, const MxSr *sr = nullptr)
 {
     if (!in || !out || (mode != kQuant && !scales) || R <= 0 || K <= 0 || R > INT64_MAX / K) return FP8Q_EINVAL;
     const int kind = tile_kind(tr, tk);
     if ((fmt != FP8Q_OCP_E4M3FN && fmt != FP8Q_OCP_E5M2) || kind < 0) return FP8Q_EUNSUPPORTED;
     if (value_side_misaligned(in, in_type) || value_side_misaligned(out, out_type) || ((uintptr_t)scales & 3))
         return FP8Q_EINVAL;
+    if (sr && (sr->offset & 7u)) return FP8Q_EINVAL;
     const bool aligned16 = (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
     const int64_t n = R * K;
     const bool nt = n >= kNtBytes / 4;
-    OcpbArgs a = {};
+    OcpbSrArgs a = {};
+    if (sr) a.sr = *sr;
     a.scales = scales;
     a.R = R;
     a.K = K;
@@ -380,20 +403,27 @@ int ocpb_launch(int mode, const void *in, void *out, float *scales, int in_type,
             constexpr int F = decltype(fc)::value;
             if constexpr (MODE == kDecode) {
                 const uint8_t *c = static_cast<const uint8_t *>(in);
-                if (!route) hipLaunchKernelGGL((k_ocpb_decode<F, OUT, false, false>), g, b, 0, st, c, out, a);
-                else if (nt) hipLaunchKernelGGL((k_ocpb_decode<F, OUT, true, true>), g, b, 0, st, c, out, a);
-                else hipLaunchKernelGGL((k_ocpb_decode<F, OUT, true, false>), g, b, 0, st, c, out, a);
-            } else if (route == FP8Q_OCPB_PLAIN) {
-                hipLaunchKernelGGL((k_ocpb_plain<MODE, F, IN, OUT>), g, b, 0, st, in, out, a);
+                const OcpbArgs &ad = a;
+                if (!route) hipLaunchKernelGGL((k_ocpb_decode<F, OUT, false, false>), g, b, 0, st, c, out, ad);
+                else if (nt) hipLaunchKernelGGL((k_ocpb_decode<F, OUT, true, true>), g, b, 0, st, c, out, ad);
+                else hipLaunchKernelGGL((k_ocpb_decode<F, OUT, true, false>), g, b, 0, st, c, out, ad);
             } else {
-                dispatch<true, false>(nt, [&](auto ntc) {
-                    constexpr bool NT = decltype(ntc)::value;
-                    if (route == FP8Q_OCPB_ROWS)
-                        hipLaunchKernelGGL((k_ocpb_rows<MODE, F, IN, OUT, NT>), g, b, 0, st, in, out, a);
-                    else if (kind == kTileCol)
-                        hipLaunchKernelGGL((k_ocpb_panel<MODE, F, IN, OUT, kTileCol, NT>), g, b, 0, st, in, out, a);
-                    else
-                        hipLaunchKernelGGL((k_ocpb_panel<MODE, F, IN, OUT, kTileFull, NT>), g, b, 0, st, in, out, a);
+                dispatch<true, false>(sr != nullptr, [&](auto src) {
+                    constexpr bool SR = decltype(src)::value;
+                    const OcpbArgsOf<SR> &as = a;       // (the round-to-nearest-even kernels take the OcpbArgs part)
+                    if (route == FP8Q_OCPB_PLAIN) {
+                        hipLaunchKernelGGL((k_ocpb_plain<MODE, F, IN, OUT, SR>), g, b, 0, st, in, out, as);
+                        return;
+                    }
+                    dispatch<true, false>(nt, [&](auto ntc) {
+                        constexpr bool NT = decltype(ntc)::value;
+                        if (route == FP8Q_OCPB_ROWS)
+                            hipLaunchKernelGGL((k_ocpb_rows<MODE, F, IN, OUT, NT, SR>), g, b, 0, st, in, out, as);
+                        else if (kind == kTileCol)
+                            hipLaunchKernelGGL((k_ocpb_panel<MODE, F, IN, OUT, kTileCol, NT, SR>), g, b, 0, st, in, out, as);
+                        else
+                            hipLaunchKernelGGL((k_ocpb_panel<MODE, F, IN, OUT, kTileFull, NT, SR>), g, b, 0, st, in, out, as);
+                    });
                 });
             }
         });
@@ -449,6 +479,37 @@ int fp8q_ocpb_quantize_h16(const void *x, void *y, int x_type, int y_type, int64
 {
     if (int rc = check_types(x_type, y_type)) return rc;
     return ocpb_launch(kQuant, x, y, nullptr, x_type, y_type, R, K, tile_r, tile_k, fmt, eps, (hipStream_t)stream);
+}
+
+int fp8q_ocpbsr_encode_f32(const float *x, uint8_t *codes, float *scales, int64_t R, int64_t K, int tile_r, int tile_k, int fmt,
+                           float eps, uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    const MxSr sr = mx_sr_args(seed, offset);
+    return ocpb_launch(kEncode, x, codes, scales, FP8Q_DT_F32, -1, R, K, tile_r, tile_k, fmt, eps, (hipStream_t)stream, &sr);
+}
+
+int fp8q_ocpbsr_encode_h16(const void *x, uint8_t *codes, float *scales, int x_type, int64_t R, int64_t K, int tile_r,
+                           int tile_k, int fmt, float eps, uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    if (!half_type(x_type)) return FP8Q_EINVAL;
+    const MxSr sr = mx_sr_args(seed, offset);
+    return ocpb_launch(kEncode, x, codes, scales, x_type, -1, R, K, tile_r, tile_k, fmt, eps, (hipStream_t)stream, &sr);
+}
+
+int fp8q_ocpbsr_quantize_f32(const float *x, float *y, int64_t R, int64_t K, int tile_r, int tile_k, int fmt, float eps,
+                             uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    const MxSr sr = mx_sr_args(seed, offset);
+    return ocpb_launch(kQuant, x, y, nullptr, FP8Q_DT_F32, FP8Q_DT_F32, R, K, tile_r, tile_k, fmt, eps, (hipStream_t)stream,
+                       &sr);
+}
+
+int fp8q_ocpbsr_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int tile_r, int tile_k,
+                             int fmt, float eps, uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    if (int rc = check_types(x_type, y_type)) return rc;
+    const MxSr sr = mx_sr_args(seed, offset);
+    return ocpb_launch(kQuant, x, y, nullptr, x_type, y_type, R, K, tile_r, tile_k, fmt, eps, (hipStream_t)stream, &sr);
 }
 
 }  // extern "C"

@@ -59,6 +59,17 @@
 // NT: nontemporal loads and stores from 64 MiB of values (kNtBytes), the lane's rule.  One launch per call, nothing read back, no
 // allocation, no workspace.  Registers, scratch (none) and occupancy of every instantiation: profiles/ocp_block_t_resources.txt.
 // gfx950's scaled conversions are not used, for the reason fp8q_ocp.hip gives.
+//
+// SR, the trailing template parameter of both kernels (the fp8q_ocpbtsr_* entries; include/fp8q.h states the draw and the
+// rounding): code = RNE(SR(q, r)), q by the IEEE division for every element (fp8q_ocpq.h says why), r the draw of the element's
+// flat index offset + row K + col in x AS IT LIES, whichever orientation the code is stored in.  On the panel route a lane's 4
+// columns of one row are an aligned group of four flat indices, half a Philox call.  (128, 128): the codes are still made once,
+// row-wise, each word under its row's draws.  (1, 128): a transposed word holds one column of four ROWS, so the draws of the
+// four rows 4 h .. 4 h + 3 (four half calls, 16 draws) are made once per h and serve the lane's four columns -- the loop runs h
+// outside, j inside, where the kernel without SR runs j outside.  encode_both converts and stores the row-wise half first and
+// draws again for the transposed half (the same draws: the draw belongs to the element), so the 32 words of a lane's draws are
+// never held next to its 64 values.  The plain route takes one call per element.  SR = false is the kernel as it was,
+// argument block included.  Registers, scratch (none) and occupancy of both: profiles/ocp_sr_resources.txt.
 #include "fp8q_common.h"
 #include "fp8q_io.h"
 #include "fp8q_mxq.h"       // abs_bits, umax4, umax_xor: the MX lane's integer maxima
@@ -83,6 +94,13 @@ struct OcpbtArgs {
     int gran;                           // bytes per store of transposed codes: 16, 4 or 1
     float eps;
 };
+
+// the SR kernels' argument block: OcpbtArgs and the call's seed and offset
+struct OcpbtSrArgs : OcpbtArgs {
+    MxSr sr;
+};
+template <bool SR>
+using OcpbtArgsOf = std::conditional_t<SR, OcpbtSrArgs, OcpbtArgs>;
 
 __device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
@@ -111,9 +129,9 @@ __device__ __forceinline__ void store_runs(const uint32_t *s, uint8_t *dst, int6
 }
 
 // ---- the panel route ----
-template <int OP, int F, class IN, int TILE, bool NT>
+template <int OP, int F, class IN, int TILE, bool NT, bool SR>
 __global__ void __launch_bounds__(kBlock)
-k_ocpbt_panel(const void *__restrict__ in, OcpbtArgs a)
+k_ocpbt_panel(const void *__restrict__ in, OcpbtArgsOf<SR> a)
 {
     typedef typename IN::elem in_t;
     __shared__ uint32_t s_codes[8 * kGroupPitch];
@@ -158,7 +176,8 @@ k_ocpbt_panel(const void *__restrict__ in, OcpbtArgs a)
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 const int i = 4 * h + p;
-                w[p] = code4<F>(v[i], k4);
+                if constexpr (SR) w[p] = code4_sr_at<F>(a.sr, v[i], k4, (row0 + i) * a.K + c);
+                else w[p] = code4<F>(v[i], k4);
                 if constexpr (OP == kOpBoth) {
                     const int64_t row = row0 + i;
                     if (col_live && row < a.R) stv<NT>(reinterpret_cast<uint32_t *>(a.codes + row * a.K + c), w[p]);
@@ -198,8 +217,10 @@ k_ocpbt_panel(const void *__restrict__ in, OcpbtArgs a)
                 m = umax_shfl<16>(m);
                 const float4 k = ocp_scale_pair<F>(__uint_as_float(m), a.eps);
                 const float4 k4[4] = {k, k, k, k};
-                const uint32_t w = code4<F>(v[i], k4);
                 const int64_t row = row0 + i;
+                uint32_t w;
+                if constexpr (SR) w = code4_sr_at<F>(a.sr, v[i], k4, row * a.K + c);
+                else w = code4<F>(v[i], k4);
                 if (row < a.R) {
                     if (col_live) stv<NT>(reinterpret_cast<uint32_t *>(a.codes + row * a.K + c), w);
                     if (cg == 0) a.scales[row * a.nK + pc] = k.x;
@@ -207,15 +228,37 @@ k_ocpbt_panel(const void *__restrict__ in, OcpbtArgs a)
             }
         }
         __syncthreads();
+        if constexpr (SR) {
+            float4 kc[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float2 kj = s_k[4 * cg + j];
-            const float4 k = make_float4(kj.x, kj.y, 0.0f, 0.0f);
-            const float4 k4[4] = {k, k, k, k};
+            for (int j = 0; j < 4; ++j) {
+                const float2 kj = s_k[4 * cg + j];
+                kc[j] = make_float4(kj.x, kj.y, 0.0f, 0.0f);
+            }
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
-                const float t[4] = {v[4 * h][j], v[4 * h + 1][j], v[4 * h + 2][j], v[4 * h + 3][j]};
-                mine[4 * j + h] = code4<F>(t, k4);
+                uint32_t r[4][4];               // [row 4 h + p][column j]
+#pragma unroll
+                for (int p = 0; p < 4; ++p) sr_draws4(a.sr, a.sr.offset + (uint64_t)((row0 + 4 * h + p) * a.K + c), r[p]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float4 k4[4] = {kc[j], kc[j], kc[j], kc[j]};
+                    const float t[4] = {v[4 * h][j], v[4 * h + 1][j], v[4 * h + 2][j], v[4 * h + 3][j]};
+                    const uint32_t rt[4] = {r[0][j], r[1][j], r[2][j], r[3][j]};
+                    mine[4 * j + h] = code4_sr<F>(t, k4, rt);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float2 kj = s_k[4 * cg + j];
+                const float4 k = make_float4(kj.x, kj.y, 0.0f, 0.0f);
+                const float4 k4[4] = {k, k, k, k};
+#pragma unroll
+                for (int h = 0; h < 4; ++h) {
+                    const float t[4] = {v[4 * h][j], v[4 * h + 1][j], v[4 * h + 2][j], v[4 * h + 3][j]};
+                    mine[4 * j + h] = code4<F>(t, k4);
+                }
             }
         }
     }
@@ -229,9 +272,9 @@ k_ocpbt_panel(const void *__restrict__ in, OcpbtArgs a)
 }
 
 // ---- the general route: one wave per tile, element by element ----
-template <int OP, int F, class IN, int TILE>
+template <int OP, int F, class IN, int TILE, bool SR>
 __global__ void __launch_bounds__(kBlock)
-k_ocpbt_plain(const void *__restrict__ in, OcpbtArgs a)
+k_ocpbt_plain(const void *__restrict__ in, OcpbtArgsOf<SR> a)
 {
     typedef typename IN::elem in_t;
     const in_t *x = static_cast<const in_t *>(in);
@@ -279,7 +322,9 @@ k_ocpbt_plain(const void *__restrict__ in, OcpbtArgs a)
     for (int e = lane; e < n; e += 64) {
         const int i = e / wd, j = e - i * wd;
         const int64_t at = (r0 + i) * a.K + c0 + j;
-        const uint8_t code = (uint8_t)code1<F>(IN::load1(x + at), k);
+        uint8_t code;
+        if constexpr (SR) code = (uint8_t)code1_sr<F>(IN::load1(x + at), k, mx_draw1(a.sr, a.sr.offset + (uint64_t)at));
+        else code = (uint8_t)code1<F>(IN::load1(x + at), k);
         if (rowwise) {
             a.codes[at] = code;
         } else {
@@ -313,21 +358,24 @@ int ocpbt_route(int64_t R, int64_t K, int tr, int tk, int x_type, int aligned16,
 }
 
 // Argument checks (everything is reported before the launch, in ocpb_launch's order and with its codes) and the one launch.
-// codes / scales: the row-wise operands of encode_both, null for encode_t.
+// codes / scales: the row-wise operands of encode_both, null for encode_t.  sr: the seed and offset of a stochastic-rounding
+// entry, null for round to nearest even.
 template <int OP>
 int ocpbt_launch(const void *x, uint8_t *codes, float *scales, uint8_t *codes_t, float *scales_t, int x_type, int64_t R,
-                 int64_t K, int tr, int tk, int fmt, float eps, hipStream_t st)
+                 int64_t K, int tr, int tk, int fmt, float eps, hipStream_t st, const MxSr *sr = nullptr)
 {
     if (!x || !codes_t || !scales_t || (OP == kOpBoth && (!codes || !scales)) || R <= 0 || K <= 0 || R > INT64_MAX / K)
         return FP8Q_EINVAL;
     const int kind = tile_kind(tr, tk);
     if ((fmt != FP8Q_OCP_E4M3FN && fmt != FP8Q_OCP_E5M2) || kind < 0) return FP8Q_EUNSUPPORTED;
     if (value_side_misaligned(x, x_type) || (((uintptr_t)scales | (uintptr_t)scales_t) & 3)) return FP8Q_EINVAL;
+    if (sr && (sr->offset & 7u)) return FP8Q_EINVAL;
     const uintptr_t ptrs = (uintptr_t)x | (uintptr_t)codes | (uintptr_t)scales | (uintptr_t)codes_t | (uintptr_t)scales_t;
     fp8q_ocpbt_route_info route;                // (encode_t passes null for what it does not take)
     if (int rc = ocpbt_route(R, K, tr, tk, x_type, (ptrs & 15) == 0, &route)) return rc;
     const bool panel = route.kernel == FP8Q_OCPBT_PANEL;
-    OcpbtArgs a = {};
+    OcpbtSrArgs a = {};
+    if (sr) a.sr = *sr;
     a.codes = codes;
     a.codes_t = codes_t;
     a.scales = scales;
@@ -358,14 +406,18 @@ int ocpbt_launch(const void *x, uint8_t *codes, float *scales, uint8_t *codes_t,
             constexpr int F = decltype(fc)::value;
             dispatch<(int)kTileRow, (int)kTileFull>(kind, [&](auto tc) {
                 constexpr int TILE = decltype(tc)::value;
-                if (!panel) {
-                    hipLaunchKernelGGL((k_ocpbt_plain<OP, F, IN, TILE>), g, b, 0, st, x, a);
-                } else {
-                    dispatch<true, false>(route.nontemporal != 0, [&](auto ntc) {
-                        constexpr bool NT = decltype(ntc)::value;
-                        hipLaunchKernelGGL((k_ocpbt_panel<OP, F, IN, TILE, NT>), g, b, 0, st, x, a);
-                    });
-                }
+                dispatch<true, false>(sr != nullptr, [&](auto src) {
+                    constexpr bool SR = decltype(src)::value;
+                    const OcpbtArgsOf<SR> &as = a;      // (the round-to-nearest-even kernels take the OcpbtArgs part)
+                    if (!panel) {
+                        hipLaunchKernelGGL((k_ocpbt_plain<OP, F, IN, TILE, SR>), g, b, 0, st, x, as);
+                    } else {
+                        dispatch<true, false>(route.nontemporal != 0, [&](auto ntc) {
+                            constexpr bool NT = decltype(ntc)::value;
+                            hipLaunchKernelGGL((k_ocpbt_panel<OP, F, IN, TILE, NT, SR>), g, b, 0, st, x, as);
+                        });
+                    }
+                });
             });
         });
     });
@@ -409,6 +461,42 @@ int fp8q_ocpbt_encode_both_h16(const void *x, uint8_t *codes, float *scales, uin
     if (!half_type(x_type)) return FP8Q_EINVAL;
     return ocpbt_launch<kOpBoth>(x, codes, scales, codes_t, scales_t, x_type, R, K, tile_r, tile_k, fmt, eps,
                                  (hipStream_t)stream);
+}
+
+int fp8q_ocpbtsr_encode_f32(const float *x, uint8_t *codes_t, float *scales_t, int64_t R, int64_t K, int tile_r, int tile_k,
+                            int fmt, float eps, uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    const MxSr sr = mx_sr_args(seed, offset);
+    return ocpbt_launch<kOpT>(x, nullptr, nullptr, codes_t, scales_t, FP8Q_DT_F32, R, K, tile_r, tile_k, fmt, eps,
+                              (hipStream_t)stream, &sr);
+}
+
+int fp8q_ocpbtsr_encode_h16(const void *x, uint8_t *codes_t, float *scales_t, int x_type, int64_t R, int64_t K, int tile_r,
+                            int tile_k, int fmt, float eps, uint64_t seed, uint64_t offset, fp8q_stream_t stream)
+{
+    if (!half_type(x_type)) return FP8Q_EINVAL;
+    const MxSr sr = mx_sr_args(seed, offset);
+    return ocpbt_launch<kOpT>(x, nullptr, nullptr, codes_t, scales_t, x_type, R, K, tile_r, tile_k, fmt, eps,
+                              (hipStream_t)stream, &sr);
+}
+
+int fp8q_ocpbtsr_encode_both_f32(const float *x, uint8_t *codes, float *scales, uint8_t *codes_t, float *scales_t, int64_t R,
+                                 int64_t K, int tile_r, int tile_k, int fmt, float eps, uint64_t seed, uint64_t offset,
+                                 fp8q_stream_t stream)
+{
+    const MxSr sr = mx_sr_args(seed, offset);
+    return ocpbt_launch<kOpBoth>(x, codes, scales, codes_t, scales_t, FP8Q_DT_F32, R, K, tile_r, tile_k, fmt, eps,
+                                 (hipStream_t)stream, &sr);
+}
+
+int fp8q_ocpbtsr_encode_both_h16(const void *x, uint8_t *codes, float *scales, uint8_t *codes_t, float *scales_t, int x_type,
+                                 int64_t R, int64_t K, int tile_r, int tile_k, int fmt, float eps, uint64_t seed,
+                                 uint64_t offset, fp8q_stream_t stream)
+{
+    if (!half_type(x_type)) return FP8Q_EINVAL;
+    const MxSr sr = mx_sr_args(seed, offset);
+    return ocpbt_launch<kOpBoth>(x, codes, scales, codes_t, scales_t, x_type, R, K, tile_r, tile_k, fmt, eps,
+                                 (hipStream_t)stream, &sr);
 }
 
 }  // extern "C"

@@ -230,6 +230,18 @@ SIGNATURES = {
     "fp8q_mxsr_encode_both_h16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i, _i, _u64, _u64, _vp]),
     "fp8q_mxsr_quantize_t_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _u64, _u64, _vp]),
     "fp8q_mxsr_quantize_t_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _i, _u64, _u64, _vp]),
+    "fp8q_ocpsr_encode_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _f, _vp, _u64, _u64, _vp]),
+    "fp8q_ocpsr_encode_h16": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _i64, _i, _f, _vp, _u64, _u64, _vp]),
+    "fp8q_ocpsr_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _f, _u64, _u64, _vp]),
+    "fp8q_ocpsr_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _i64, _i, _f, _u64, _u64, _vp]),
+    "fp8q_ocpbsr_encode_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _i, _f, _u64, _u64, _vp]),
+    "fp8q_ocpbsr_encode_h16": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _i, _f, _u64, _u64, _vp]),
+    "fp8q_ocpbsr_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _i, _f, _u64, _u64, _vp]),
+    "fp8q_ocpbsr_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _i, _i, _f, _u64, _u64, _vp]),
+    "fp8q_ocpbtsr_encode_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _i, _f, _u64, _u64, _vp]),
+    "fp8q_ocpbtsr_encode_h16": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _i, _f, _u64, _u64, _vp]),
+    "fp8q_ocpbtsr_encode_both_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _f, _u64, _u64, _vp]),
+    "fp8q_ocpbtsr_encode_both_h16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i, _i, _i, _f, _u64, _u64, _vp]),
 }
 
 

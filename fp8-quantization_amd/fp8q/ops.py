@@ -1640,14 +1640,26 @@ def ocp_scale(maxval, fmt, eps=1e-8):
     return scale
 
 
-def ocp_encode(x, maxval, fmt, eps=1e-8, out=None, want_scale=True):
+def _ocp_sr(seed, offset):
+    """(entry prefix suffix, trailing arguments) of an OCP call: ("", ()) for seed=None, ("sr", (seed, offset)) otherwise;
+    checked as _mx_sr checks them, from the arguments alone, so raised before the device check"""
+    sr = _mx_sr(seed, offset)
+    return ("sr" if sr else ""), sr
+
+
+def ocp_encode(x, maxval, fmt, eps=1e-8, out=None, want_scale=True, *, seed=None, offset=0):
     """Hardware FP8 codes of x: (codes, scale).  fmt: torch.float8_e4m3fn or torch.float8_e5m2; maxval [1] or [C] CUDA float32.
     scale = max(maxval, eps) / fmax, codes = RNE(clamp(x / scale, -fmax, fmax)) as OCP bytes -- what
     torch.clamp(x / scale, -fmax, fmax).to(fmt) gives on the CPU, every NaN as 0x7F.  codes is a tensor of dtype `fmt` shaped
     like x (a view of the uint8 buffer the kernel wrote; `out`: a contiguous uint8 or `fmt` tensor), scale float32 [1] or [C]
     (None with want_scale=False).  x float32, or float16 / bfloat16 (widened exactly: the codes of x.float()).  One launch.
-    Dynamic scaling is minmax(x, per_channel, want_maxval=True) followed by this call."""
+    Dynamic scaling is minmax(x, per_channel, want_maxval=True) followed by this call.
+    seed: None rounds to nearest even; a Python int in [0, 2^64) rounds stochastically, code = RNE(SR(q, r)) (include/fp8q.h:
+    16 bits of Philox4x32-10 per element, drawn by the element's flat index offset + position in x as it lies; offset a
+    multiple of 8), the draws of the mx_* ops: the same (seed, offset) gives the same draw to the same element in every
+    ocp_* op, and a slice encoded under the same scale with the offset of its first element equals the slice of the whole."""
     f = _ocp_fmt(fmt)
+    tag, sr = _ocp_sr(seed, offset)
     _require(x, "x", _VALUES)
     maxval = _ocp_range(maxval, "maxval", x)
     n = maxval.numel()
@@ -1660,8 +1672,8 @@ def ocp_encode(x, maxval, fmt, eps=1e-8, out=None, want_scale=True):
     if x.numel() == 0:
         return codes.view(fmt), (ocp_scale(maxval, fmt, eps) if want_scale else None)
     sfx, types = _lane(x.dtype)
-    _run("fp8q_ocp_encode" + sfx, x, x.data_ptr(), codes.data_ptr(), *types, C, inner, maxval.data_ptr(), n, f, float(eps),
-         scale.data_ptr() if want_scale else None)
+    _run(f"fp8q_ocp{tag}_encode" + sfx, x, x.data_ptr(), codes.data_ptr(), *types, C, inner, maxval.data_ptr(), n, f,
+         float(eps), scale.data_ptr() if want_scale else None, *sr)
     return codes.view(fmt), scale
 
 
@@ -1685,11 +1697,13 @@ def ocp_decode(codes, scale, out=None, out_dtype=None, fmt=None):
     return y
 
 
-def ocp_quantize(x, maxval, fmt, eps=1e-8, out=None, out_dtype=None):
+def ocp_quantize(x, maxval, fmt, eps=1e-8, out=None, out_dtype=None, *, seed=None, offset=0):
     """Fake-quantize to hardware FP8: ocp_decode(*ocp_encode(x, maxval, fmt, eps)) bit for bit, in one launch.  x float32
     gives float32; x float16 / bfloat16 gives float32 unless `out` or out_dtype=x.dtype ask for x's own dtype (the float32
-    result rounded once)."""
+    result rounded once).  seed / offset: as in ocp_encode, and ocp_quantize(x, ..., seed=s) ==
+    ocp_decode(*ocp_encode(x, ..., seed=s)) bit for bit."""
     f = _ocp_fmt(fmt)
+    tag, sr = _ocp_sr(seed, offset)
     _require(x, "x", _VALUES)
     dt = _quantize_out_dtype(x, out, out_dtype)
     maxval = _ocp_range(maxval, "maxval", x)
@@ -1700,7 +1714,8 @@ def ocp_quantize(x, maxval, fmt, eps=1e-8, out=None, out_dtype=None):
     if x.numel() == 0:
         return y
     sfx, types = _lane(x.dtype, dt)
-    _run("fp8q_ocp_quantize" + sfx, x, x.data_ptr(), y.data_ptr(), *types, C, inner, maxval.data_ptr(), n, f, float(eps))
+    _run(f"fp8q_ocp{tag}_quantize" + sfx, x, x.data_ptr(), y.data_ptr(), *types, C, inner, maxval.data_ptr(), n, f,
+         float(eps), *sr)
     return y
 
 
@@ -1750,16 +1765,17 @@ def ocp_block_route(R, K, tile, dtype, aligned16=True):
     return OCP_BLOCK_KERNELS[rc]
 
 
-def ocp_block_encode(x, fmt, tile=(1, 128), eps=1e-8, out=None, scales_out=None):
+def ocp_block_encode(x, fmt, tile=(1, 128), eps=1e-8, out=None, scales_out=None, *, seed=None, offset=0):
     """Block-scaled hardware FP8 operands of x: (codes, scales).  Every tile of `tile` = (1, 128), (128, 1) or (128, 128)
     elements gets its own float32 scale = max(amax(|tile|), eps) / fmax, found in the same pass; its codes are byte for byte
     ocp_encode(x[tile], amax, fmt, eps)'s.  codes: dtype `fmt`, x's shape and layout for every tile (nothing is transposed);
     scales: float32 [ceil(R / tr), ceil(K / tk)], row-major.  (1, 128) takes a tensor of any rank and tiles its last
     dimension (scales: x.shape[:-1] + (ceil(K / 128),)); the tiles that span rows need a 2-D x.  Edge tiles are short.  x
     float32, or float16 / bfloat16 (widened exactly).  `out`: contiguous uint8 or `fmt`; `scales_out`: contiguous float32 of
-    the scales' shape.  One launch, x read once."""
+    the scales' shape.  One launch, x read once.  seed / offset: as in ocp_encode (the scales do not change)."""
     f = _ocp_fmt(fmt)
     tile = _ocpb_tile(tile)
+    tag, sr = _ocp_sr(seed, offset)
     if isinstance(x, torch.Tensor):
         _ocpb_geometry(x.shape, tile)
     _require(x, "x", _VALUES)
@@ -1778,8 +1794,8 @@ def ocp_block_encode(x, fmt, tile=(1, 128), eps=1e-8, out=None, scales_out=None)
         scales = scales_out
     if x.numel():
         sfx, types = _lane(x.dtype)
-        _run("fp8q_ocpb_encode" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), *types, R, K, *tile, f,
-             float(eps))
+        _run(f"fp8q_ocpb{tag}_encode" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), *types, R, K, *tile, f,
+             float(eps), *sr)
     return codes.view(fmt).view(x.shape), scales
 
 
@@ -1809,12 +1825,14 @@ def ocp_block_decode(codes, scales, tile=(1, 128), out_dtype=None, out=None, fmt
     return y
 
 
-def ocp_block_quantize(x, fmt, tile=(1, 128), eps=1e-8, out_dtype=None, out=None):
+def ocp_block_quantize(x, fmt, tile=(1, 128), eps=1e-8, out_dtype=None, out=None, *, seed=None, offset=0):
     """Fake-quantize the way a block-scaled FP8 matrix multiplication sees x: ocp_block_decode(*ocp_block_encode(x, fmt,
     tile, eps), tile) bit for bit, in one launch, the scales never leaving the chip.  x float32 gives float32; x float16 /
-    bfloat16 gives float32 unless `out` or out_dtype=x.dtype ask for x's own dtype (the float32 result rounded once)."""
+    bfloat16 gives float32 unless `out` or out_dtype=x.dtype ask for x's own dtype (the float32 result rounded once).
+    seed / offset: as in ocp_encode, and the identity above holds seed for seed."""
     f = _ocp_fmt(fmt)
     tile = _ocpb_tile(tile)
+    tag, sr = _ocp_sr(seed, offset)
     if isinstance(x, torch.Tensor):
         _ocpb_geometry(x.shape, tile)
     _require(x, "x", _VALUES)
@@ -1825,7 +1843,7 @@ def ocp_block_quantize(x, fmt, tile=(1, 128), eps=1e-8, out_dtype=None, out=None
     if x.numel() == 0:
         return y
     sfx, types = _lane(x.dtype, dt)
-    _run("fp8q_ocpb_quantize" + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, *tile, f, float(eps))
+    _run(f"fp8q_ocpb{tag}_quantize" + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, *tile, f, float(eps), *sr)
     return y
 
 
@@ -1899,15 +1917,18 @@ def ocp_block_t_route(R, K, tile, dtype, aligned16=True):
             "nontemporal": bool(info.nontemporal)}
 
 
-def ocp_block_encode_t(x, fmt, tile=(1, 128), eps=1e-8, out=None, scales_out=None):
+def ocp_block_encode_t(x, fmt, tile=(1, 128), eps=1e-8, out=None, scales_out=None, *, seed=None, offset=0):
     """Block-scaled hardware FP8 operands of x.t() made from x as it lies: (codes_t, scales_t), byte for byte
     ocp_block_encode(x.t().contiguous(), fmt, tile, eps) -- the operands of a product that reduces over dim 0 of x -- in one
     launch that reads x once and makes no transposed copy.  x: 2-D [R, K] (reshape anything else), float32 / float16 /
     bfloat16.  tile: (1, 128) or (128, 128).  codes_t: dtype `fmt`, [K, R]; scales_t: float32 [K, ceil(R / 128)] for
     (1, 128), [ceil(K / 128), ceil(R / 128)] for (128, 128).  ocp_block_decode(codes_t, scales_t, tile) gives the values of
-    x.t().  `out`: contiguous uint8 or `fmt` of R * K elements; `scales_out`: contiguous float32 of the scales' shape."""
+    x.t().  `out`: contiguous uint8 or `fmt` of R * K elements; `scales_out`: contiguous float32 of the scales' shape.
+    seed / offset: as in ocp_encode; an element is drawn by its position in x, not in x.t(), so with a seed this is NOT
+    ocp_block_encode(x.t().contiguous(), ..., seed=seed) but the transposed half of ocp_block_encode_both(x, ..., seed=seed)."""
     f = _ocp_fmt(fmt)
     tile = _ocpbt_tile(tile)
+    tag, sr = _ocp_sr(seed, offset)
     R, K, _, stshape = _ocpbt_geometry(x, tile)
     _ocpbt_buffer(out, "out", (torch.uint8, fmt), numel=R * K)
     _ocpbt_buffer(scales_out, "scales_out", (torch.float32,), shape=stshape)
@@ -1917,18 +1938,21 @@ def ocp_block_encode_t(x, fmt, tile=(1, 128), eps=1e-8, out=None, scales_out=Non
     scales_t = _ocpbt_take(scales_out, "scales_out", stshape, torch.float32, x)
     if x.numel():
         sfx, types = _lane(x.dtype)
-        _run("fp8q_ocpbt_encode" + sfx, x, x.data_ptr(), codes_t.data_ptr(), scales_t.data_ptr(), *types, R, K, *tile, f,
-             float(eps))
+        _run(f"fp8q_ocpbt{tag}_encode" + sfx, x, x.data_ptr(), codes_t.data_ptr(), scales_t.data_ptr(), *types, R, K, *tile, f,
+             float(eps), *sr)
     return codes_t.view(fmt).view(K, R), scales_t
 
 
-def ocp_block_encode_both(x, fmt, tile=(1, 128), eps=1e-8, out=None, scales_out=None, out_t=None, scales_out_t=None):
+def ocp_block_encode_both(x, fmt, tile=(1, 128), eps=1e-8, out=None, scales_out=None, out_t=None, scales_out_t=None, *,
+                          seed=None, offset=0):
     """Both orientations of x's block-scaled operands from ONE read of x: (codes, scales, codes_t, scales_t) =
     ocp_block_encode(x, fmt, tile, eps) + ocp_block_encode_t(x, fmt, tile, eps), byte for byte, in one launch.  (1, 128): two
     quantizations (row tiles and column tiles have their own scales); (128, 128): one, stored twice -- codes_t == codes.t()
-    and scales_t == scales.t().  x: 2-D.  out / scales_out / out_t / scales_out_t: as in ocp_block_encode_t."""
+    and scales_t == scales.t().  x: 2-D.  out / scales_out / out_t / scales_out_t: as in ocp_block_encode_t.  seed / offset: as
+    in ocp_encode; both identities hold seed for seed."""
     f = _ocp_fmt(fmt)
     tile = _ocpbt_tile(tile)
+    tag, sr = _ocp_sr(seed, offset)
     R, K, sshape, stshape = _ocpbt_geometry(x, tile)
     _ocpbt_buffer(out, "out", (torch.uint8, fmt), numel=R * K)
     _ocpbt_buffer(scales_out, "scales_out", (torch.float32,), shape=sshape)
@@ -1942,8 +1966,8 @@ def ocp_block_encode_both(x, fmt, tile=(1, 128), eps=1e-8, out=None, scales_out=
     scales_t = _ocpbt_take(scales_out_t, "scales_out_t", stshape, torch.float32, x)
     if x.numel():
         sfx, types = _lane(x.dtype)
-        _run("fp8q_ocpbt_encode_both" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), codes_t.data_ptr(),
-             scales_t.data_ptr(), *types, R, K, *tile, f, float(eps))
+        _run(f"fp8q_ocpbt{tag}_encode_both" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), codes_t.data_ptr(),
+             scales_t.data_ptr(), *types, R, K, *tile, f, float(eps), *sr)
     return codes.view(fmt).view(R, K), scales, codes_t.view(fmt).view(K, R), scales_t
 
 

@@ -1359,6 +1359,60 @@ int fp8q_mxsr_quantize_t_f32(const float *x, float *y, int64_t R, int64_t K, int
 int fp8q_mxsr_quantize_t_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int fmt, int rounding,
                              uint64_t seed, uint64_t offset, fp8q_stream_t stream);
 
+/* ---- hardware FP8 with seeded stochastic rounding: per tensor / channel, per tile, and the transposed operands ----------------
+ * (csrc/fp8q_ocpq.h, used by csrc/fp8q_ocp.hip, csrc/fp8q_ocp_block.hip and csrc/fp8q_ocp_block_t.hip)  The operands these lanes
+ * make for the backward products are gradients, and the reason the block above gives for the MX lane holds for them.  These
+ * twelve entries are the twins of the OCP entries that convert elements, with `uint64_t seed, uint64_t offset` in front of
+ * `stream`.  Everything up to q is the twin's contract: scale = max(maxval, eps) / fmax (in the tile lanes from the tile's own
+ * amax), q = clamp(x / scale, -fmax, fmax) with x / scale the float32 IEEE quotient, a NaN q stores 0x7F, and the reported
+ * scales are unchanged.  Only
+ *   code = RNE(q)   becomes   code = RNE(SR(q, r))
+ * with SR the rounding of the block above for E4M3FN (M = 3, B = 7) and E5M2 (M = 2, B = 15) -- the 16 bits under the kept
+ * mantissa in the normal range, the one truncated float32 product in the format-subnormal range, the sign kept on a zero too,
+ * fmax a grid point that nothing passes -- and r the 16-bit draw of the block above: key from seed, counter from g = i >> 3,
+ * word (i >> 1) & 3, half i & 1, where i = offset + the flat index of the element in x AS IT LIES mod 2^64 (the transposed
+ * entries index by the position in x, not in x^T; for [R, K] that is offset + row * K + col).
+ * What follows: grid points never move; every result is one of q's two grid neighbours; P(away from zero) =
+ * floor(f * 2^16) / 2^16; quantize(seed) == decode(encode(seed)); encode_both(seed) == (encode(seed), encode_t(seed)), and at
+ * (128, 128) codes_t is still the transpose of codes; a slice encoded under the same scale with the offset of its first
+ * element (a multiple of 8) equals the slice of the whole.
+ * The quotient.  The round-to-nearest-even kernels never form fl32(x / scale): they convert the two ends of an interval around
+ * x * (1 / scale) and redo a dword by division where the ends disagree.  SR reads every bit of the quotient -- a wrong last
+ * bit moves f16 by one and can flip a code -- so these kernels take the IEEE division for every element.
+ * Errors are the twin's, all reported before the launch; an offset that is no multiple of 8 is FP8Q_EINVAL.  Routes
+ * (fp8q_chunk_route, fp8q_ocpb_route, fp8q_ocpbt_route), launch geometry and traffic are the twin's.  gfx950's own stochastic
+ * conversions (v_cvt_sr_*) are not used: they take 32 random bits and are unproven against this contract, the decision the MX
+ * lane made.
+ * Names: fp8q_ocpsr_*, fp8q_ocpbsr_*, fp8q_ocpbtsr_*; the sets of fp8q_ocp_*, fp8q_ocpb_* and fp8q_ocpbt_* entries are
+ * unchanged.  FP8Q_VERSION is unchanged: the entries are additive. */
+int fp8q_ocpsr_encode_f32(const float *x, uint8_t *codes, int64_t C, int64_t inner, const float *maxval, int64_t n_maxval,
+                          int fmt, float eps, float *scale_out, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_ocpsr_encode_h16(const void *x, uint8_t *codes, int x_type, int64_t C, int64_t inner, const float *maxval,
+                          int64_t n_maxval, int fmt, float eps, float *scale_out, uint64_t seed, uint64_t offset,
+                          fp8q_stream_t stream);
+int fp8q_ocpsr_quantize_f32(const float *x, float *y, int64_t C, int64_t inner, const float *maxval, int64_t n_maxval, int fmt,
+                            float eps, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_ocpsr_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t C, int64_t inner, const float *maxval,
+                            int64_t n_maxval, int fmt, float eps, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_ocpbsr_encode_f32(const float *x, uint8_t *codes, float *scales, int64_t R, int64_t K, int tile_r, int tile_k, int fmt,
+                           float eps, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_ocpbsr_encode_h16(const void *x, uint8_t *codes, float *scales, int x_type, int64_t R, int64_t K, int tile_r,
+                           int tile_k, int fmt, float eps, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_ocpbsr_quantize_f32(const float *x, float *y, int64_t R, int64_t K, int tile_r, int tile_k, int fmt, float eps,
+                             uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_ocpbsr_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int tile_r, int tile_k,
+                             int fmt, float eps, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_ocpbtsr_encode_f32(const float *x, uint8_t *codes_t, float *scales_t, int64_t R, int64_t K, int tile_r, int tile_k,
+                            int fmt, float eps, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_ocpbtsr_encode_h16(const void *x, uint8_t *codes_t, float *scales_t, int x_type, int64_t R, int64_t K, int tile_r,
+                            int tile_k, int fmt, float eps, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_ocpbtsr_encode_both_f32(const float *x, uint8_t *codes, float *scales, uint8_t *codes_t, float *scales_t, int64_t R,
+                                 int64_t K, int tile_r, int tile_k, int fmt, float eps, uint64_t seed, uint64_t offset,
+                                 fp8q_stream_t stream);
+int fp8q_ocpbtsr_encode_both_h16(const void *x, uint8_t *codes, float *scales, uint8_t *codes_t, float *scales_t, int x_type,
+                                 int64_t R, int64_t K, int tile_r, int tile_k, int fmt, float eps, uint64_t seed,
+                                 uint64_t offset, fp8q_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
