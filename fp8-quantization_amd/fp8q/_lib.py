@@ -9,6 +9,7 @@ _lib = None
 
 _i64 = ctypes.c_int64
 _u64 = ctypes.c_uint64
+_u32 = ctypes.c_uint32
 _vp = ctypes.c_void_p
 _f = ctypes.c_float
 _i = ctypes.c_int
@@ -230,6 +231,17 @@ SIGNATURES = {
     "fp8q_mxsr_encode_both_h16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _i64, _i, _i, _u64, _u64, _vp]),
     "fp8q_mxsr_quantize_t_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _u64, _u64, _vp]),
     "fp8q_mxsr_quantize_t_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _i, _u64, _u64, _vp]),
+    # under a block Hadamard rotation: (sign_mask, sr, seed, offset) in front of the stream; transform: (sign_mask, inverse)
+    "fp8q_mxh_transform_f32": (_i, [_vp, _vp, _i64, _i64, _u32, _i, _vp]),
+    "fp8q_mxh_transform_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _u32, _i, _vp]),
+    "fp8q_mxh_encode_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _u32, _i, _u64, _u64, _vp]),
+    "fp8q_mxh_encode_h16": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _u32, _i, _u64, _u64, _vp]),
+    "fp8q_mxh_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _u32, _i, _u64, _u64, _vp]),
+    "fp8q_mxh_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _i, _u32, _i, _u64, _u64, _vp]),
+    "fp8q_mxh_encode_t_f32": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _u32, _i, _u64, _u64, _vp]),
+    "fp8q_mxh_encode_t_h16": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _i, _i, _u32, _i, _u64, _u64, _vp]),
+    "fp8q_mxh_quantize_t_f32": (_i, [_vp, _vp, _i64, _i64, _i, _i, _u32, _i, _u64, _u64, _vp]),
+    "fp8q_mxh_quantize_t_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _i, _u32, _i, _u64, _u64, _vp]),
     "fp8q_ocpsr_encode_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _f, _vp, _u64, _u64, _vp]),
     "fp8q_ocpsr_encode_h16": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _i64, _i, _f, _vp, _u64, _u64, _vp]),
     "fp8q_ocpsr_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _f, _u64, _u64, _vp]),

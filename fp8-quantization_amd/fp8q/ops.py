@@ -2046,7 +2046,54 @@ def _mx_bytes(out, shape, dtype, name, like):
     return out.view(torch.uint8)
 
 
-def mx_encode(x, fmt, rounding="floor", out=None, scales_out=None, *, seed=None, offset=0):
+def _mx_hadamard(hadamard, name="hadamard", none_ok=True):
+    """the sign vector of a block Hadamard rotation: a Python int in [0, 2^32), bit i flips element i of every block; None (no
+    rotation) where none_ok.  Told from the argument alone, so raised before the device check."""
+    if hadamard is None and none_ok:
+        return None
+    if isinstance(hadamard, bool) or not isinstance(hadamard, int) or not 0 <= hadamard < 1 << 32:
+        raise ValueError(f"{name} must be a Python int in [0, 2^32), the signs of the rotation"
+                         f"{' (or None: no rotation)' if none_ok else ''}, got {hadamard!r}")
+    return hadamard
+
+
+def _mx_had_whole(n, what):
+    """blocks are never short under a rotation"""
+    if n % MX_BLOCK:
+        raise ValueError(f"a Hadamard rotation takes whole blocks: {what} must be a multiple of {MX_BLOCK}, got {n}")
+
+
+def _mx_had_args(had, sr):
+    """the trailing arguments of a fp8q_mxh_* entry that converts: (sign_mask, sr, seed, offset)"""
+    return (had, 1, *sr) if sr else (had, 0, 0, 0)
+
+
+def hadamard32(x, sign_mask=0, inverse=False, out=None, out_dtype=None):
+    """The block Hadamard rotation of the MX lane on its own (csrc/fp8q_mx_had.hip; include/fp8q.h states the arithmetic):
+    every block of 32 along the last dimension (a multiple of 32) has the sign of element i flipped where bit i of sign_mask
+    is set, then goes through the orthonormal 32 x 32 Walsh-Hadamard transform -- five stages of float32 butterflies and one
+    multiplication, a fixed order, so the result is defined bit for bit.  inverse=True undoes it (the transform, then the
+    signs).  x float32 / float16 / bfloat16 (widened exactly); float32 out unless `out` / out_dtype ask for a half type (the
+    float32 result rounded once).  One launch.  mx_encode(x, hadamard=m) == mx_encode(hadamard32(x, m))."""
+    m = _mx_hadamard(sign_mask, "sign_mask", none_ok=False)
+    dt = _decode_out_dtype(out, out_dtype)
+    if isinstance(x, torch.Tensor):
+        if x.dim() == 0:
+            raise ValueError("the blocks run along the last dimension: the tensor needs at least one")
+        _mx_had_whole(int(x.shape[-1]), "the last dimension")
+    _require(x, "x", _VALUES)
+    x = x.detach().contiguous()
+    y = _out(out, x, dt)
+    if x.numel() == 0:
+        return y
+    K = int(x.shape[-1])
+    half = x.dtype in _HALF or dt in _HALF
+    _run("fp8q_mxh_transform" + ("_h16" if half else "_f32"), x, x.data_ptr(), y.data_ptr(),
+         *((_DT[x.dtype], _DT[dt]) if half else ()), x.numel() // K, K, m, int(bool(inverse)))
+    return y
+
+
+def mx_encode(x, fmt, rounding="floor", out=None, scales_out=None, *, seed=None, offset=0, hadamard=None):
     """MX operands of x: (codes, scales).  Blocks of 32 along the last dimension, one E8M0 scale byte each (include/fp8q.h
     states the arithmetic).  fmt: torch.float8_e4m3fn / torch.float8_e5m2 (codes shaped like x) or torch.float4_e2m1fn_x2
     (codes [..., K / 2], the even-indexed element in the low nibble; K must be even) or MX_E2M3 / MX_E3M2, the strings "e2m3" /
@@ -2058,11 +2105,17 @@ def mx_encode(x, fmt, rounding="floor", out=None, scales_out=None, *, seed=None,
     seed: None rounds the elements to nearest even; a Python int in [0, 2^64) rounds them stochastically (include/fp8q.h: 16
     bits of Philox4x32-10 per element, drawn by the element's flat index offset + position in x -- so the same (seed, offset)
     gives the same draw to the same element in every mx_* op, and a slice encoded with the offset of its first element (a
-    multiple of 8) equals the slice of the whole)."""
+    multiple of 8) equals the slice of the whole).
+    hadamard: None, or the 32-bit sign vector of a block Hadamard rotation applied to every block before its range is taken
+    (the last dimension must then be a multiple of 32): the result is mx_encode(hadamard32(x, hadamard), ...) byte for byte,
+    from one read of x.  Give both operands of a product the same vector along the reduction dimension."""
     f, r = _mx_fmt(fmt), _mx_rounding(rounding)
     sr = _mx_sr(seed, offset)
+    had = _mx_hadamard(hadamard)
     if isinstance(x, torch.Tensor):
         _mx_geometry(x.shape, fmt)      # (argument errors before the device check: they need no GPU to be told)
+        if had is not None:
+            _mx_had_whole(int(x.shape[-1]), "the last dimension")
     _require(x, "x", _VALUES)
     x = x.detach().contiguous()
     R, K, cshape, sshape = _mx_geometry(x.shape, fmt)
@@ -2071,8 +2124,12 @@ def mx_encode(x, fmt, rounding="floor", out=None, scales_out=None, *, seed=None,
     scales = _mx_bytes(scales_out, sshape, MX_SCALE_DTYPE, "scales_out", x)
     if x.numel():
         sfx, types = _lane(x.dtype)
-        _run(("fp8q_mxsr_encode" if sr else "fp8q_mx_encode") + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(),
-             *types, R, K, f, r, *sr)
+        if had is not None:
+            _run("fp8q_mxh_encode" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), *types, R, K, f, r,
+                 *_mx_had_args(had, sr))
+        else:
+            _run(("fp8q_mxsr_encode" if sr else "fp8q_mx_encode") + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(),
+                 *types, R, K, f, r, *sr)
     return codes.view(cdt).view(cshape), scales.view(MX_SCALE_DTYPE).view(sshape)
 
 
@@ -2116,15 +2173,20 @@ def mx_decode(codes, scales, fmt=None, out_dtype=None, out=None):
     return y
 
 
-def mx_quantize(x, fmt, rounding="floor", out_dtype=None, out=None, *, seed=None, offset=0):
+def mx_quantize(x, fmt, rounding="floor", out_dtype=None, out=None, *, seed=None, offset=0, hadamard=None):
     """Fake-quantize the way an MX matrix multiplication sees x: mx_decode(*mx_encode(x, fmt, rounding)) bit for bit, in one
     launch, the scales never leaving the registers.  x float32 gives float32; x float16 / bfloat16 gives float32 unless `out`
     or out_dtype=x.dtype ask for x's own dtype (the float32 result rounded once).  seed / offset: as in mx_encode, and
-    mx_quantize(x, seed=s) == mx_decode(*mx_encode(x, seed=s)) bit for bit."""
+    mx_quantize(x, seed=s) == mx_decode(*mx_encode(x, seed=s)) bit for bit.
+    hadamard: as in mx_encode; the result is rotated back into x's own domain, hadamard32(mx_quantize(hadamard32(x, m), ...),
+    m, inverse=True, out_dtype=...) bit for bit -- float32 in between, a half result rounded once at the end."""
     f, r = _mx_fmt(fmt), _mx_rounding(rounding)
     sr = _mx_sr(seed, offset)
+    had = _mx_hadamard(hadamard)
     if isinstance(x, torch.Tensor):
         _mx_geometry(x.shape, fmt)      # (argument errors before the device check, as in mx_encode)
+        if had is not None:
+            _mx_had_whole(int(x.shape[-1]), "the last dimension")
     _require(x, "x", _VALUES)
     dt = _quantize_out_dtype(x, out, out_dtype)
     x = x.detach().contiguous()
@@ -2133,7 +2195,10 @@ def mx_quantize(x, fmt, rounding="floor", out_dtype=None, out=None, *, seed=None
     if x.numel() == 0:
         return y
     sfx, types = _lane(x.dtype, dt)
-    _run(("fp8q_mxsr_quantize" if sr else "fp8q_mx_quantize") + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, f, r, *sr)
+    if had is not None:
+        _run("fp8q_mxh_quantize" + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, f, r, *_mx_had_args(had, sr))
+    else:
+        _run(("fp8q_mxsr_quantize" if sr else "fp8q_mx_quantize") + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, f, r, *sr)
     return y
 
 
@@ -2170,16 +2235,21 @@ def mx_t_route(R, K, fmt, dtype, aligned16=True):
             "nontemporal": bool(info.nontemporal), "code_store_bytes": info.code_store_bytes}
 
 
-def mx_encode_t(x, fmt, rounding="floor", out=None, scales_out=None, *, seed=None, offset=0):
+def mx_encode_t(x, fmt, rounding="floor", out=None, scales_out=None, *, seed=None, offset=0, hadamard=None):
     """MX operands of x.t() made from x as it lies: (codes_t, scales_t), byte for byte mx_encode(x.t().contiguous(), fmt,
     rounding) -- blocks of 32 along dim 0 of x, for a product that reduces over it -- in one launch that reads x once and
     makes no transposed copy.  x: 2-D [R, K] (reshape anything else), float32 / float16 / bfloat16.  codes_t: [K, R] (FP8),
     [K, R / 2] (E2M1: rows 2i and 2i + 1 of a column share a byte, R even) or uint8 [K, 3R / 4] ("e2m3" / "e3m2": R a multiple
     of 4); scales_t: torch.float8_e8m0fnu [K, ceil(R / 32)].  mx_decode(codes_t, scales_t).t() gives the values back.
-    seed / offset: as in mx_encode; the draws go by the position in x, not in x.t()."""
+    seed / offset: as in mx_encode; the draws go by the position in x, not in x.t().
+    hadamard: as in mx_encode, the blocks being those along dim 0 (R a multiple of 32): mx_encode(x.t().contiguous(), ...,
+    hadamard=m) byte for byte."""
     f, r = _mx_fmt(fmt), _mx_rounding(rounding)
     sr = _mx_sr(seed, offset)
+    had = _mx_hadamard(hadamard)
     _mx_t_geometry(x, fmt)
+    if had is not None:
+        _mx_had_whole(int(x.shape[0]), "dim 0 (rows)")
     _require(x, "x", _VALUES)
     x = x.detach().contiguous()
     R, K = x.shape
@@ -2189,17 +2259,26 @@ def mx_encode_t(x, fmt, rounding="floor", out=None, scales_out=None, *, seed=Non
     scales = _mx_bytes(scales_out, sshape, MX_SCALE_DTYPE, "scales_out", x)
     if x.numel():
         sfx, types = _lane(x.dtype)
-        _run(("fp8q_mxsr_encode_t" if sr else "fp8q_mxt_encode") + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(),
-             *types, R, K, f, r, *sr)
+        if had is not None:
+            _run("fp8q_mxh_encode_t" + sfx, x, x.data_ptr(), codes.data_ptr(), scales.data_ptr(), *types, R, K, f, r,
+                 *_mx_had_args(had, sr))
+        else:
+            _run(("fp8q_mxsr_encode_t" if sr else "fp8q_mxt_encode") + sfx, x, x.data_ptr(), codes.data_ptr(),
+                 scales.data_ptr(), *types, R, K, f, r, *sr)
     return codes.view(cdt).view(cshape), scales.view(MX_SCALE_DTYPE).view(sshape)
 
 
 def mx_encode_both(x, fmt, rounding="floor", out=None, scales_out=None, out_t=None, scales_out_t=None, *, seed=None,
-                   offset=0):
+                   offset=0, hadamard=None):
     """Both orientations of x's MX operands from ONE read of x: (codes, scales, codes_t, scales_t) = mx_encode(x) +
     mx_encode_t(x), byte for byte, in one launch.  x: 2-D; E2M1 needs R and K even, the 6-bit formats multiples of 4.
     out / scales_out / out_t / scales_out_t: contiguous tensors of the results' dtype or uint8, as in mx_encode.
-    seed / offset: as in mx_encode; an element has one draw, used by both orientations."""
+    seed / offset: as in mx_encode; an element has one draw, used by both orientations.
+    hadamard: refused -- the two orientations are two different rotations, and making both from one read is not built; call
+    mx_encode and mx_encode_t."""
+    if hadamard is not None:
+        raise ValueError("mx_encode_both takes no Hadamard rotation: the two orientations rotate along different dimensions; "
+                         "call mx_encode(hadamard=) and mx_encode_t(hadamard=)")
     f, r = _mx_fmt(fmt), _mx_rounding(rounding)
     sr = _mx_sr(seed, offset)
     _mx_t_geometry(x, fmt, need_k=True)
@@ -2221,13 +2300,17 @@ def mx_encode_both(x, fmt, rounding="floor", out=None, scales_out=None, out_t=No
             codes_t.view(cdt).view(ctshape), scales_t.view(MX_SCALE_DTYPE).view(stshape))
 
 
-def mx_quantize_t(x, fmt, rounding="floor", out_dtype=None, out=None, *, seed=None, offset=0):
+def mx_quantize_t(x, fmt, rounding="floor", out_dtype=None, out=None, *, seed=None, offset=0, hadamard=None):
     """Fake-quantize x with the MX blocks along dim 0, in x's own layout: mx_decode(*mx_encode_t(x, fmt, rounding)).t() bit
     for bit, in one launch.  x: 2-D, any R and K -- nothing is packed, so E2M1 and the 6-bit formats need no divisible shape
-    here (mx_encode_t does).  Output dtype as mx_quantize.  seed / offset: as in mx_encode_t."""
+    here (mx_encode_t does).  Output dtype as mx_quantize.  seed / offset: as in mx_encode_t.
+    hadamard: as in mx_quantize along dim 0 (R a multiple of 32): mx_quantize(x.t().contiguous(), ..., hadamard=m).t()."""
     f, r = _mx_fmt(fmt), _mx_rounding(rounding)
     sr = _mx_sr(seed, offset)
+    had = _mx_hadamard(hadamard)
     _mx_t_geometry(x, fmt, need_r=False)
+    if had is not None:
+        _mx_had_whole(int(x.shape[0]), "dim 0 (rows)")
     _require(x, "x", _VALUES)
     dt = _quantize_out_dtype(x, out, out_dtype)
     x = x.detach().contiguous()
@@ -2236,7 +2319,11 @@ def mx_quantize_t(x, fmt, rounding="floor", out_dtype=None, out=None, *, seed=No
     if x.numel() == 0:
         return y
     sfx, types = _lane(x.dtype, dt)
-    _run(("fp8q_mxsr_quantize_t" if sr else "fp8q_mxt_quantize") + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, f, r, *sr)
+    if had is not None:
+        _run("fp8q_mxh_quantize_t" + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, f, r, *_mx_had_args(had, sr))
+    else:
+        _run(("fp8q_mxsr_quantize_t" if sr else "fp8q_mxt_quantize") + sfx, x, x.data_ptr(), y.data_ptr(), *types, R, K, f, r,
+             *sr)
     return y
 
 

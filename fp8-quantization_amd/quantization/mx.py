@@ -20,6 +20,11 @@ element), which is what the operands of a backward product want: call number n o
 (seed + n) mod 2^64 and records it as `last_seed`, so that ops.mx_quantize(x, ..., seed=q.last_seed) reproduces the call;
 reseed(seed) starts the count again.
 
+hadamard=m (a Python int in [0, 2^32), the signs) rotates every block by the block Hadamard transform before it is quantized
+and, in forward, back afterwards (include/fp8q.h; ops.hadamard32 is the rotation alone): an outlier no longer sets the scale
+of its 31 neighbours.  The blocked dimension must then be a multiple of 32.  encode() returns the operands of the ROTATED
+tensor -- what the matrix instruction wants when the other operand carries the same rotation -- and decode() rotates back.
+
 It follows the quantizer protocol (QuantizerBase) and the model zoo takes it as `method=MXQuantizer`; it is deliberately NOT a
 member of QMethods (the CLI's choices).  Forward only: there is no backward kernel, and a call that would need a gradient
 raises NotImplementedError.  There is no CPU path.
@@ -39,7 +44,7 @@ class MXQuantizer(QuantizerBase):
     range_free = True
 
     def __init__(self, n_bits=None, fmt=torch.float8_e4m3fn, rounding="floor", keep_dtype=False, flatten_rows=False,
-                 per_channel=False, scale_domain=None, block_axis=-1, stochastic=False, seed=0, **kwargs):
+                 per_channel=False, scale_domain=None, block_axis=-1, stochastic=False, seed=0, hadamard=None, **kwargs):
         if not isinstance(fmt, (torch.dtype, str)) or fmt not in _BITS:
             raise ValueError(f"fmt must be torch.float8_e4m3fn, torch.float8_e5m2, torch.float4_e2m1fn_x2, 'e2m3' or 'e3m2', "
                              f"got {fmt!r}")
@@ -53,6 +58,7 @@ class MXQuantizer(QuantizerBase):
         if not isinstance(stochastic, bool):
             raise ValueError(f"stochastic must be True or False, got {stochastic!r}")
         self._check_seed(seed)
+        _ops._mx_hadamard(hadamard)
         # per_channel is the protocol's argument; the scales are per block either way
         super().__init__(n_bits=_BITS[fmt], per_channel=per_channel, **kwargs)
         self.fmt = fmt
@@ -62,6 +68,7 @@ class MXQuantizer(QuantizerBase):
         self.flatten_rows = flatten_rows
         self.block_axis = block_axis
         self.stochastic = stochastic
+        self.hadamard = hadamard
         self.reseed(seed)
 
     @staticmethod
@@ -77,13 +84,14 @@ class MXQuantizer(QuantizerBase):
         self.last_seed = None
 
     def _draw(self):
-        """the keywords this call adds to its op: none unless stochastic, else seed=(seed + calls) mod 2^64, recorded as
-        last_seed"""
-        if not self.stochastic:
-            return {}
-        self.last_seed = (self.seed + self.calls) % (1 << 64)
-        self.calls += 1
-        return {"seed": self.last_seed}
+        """the keywords this call adds to its op: hadamard= where a rotation is set; seed=(seed + calls) mod 2^64, recorded as
+        last_seed, where stochastic"""
+        kw = {} if self.hadamard is None else {"hadamard": self.hadamard}
+        if self.stochastic:
+            self.last_seed = (self.seed + self.calls) % (1 << 64)
+            self.calls += 1
+            kw["seed"] = self.last_seed
+        return kw
 
     @property
     def is_initialized(self):
@@ -143,12 +151,18 @@ class MXQuantizer(QuantizerBase):
     def decode(self, codes, scales, out_dtype=None):
         """Values of encode()'s operands, float32 or out_dtype (float16 / bfloat16: the float32 value rounded once), shaped as
         encode() saw them: decode(*encode(x)) == forward(x) bit for bit (after .view(x.shape) with flatten_rows).
-        block_axis=-2: the transposed operands decode to [K, R]; the result is that, transposed back (a view)."""
-        if self.block_axis == -2:
-            return _ops.mx_decode(codes, scales, fmt=self.fmt, out_dtype=out_dtype).t()
-        return _ops.mx_decode(codes, scales, fmt=self.fmt, out_dtype=out_dtype)
+        block_axis=-2: the transposed operands decode to [K, R]; the result is that, transposed back (a view).
+        hadamard: the operands hold rotated values; they are decoded in float32 and rotated back (ops.hadamard32, inverse),
+        a half out_dtype rounding once at the end, as forward does."""
+        if self.hadamard is None:
+            y = _ops.mx_decode(codes, scales, fmt=self.fmt, out_dtype=out_dtype)
+        else:
+            y = _ops.hadamard32(_ops.mx_decode(codes, scales, fmt=self.fmt), self.hadamard, inverse=True, out_dtype=out_dtype)
+        return y.t() if self.block_axis == -2 else y
 
     def extra_repr(self):
         sr = f"stochastic=True, seed={self.seed}, " if self.stochastic else ""
+        if self.hadamard is not None:
+            sr += f"hadamard={self.hadamard:#010x}, "
         return f"{super().extra_repr()}, fmt={_NAME[self.fmt]}, rounding={self.rounding}, flatten_rows={self.flatten_rows}, " \
                f"{sr}block_axis={self.block_axis}"

@@ -1359,6 +1359,68 @@ int fp8q_mxsr_quantize_t_f32(const float *x, float *y, int64_t R, int64_t K, int
 int fp8q_mxsr_quantize_t_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int fmt, int rounding,
                              uint64_t seed, uint64_t offset, fp8q_stream_t stream);
 
+/* ---- microscaling under a block Hadamard rotation ------------------------------------------------------------------------------
+ * (csrc/fp8q_hadq.h, used by csrc/fp8q_mx_had.hip and csrc/fp8q_mx_had_t.hip)  One outlier in a block of 32 sets the E8M0 scale
+ * of all 32 elements, and at 4 and 6 bits the other 31 land on the lowest few codes.  A sign vector followed by the orthonormal
+ * 32 x 32 Walsh-Hadamard transform spreads the outlier over the block; both operands of a product take the same rotation along
+ * the reduction dimension, so the product is unchanged.  It is the companion of the stochastic rounding above in the published
+ * MXFP4 training recipes, and it runs inside the pass that already holds the block in registers.
+ *
+ * The rotation H32(v, sign_mask) of one block v[0..31] of float32 values (a half input is widened exactly):
+ *   1. signs        v[i] has its sign bit flipped where bit i of sign_mask is set: an exact flip, of zeros, infinities and
+ *                   NaNs as well
+ *   2. butterflies  five stages s = 0, 1, 2, 3, 4 in that order; for every i with bit s clear and j = i | (1 << s):
+ *                     (v[i], v[j]) <- (fl32(v[i] + v[j]), fl32(v[i] - v[j]))
+ *                   The upper element is lower - upper, computed as that subtraction -- NOT -(upper - lower), which differs
+ *                   in the sign of a zero result.  Each result is one IEEE float32 addition, round to nearest even,
+ *                   subnormals kept.  This is the Sylvester (natural-order) matrix H[i][j] = (-1)^popcount(i & j).
+ *   3. norm         one float32 multiplication of each result by c = 0x3E3504F3, the float32 nearest to 2^-2.5
+ * There is no fused multiply-add anywhere: nothing above is of the form a * b + c, and it must stay that way.
+ * The inverse runs steps 2 and 3, then step 1 (H is symmetric, so the butterflies are the same).
+ * Nothing is special-cased: a block with a NaN becomes all NaN, one with an infinity infinities and NaNs, one whose sums
+ * overflow infinite -- in all three every element has E == 255, so the scale rule above gives 0xFF and the code rule 0x7F / 0x0.
+ * Why butterflies and not the matrix cores: the accumulation order of a v_mfma_* instruction is not specified, so no byte-exact
+ * contract could be stated; and 160 additions per block against 1024 multiply-adds would make the pass arithmetic-bound.
+ *
+ * Blocks are never short: K % 32 == 0 (R % 32 == 0 for the entries with the blocks along dim 0), else FP8Q_EINVAL.
+ *   fp8q_mxh_transform_*   y = H32 of every block of x along the last dimension, or the inverse (inverse != 0); x and y each
+ *                          float32, float16 or bfloat16 (_h16: at least one a half type), a half y rounds the float32 once
+ *   fp8q_mxh_encode_*      fp8q_mx_encode_* (sr == 0) or fp8q_mxsr_encode_* (sr == 1: seed, offset) of H32(x), byte for byte,
+ *                          codes and scales.  The draw of an element goes by its flat index, which the rotation does not move.
+ *   fp8q_mxh_quantize_*    H32^-1(fp8q_mx[sr]_quantize(H32(x))): the result is in x's own domain.  Intermediates are float32,
+ *                          rounded once to a half y_type at the end; the rotated-domain values are the decode of
+ *                          fp8q_mxh_encode_*'s operands.
+ *   fp8q_mxh_encode_t_*    fp8q_mxh_encode_* of the contiguous [K, R] tensor x^T, from x [R, K] as it lies (draws by the
+ *                          position in x, as in fp8q_mxsr_encode_t_*)
+ *   fp8q_mxh_quantize_t_*  fp8q_mxh_quantize_* of x^T, transposed back: y lies as x does
+ * sr: 0 rounds to nearest even (seed and offset are ignored), 1 stochastically (offset a multiple of 8); anything else is
+ * FP8Q_EINVAL.  Every other error is the twin's, all reported before the launch.  Routes: the row-wise entries take their fast
+ * kernel where x and y / codes are 16-byte aligned and a lane-per-block kernel otherwise; the dim-0 entries follow
+ * fp8q_mxt_route.  Nontemporal from 64 MiB.  One launch, no workspace.  A rotation of both orientations from one read
+ * (encode_both), transforms wider than the block and a sign vector per block are out of scope.
+ * Names: fp8q_mxh_*; the sets of fp8q_mx_*, fp8q_mxt_* and fp8q_mxsr_* entries are unchanged.  FP8Q_VERSION is unchanged: the
+ * entries are additive. */
+int fp8q_mxh_transform_f32(const float *x, float *y, int64_t R, int64_t K, uint32_t sign_mask, int inverse,
+                           fp8q_stream_t stream);
+int fp8q_mxh_transform_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, uint32_t sign_mask,
+                           int inverse, fp8q_stream_t stream);
+int fp8q_mxh_encode_f32(const float *x, uint8_t *codes, uint8_t *scales, int64_t R, int64_t K, int fmt, int rounding,
+                        uint32_t sign_mask, int sr, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxh_encode_h16(const void *x, uint8_t *codes, uint8_t *scales, int x_type, int64_t R, int64_t K, int fmt,
+                        int rounding, uint32_t sign_mask, int sr, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxh_quantize_f32(const float *x, float *y, int64_t R, int64_t K, int fmt, int rounding, uint32_t sign_mask, int sr,
+                          uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxh_quantize_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int fmt, int rounding,
+                          uint32_t sign_mask, int sr, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxh_encode_t_f32(const float *x, uint8_t *codes_t, uint8_t *scales_t, int64_t R, int64_t K, int fmt, int rounding,
+                          uint32_t sign_mask, int sr, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxh_encode_t_h16(const void *x, uint8_t *codes_t, uint8_t *scales_t, int x_type, int64_t R, int64_t K, int fmt,
+                          int rounding, uint32_t sign_mask, int sr, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxh_quantize_t_f32(const float *x, float *y, int64_t R, int64_t K, int fmt, int rounding, uint32_t sign_mask, int sr,
+                            uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+int fp8q_mxh_quantize_t_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int fmt, int rounding,
+                            uint32_t sign_mask, int sr, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
+
 /* ---- hardware FP8 with seeded stochastic rounding: per tensor / channel, per tile, and the transposed operands ----------------
  * (csrc/fp8q_ocpq.h, used by csrc/fp8q_ocp.hip, csrc/fp8q_ocp_block.hip and csrc/fp8q_ocp_block_t.hip)  The operands these lanes
  * make for the backward products are gradients, and the reason the block above gives for the MX lane holds for them.  These
