@@ -2327,6 +2327,80 @@ def mx_quantize_t(x, fmt, rounding="floor", out_dtype=None, out=None, *, seed=No
     return y
 
 
+# ---- the product of two MX operands on the matrix cores (csrc/fp8q_mx_mm.hip) ----
+def _mx_mm_operand(codes, fmt, name):
+    """(format, K in elements) of one operand of mx_matmul, told from its dtype and shape alone: raised before the device check"""
+    if not isinstance(codes, torch.Tensor):
+        raise Fp8qError(f"{name}_codes must be a CUDA(HIP) tensor: the FP8 engine has no CPU path")
+    if codes.dtype == torch.uint8:
+        if fmt is None:
+            raise Fp8qError(f"uint8 codes carry no format: pass {name}_fmt=")
+    elif codes.dtype in _MX_FMT:
+        if fmt is not None and fmt != codes.dtype:
+            raise Fp8qError(f"{name}_codes are {codes.dtype} but {name}_fmt is {fmt}")
+        fmt = codes.dtype
+    else:
+        raise Fp8qError(f"{name}_codes must be float8_e4m3fn, float8_e5m2, float4_e2m1fn_x2 or uint8, got {codes.dtype}")
+    _mx_fmt(fmt)
+    if codes.dim() == 0:
+        raise Fp8qError(f"MX blocks run along the last dimension: {name}_codes need at least one")
+    kb = int(codes.shape[-1])
+    if fmt in _MX_FP6 and kb % 3:
+        raise Fp8qError(f"four FP6 elements share three bytes: the last dimension of {name}_codes must be a multiple of 3, got {kb}")
+    return fmt, (kb * 4 // 3 if fmt in _MX_FP6 else kb * (2 if fmt == torch.float4_e2m1fn_x2 else 1))
+
+
+def mx_matmul(a_codes, a_scales, b_codes, b_scales, a_fmt=None, b_fmt=None, out_dtype=torch.float32, out=None):
+    """y[M, N] = A[M, K] . B[N, K]^T of two MX operands on gfx950's scaled matrix instruction (csrc/fp8q_mx_mm.hip; include/fp8q.h
+    states the contract): the product of the operands' mx_decode values, accumulated in float32 by the instruction in an order
+    that is not specified -- defined up to the summation bound stated there (the instruction's own sum of 8 neighbouring
+    products is narrower than float32), not bit for bit.  Both operands have K
+    contiguous, exactly as mx_encode and mx_encode_t return them, so a linear layer's three products need no other form:
+        y  = x . W^T     mx_matmul(*mx_encode(x, f),    *mx_encode(W, f))
+        dx = dy . W      mx_matmul(*mx_encode(dy, f),   *mx_encode_t(W, f))
+        dW = dy^T . x    mx_matmul(*mx_encode_t(dy, f), *mx_encode_t(x, f))
+    a_codes [..., K'] (leading dimensions are flattened to M), b_codes [N, K']: an MX element dtype, or uint8 with a_fmt / b_fmt
+    naming the format as mx_decode's fmt= does (the only way for "e2m3" / "e3m2").  The two formats are independent: all 25
+    pairs are served.  a_scales [..., K / 32], b_scales [N, K / 32]: torch.float8_e8m0fnu or uint8.  K, in elements, is equal
+    for both operands and a multiple of 32: short last blocks are out of scope.  M, N >= 1 are arbitrary; an empty M or N gives
+    an empty result with no launch.  The result is float32, or float16 / bfloat16 where `out` / out_dtype ask (the float32
+    accumulator rounded once).  Operands are expected finite with products in float32's normal range.  One launch; no
+    autograd, no split-K or small-M kernel, no batched B."""
+    dt = _decode_out_dtype(out, out_dtype)
+    a_fmt, K = _mx_mm_operand(a_codes, a_fmt, "a")
+    b_fmt, Kb = _mx_mm_operand(b_codes, b_fmt, "b")
+    if b_codes.dim() != 2:
+        raise Fp8qError(f"b_codes must be 2-D [N, K'], got {tuple(b_codes.shape)}")
+    if K != Kb:
+        raise Fp8qError(f"the operands disagree on K: a has {K} elements along its last dimension, b has {Kb}")
+    if K == 0 or K % MX_BLOCK:
+        raise Fp8qError(f"K must be a positive multiple of {MX_BLOCK} (short last blocks are out of scope), got {K}")
+    lead, N = tuple(a_codes.shape[:-1]), int(b_codes.shape[0])
+    for name, s, shape in (("a_scales", a_scales, lead + (K // MX_BLOCK,)), ("b_scales", b_scales, (N, K // MX_BLOCK))):
+        if isinstance(s, torch.Tensor) and tuple(s.shape) != shape:
+            raise Fp8qError(f"{name} are {tuple(s.shape)}, the codes have {shape}")
+    _require(a_codes, "a_codes", (torch.uint8, _mx_code_dtype(a_fmt)))
+    _require(b_codes, "b_codes", (torch.uint8, _mx_code_dtype(b_fmt)), a_codes)
+    _require(a_scales, "a_scales", (MX_SCALE_DTYPE, torch.uint8), a_codes)
+    _require(b_scales, "b_scales", (MX_SCALE_DTYPE, torch.uint8), a_codes)
+    a, b = a_codes.contiguous().view(torch.uint8), b_codes.contiguous().view(torch.uint8)
+    sa, sb = a_scales.contiguous().view(torch.uint8), b_scales.contiguous().view(torch.uint8)
+    M = a.numel() // a.shape[-1] if a.shape[-1] else 0
+    if out is None:
+        y = torch.empty(lead + (N,), dtype=dt, device=a.device)
+    else:
+        _require(out, "out", dt, a)
+        if out.numel() != M * N or not out.is_contiguous():
+            raise Fp8qError(f"out must be a contiguous tensor of {M * N} elements (got {tuple(out.shape)}, "
+                            f"contiguous={out.is_contiguous()})")
+        y = out
+    if M * N == 0:
+        return y
+    _run("fp8q_mxmm_nt", a, a.data_ptr(), sa.data_ptr(), b.data_ptr(), sb.data_ptr(), y.data_ptr(), M, N, K, _mx_fmt(a_fmt),
+         _mx_fmt(b_fmt), _DT[dt])
+    return y
+
+
 def _nchw(x):
     """[N, C, *spatial] -> (N, C, HW)."""
     if x.dim() < 2:

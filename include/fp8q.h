@@ -1421,6 +1421,35 @@ int fp8q_mxh_quantize_t_f32(const float *x, float *y, int64_t R, int64_t K, int 
 int fp8q_mxh_quantize_t_h16(const void *x, void *y, int x_type, int y_type, int64_t R, int64_t K, int fmt, int rounding,
                             uint32_t sign_mask, int sr, uint64_t seed, uint64_t offset, fp8q_stream_t stream);
 
+/* ---- the product of two MX operands on the matrix cores -------------------------------------------------------------------------
+ * (csrc/fp8q_mx_mm.hip)  y[M, N] = A[M, K] . B[N, K]^T: both operands K contiguous, codes and scale bytes exactly as the MX
+ * encoders above write them (a_codes [M, K] / [M, 3K / 4] / [M, K / 2] bytes, a_scales [M, K / 32]; b_* the same with N rows),
+ * the two element formats independent of each other (all 25 pairs).  The three products of a linear layer need no other
+ * operand form: y = x . W^T from the row-wise operands of x and W, dx = dy . W from the row-wise operands of dy and the dim-0
+ * operands of W, dW = dy^T . x from the dim-0 operands of dy and x.  y is [M, N] row-major, y_type FP8Q_DT_F32, FP8Q_DT_F16 or
+ * FP8Q_DT_BF16.
+ * Contract.  The result is the product of the operands' decoded values (fp8q_mx_decode_*'s: value(elem) * 2^(scale - 127)),
+ * accumulated in float32 by v_mfma_scale_f32_16x16x128_f8f6f4 in an order that is not specified; so it is defined up to a
+ * summation bound, not bit for bit -- the reason the block above gives for keeping the rotation off the matrix cores.  The
+ * bound: |y - exact| <= 18480 * 2^-24 * (|A| . |B|^T) per entry, twice the largest error measured on Gaussian data with
+ * outliers.  It is an observed figure and wider than K * 2^-23 * (|A| . |B|^T), the bound of K float32 additions
+ * over exact products: inside the instruction the products of 8 consecutive K are aligned to the largest of them and what
+ * falls below that window is dropped.  Sums that need no rounding at all (products within 2^9 of each other, 20-bit sums) are
+ * exact, which is how tests/test_mx_mm_gpu.py proves the operand layouts.
+ * It is defined for finite operands whose scaled products stay in float32's normal range: what a 0xFF scale
+ * byte, a NaN element or scale byte 0 give is the instruction's business (DESIGN.md records what was observed).  A half y is
+ * the float32 accumulator rounded once, to nearest even.
+ * K % 32 == 0: blocks are never short.  M, N >= 1 are arbitrary; M == 0 or N == 0 is a no-op that returns FP8Q_OK.  Codes and
+ * scales may start at any byte (the loads narrow from 16 bytes to 8, 4 or 1 as the pointer and the row pitch require); y must
+ * be aligned to its element.  Errors, all reported before the launch: FP8Q_EUNSUPPORTED for a format id that is not one of the
+ * five, 3 included; FP8Q_EINVAL for K <= 0 or K % 32 != 0, negative M or N, an unknown y_type, null pointers, a misaligned y,
+ * a size whose grid overflows.  One launch, enqueue-only, no workspace.  Split-K, a small-M kernel, batched B and
+ * pre-swizzled scale layouts are out of scope.
+ * Names: fp8q_mxmm_*; the sets of fp8q_mx_*, fp8q_mxt_*, fp8q_mxsr_* and fp8q_mxh_* entries are unchanged.  FP8Q_VERSION is
+ * unchanged: the entry is additive. */
+int fp8q_mxmm_nt(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *b_codes, const uint8_t *b_scales, void *y,
+                 int64_t M, int64_t N, int64_t K, int a_fmt, int b_fmt, int y_type, fp8q_stream_t stream);
+
 /* ---- hardware FP8 with seeded stochastic rounding: per tensor / channel, per tile, and the transposed operands ----------------
  * (csrc/fp8q_ocpq.h, used by csrc/fp8q_ocp.hip, csrc/fp8q_ocp_block.hip and csrc/fp8q_ocp_block_t.hip)  The operands these lanes
  * make for the backward products are gradients, and the reason the block above gives for the MX lane holds for them.  These
