@@ -2401,6 +2401,86 @@ def mx_matmul(a_codes, a_scales, b_codes, b_scales, a_fmt=None, b_fmt=None, out_
     return y
 
 
+# ---- the product of two block-scaled hardware FP8 operands on the matrix cores (csrc/fp8q_ocp_block_mm.hip) ----
+OCP_BLOCK_MM_TILES = ((1, 128), (128, 128))
+
+
+def _ocpb_mm_operand(codes, scales, tile, fmt, name):
+    """(format id, K) of one operand of ocp_block_matmul, told from dtypes and shapes alone: raised before the device check"""
+    if not isinstance(codes, torch.Tensor):
+        raise Fp8qError(f"{name}_codes must be a CUDA(HIP) tensor: the FP8 engine has no CPU path")
+    if codes.dtype in _OCP_FMT:
+        if fmt is not None and fmt != codes.dtype:
+            raise Fp8qError(f"{name}_codes are {codes.dtype} but {name}_fmt is {fmt}")
+        fmt = codes.dtype
+    elif codes.dtype != torch.uint8:
+        raise Fp8qError(f"{name}_codes must be float8_e4m3fn, float8_e5m2 or uint8, got {codes.dtype}")
+    elif fmt is None:
+        raise Fp8qError(f"uint8 codes carry no format: pass {name}_fmt=torch.float8_e4m3fn or torch.float8_e5m2")
+    f = _ocp_fmt(fmt)
+    try:
+        t = tuple(tile)
+    except TypeError:
+        t = None
+    if t not in OCP_BLOCK_MM_TILES or any(isinstance(v, bool) for v in t):
+        raise Fp8qError(f"{name}_tile must be (1, 128) or (128, 128), the tiles of a product's operands, got {tile!r}")
+    if name == "b" and codes.dim() != 2:
+        raise Fp8qError(f"b_codes must be 2-D [N, K], got {tuple(codes.shape)}")
+    _, K, sshape = _ocpb_geometry(codes.shape, t)
+    if isinstance(scales, torch.Tensor) and tuple(scales.shape) != sshape:
+        raise Fp8qError(f"{name}_scales are {tuple(scales.shape)}, {name}_codes of shape {tuple(codes.shape)} under {t} tiles "
+                        f"have {sshape}")
+    return f, t, K
+
+
+def ocp_block_matmul(a_codes, a_scales, b_codes, b_scales, a_tile=(1, 128), b_tile=(128, 128), a_fmt=None, b_fmt=None,
+                     out_dtype=torch.float32, out=None):
+    """y[M, N] = A[M, K] . B[N, K]^T of two block-scaled hardware FP8 operands on gfx950's matrix cores
+    (csrc/fp8q_ocp_block_mm.hip, the entry fp8q_ocpbmm_nt; include/fp8q.h states the contract): per K tile of 128 one matrix
+    instruction forms the unscaled partial product P_t from a zero accumulator, and acc = fma(P_t, sa * sb, acc) promotes it
+    into the float32 result in ascending t -- defined up to the bound stated there, not bit for bit.  Both operands have K
+    contiguous, exactly as ocp_block_encode, ocp_block_encode_t and ocp_block_encode_both return them, so a layer's three
+    products need no other form:
+        y  = x . W^T     (*ocp_block_encode(x, f),              *ocp_block_encode(W, f, (128, 128)),   b_tile=(128, 128))
+        dx = dy . W      (*ocp_block_encode(dy, f),             *ocp_block_encode_t(W, f, (128, 128)), b_tile=(128, 128))
+        dW = dy^T . x    (*ocp_block_encode_t(dy, f, (1, 128)), *ocp_block_encode_t(x, f, (1, 128)),   b_tile=(1, 128))
+    a_codes [..., K] (with a_tile (1, 128) leading dimensions are flattened to M; (128, 128) needs 2-D), b_codes [N, K]:
+    torch.float8_e4m3fn / torch.float8_e5m2, or uint8 with a_fmt / b_fmt naming the format as ocp_block_decode's fmt= does; the
+    two formats and the two tiles are independent.  Scales: float32, shaped as the encoders return them for the codes' shape
+    and tile.  (128, 1) and every other tile is refused: it is the operand of no product.  K >= 1 is arbitrary (a short last
+    tile is what the encoders leave); M, N >= 1 are arbitrary, and an empty M or N gives an empty result with no launch.  The
+    result is float32, or float16 / bfloat16 where `out` / out_dtype ask (the float32 accumulator rounded once).  Defined for
+    finite scales and non-NaN codes.  One launch; no autograd, no split-K or small-M kernel, no batched B."""
+    dt = _decode_out_dtype(out, out_dtype)
+    fa, a_tile, K = _ocpb_mm_operand(a_codes, a_scales, a_tile, a_fmt, "a")
+    fb, b_tile, Kb = _ocpb_mm_operand(b_codes, b_scales, b_tile, b_fmt, "b")
+    if K != Kb:
+        raise Fp8qError(f"the operands disagree on K: a has {K} elements along its last dimension, b has {Kb}")
+    if K == 0:
+        raise Fp8qError("K must be at least 1")
+    _require(a_codes, "a_codes", (torch.uint8,) + tuple(_OCP_FMT))
+    _require(b_codes, "b_codes", (torch.uint8,) + tuple(_OCP_FMT), a_codes)
+    _require(a_scales, "a_scales", like=a_codes)
+    _require(b_scales, "b_scales", like=a_codes)
+    a, b = a_codes.contiguous().view(torch.uint8), b_codes.contiguous().view(torch.uint8)
+    sa, sb = a_scales.detach().contiguous(), b_scales.detach().contiguous()
+    lead, N = tuple(a.shape[:-1]), int(b.shape[0])
+    M = a.numel() // K
+    if out is None:
+        y = torch.empty(lead + (N,), dtype=dt, device=a.device)
+    else:
+        _require(out, "out", dt, a)
+        if out.numel() != M * N or not out.is_contiguous():
+            raise Fp8qError(f"out must be a contiguous tensor of {M * N} elements (got {tuple(out.shape)}, "
+                            f"contiguous={out.is_contiguous()})")
+        y = out
+    if M * N == 0:
+        return y
+    _run("fp8q_ocpbmm_nt", a, a.data_ptr(), sa.data_ptr(), b.data_ptr(), sb.data_ptr(), y.data_ptr(), M, N, K, *a_tile, *b_tile,
+         fa, fb, _DT[dt])
+    return y
+
+
 def _nchw(x):
     """[N, C, *spatial] -> (N, C, HW)."""
     if x.dim() < 2:

@@ -1450,6 +1450,41 @@ int fp8q_mxh_quantize_t_h16(const void *x, void *y, int x_type, int y_type, int6
 int fp8q_mxmm_nt(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *b_codes, const uint8_t *b_scales, void *y,
                  int64_t M, int64_t N, int64_t K, int a_fmt, int b_fmt, int y_type, fp8q_stream_t stream);
 
+/* ---- the product of two block-scaled hardware FP8 operands on the matrix cores ---------------------------------------------------
+ * (csrc/fp8q_ocp_block_mm.hip)  y[M, N] = A[M, K] . B[N, K]^T from what the fp8q_ocpb_* / fp8q_ocpbt_* encoders write: codes
+ * [rows, K] bytes, K contiguous, a_fmt / b_fmt FP8Q_OCP_E4M3FN or FP8Q_OCP_E5M2 independently; scales float32
+ * [ceil(rows / tile_r), ceil(K / 128)] row-major.  Each operand's tile is (1, 128) or (128, 128), independently: all four
+ * combinations.  (128, 1) is FP8Q_EUNSUPPORTED like every other tile: it is the operand of no product.  The three products of
+ * a linear layer, operands as (codes, scales, tile):
+ *   y  = x . W^T     A = encode(x, (1, 128)),       B = encode(W, (128, 128))
+ *   dx = dy . W      A = encode(dy, (1, 128)),      B = encode_t(W, (128, 128))      (codes_t / scales_t, tile (128, 128))
+ *   dW = dy^T . x    A = encode_t(dy, (1, 128)),    B = encode_t(x, (1, 128))        (both tiles (1, 128))
+ * y is [M, N] row-major, y_type FP8Q_DT_F32, FP8Q_DT_F16 or FP8Q_DT_BF16 (the float32 accumulator rounded once, to nearest even).
+ * Contract.
+ *   y[m, n] = sum over the K tiles t of (sa[ra(m), t] * sb[rb(n), t]) * P_t[m, n]
+ * ra(m) / rb(n) is the row for a (1, 128) tile and row / 128 for a (128, 128) tile.  P_t[m, n] is the sum over the tile's K of
+ * value(a code) * value(b code), formed by ONE v_mfma_f32_16x16x128_f8f6f4 from a zero accumulator, in an order the instruction
+ * does not specify.  sa * sb is one float32 multiplication, and acc = fma(P_t, sa * sb, acc) one fused float32 operation per
+ * tile, in ascending t from acc = 0.  So the result is defined up to a bound, not bit for bit:
+ *   |y - exact| <= 9258 * 2^-24 * (|A| . |B|^T) per entry, |A|, |B| the decoded magnitudes (value(code) * scale),
+ * twice the largest ratio measured on Gaussian data with outliers (4628.965).  It is an observed figure of
+ * the instruction's own sum (fp8q_mxmm_nt's note on 8 neighbouring products applies; its E4M3 x E4M3 figure is 4298.054), to
+ * which the promotion adds two float32 roundings per K tile.  Sums that need no rounding at all are exact, which is how
+ * tests/test_ocpb_mm_gpu.py proves the row, tile, byte and scale mapping.
+ * Defined for finite scales and codes that are not NaN; what a NaN or inf scale (a NaN or inf tile of the encoder) gives is
+ * recorded in DESIGN.md and not promised.
+ * K >= 1 is arbitrary: the last K tile is short as the encoders leave it, and codes beyond K count as zero codes (nothing past
+ * a row's end is read).  M, N >= 1 are arbitrary; M == 0 or N == 0 is a no-op that returns FP8Q_OK.  Codes may start at any
+ * byte (loads narrow from 16 bytes to 8, 4 or 1 as the pointer and K require); scales must be 4-byte aligned, y aligned to its
+ * element.  Errors, all reported before the launch: FP8Q_EUNSUPPORTED for an unknown fmt or tile; FP8Q_EINVAL for K <= 0,
+ * negative M or N, an unknown y_type, null pointers, misaligned y or scales, a size whose grid overflows.  One launch,
+ * enqueue-only, no workspace.  Split-K, a small-M kernel, batched B and pre-swizzled scales are out of scope.
+ * Names: fp8q_ocpbmm_*; the sets of fp8q_ocpb_* and fp8q_ocpbt_* entries are unchanged.  FP8Q_VERSION is unchanged: the entry is
+ * additive. */
+int fp8q_ocpbmm_nt(const uint8_t *a_codes, const float *a_scales, const uint8_t *b_codes, const float *b_scales, void *y,
+                   int64_t M, int64_t N, int64_t K, int a_tile_r, int a_tile_k, int b_tile_r, int b_tile_k, int a_fmt, int b_fmt,
+                   int y_type, fp8q_stream_t stream);
+
 /* ---- hardware FP8 with seeded stochastic rounding: per tensor / channel, per tile, and the transposed operands ----------------
  * (csrc/fp8q_ocpq.h, used by csrc/fp8q_ocp.hip, csrc/fp8q_ocp_block.hip and csrc/fp8q_ocp_block_t.hip)  The operands these lanes
  * make for the backward products are gradients, and the reason the block above gives for the MX lane holds for them.  These
