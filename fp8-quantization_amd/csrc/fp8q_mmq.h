@@ -1,4 +1,5 @@
-// fp8q_mmq.h -- what the two matrix-core products share (fp8q_mx_mm.hip: MX operands under E8M0 block scales;
+// fp8q_mmq.h -- what the matrix-core products share (fp8q_mx_mm.hip: MX operands under E8M0 block scales, and its small-M
+// kernel fp8q_mx_mm_skinny.hip, which takes the chunk loads, the stores, the load width and the MX format table;
 // fp8q_ocp_block_mm.hip: hardware FP8 under float32 tile scales): the 128-row tile and its 256 lanes, an operand's panel of one
 // K step in LDS with its bank-conflict-free layout, the chunk loads that narrow with the operand's alignment, the fragment a
 // lane hands to v_mfma_*_16x16x128_f8f6f4, the masked stores of a lane's four results, and the one host rule for the load
@@ -14,6 +15,17 @@ constexpr int kMmBlock = 256;
 
 typedef int i8v __attribute__((ext_vector_type(8)));
 typedef float f4v __attribute__((ext_vector_type(4)));
+
+// ---- the MX formats, for the two MX products (fp8q_mx_mm.hip, fp8q_mx_mm_skinny.hip) ----
+constexpr int kMmScaleOne = 127; // the E8M0 byte of 2^0: what masked rows and blocks carry
+
+// FP8Q_MX_* -> the instruction's format number and the element width
+template <int F> struct MmFmt;
+template <> struct MmFmt<FP8Q_MX_E4M3FN> { static constexpr int hw = 0, bits = 8; };
+template <> struct MmFmt<FP8Q_MX_E5M2> { static constexpr int hw = 1, bits = 8; };
+template <> struct MmFmt<FP8Q_MX_E2M3> { static constexpr int hw = 2, bits = 6; };
+template <> struct MmFmt<FP8Q_MX_E3M2> { static constexpr int hw = 3, bits = 6; };
+template <> struct MmFmt<FP8Q_MX_E2M1> { static constexpr int hw = 4, bits = 4; };
 
 // one operand's panel of a K step in LDS (fp8q_mx_mm.hip's header has the bank arithmetic)
 template <int BITS>
@@ -130,6 +142,14 @@ __device__ __forceinline__ void mm_store4(void *y, int y_type, int64_t e, const 
 }
 
 // ---- host side ----
+// the five MX element formats and the bytes of one block of 32 elements
+inline bool mm_fmt_known(int f)
+{
+    return f == FP8Q_MX_E4M3FN || f == FP8Q_MX_E5M2 || f == FP8Q_MX_E2M1 || f == FP8Q_MX_E2M3 || f == FP8Q_MX_E3M2;
+}
+
+inline int mm_block_bytes(int f) { return f == FP8Q_MX_E2M1 ? 16 : ((f == FP8Q_MX_E2M3 || f == FP8Q_MX_E3M2) ? 24 : 32); }
+
 // The one place that decides how a codes operand is loaded: the widest of 16, 8, 4 bytes that divides both the pointer and the
 // row pitch (so that every row, and every 16-byte chunk of it, starts aligned), else single bytes.
 inline int mm_load_width(const void *codes, int64_t pitch)

@@ -2,7 +2,7 @@
 // contiguous and block-scaled exactly as fp8q_mx.hip / fp8q_mx_t.hip write them (codes in 32 / 24 / 16 bytes per block of 32,
 // one E8M0 byte per block in plain [rows, K / 32] order).  include/fp8q.h states the contract: the product of the operands'
 // decoded values, accumulated in float32 by v_mfma_scale_f32_16x16x128_f8f6f4 in an order the instruction does not specify.
-// K % 32 == 0; short last blocks, split-K, a small-M kernel and batched B are out of scope.
+// K % 32 == 0; short last blocks and batched B are out of scope; split-K for M <= 64 is fp8q_mx_mm_skinny.hip's kernel.
 //
 // The instruction.  One v_mfma_scale_f32_16x16x128_f8f6f4 multiplies 16 rows x 128 K of its "A" operand with 16 rows x 128 K
 // of its "B" operand.  Lane l holds, of either operand, row l % 16, g = l / 16.  FP6 and FP4: the K elements [32 g, 32 g + 32),
@@ -42,20 +42,11 @@
 //   row's banks under a permutation, the next row the other half (FP8) or the next quarter (FP4): conflict-free per 16 lanes.
 // There is no float arithmetic outside the instruction and the final conversion to a half type.
 // The tile, the panel, the chunk load, the fragment read, the stores and mm_load_width are in fp8q_mmq.h, which
-// fp8q_ocp_block_mm.hip shares.
+// fp8q_ocp_block_mm.hip shares; the MX format table (MmFmt, mm_fmt_known, mm_block_bytes) is there too, shared with the
+// small-M kernel of fp8q_mx_mm_skinny.hip.
 #include "fp8q_mmq.h"
 
 namespace {
-
-constexpr int kMmScaleOne = 127; // the E8M0 byte of 2^0: what masked rows and blocks carry
-
-// FP8Q_MX_* -> the instruction's format number and the element width
-template <int F> struct MmFmt;
-template <> struct MmFmt<FP8Q_MX_E4M3FN> { static constexpr int hw = 0, bits = 8; };
-template <> struct MmFmt<FP8Q_MX_E5M2> { static constexpr int hw = 1, bits = 8; };
-template <> struct MmFmt<FP8Q_MX_E2M3> { static constexpr int hw = 2, bits = 6; };
-template <> struct MmFmt<FP8Q_MX_E3M2> { static constexpr int hw = 3, bits = 6; };
-template <> struct MmFmt<FP8Q_MX_E2M1> { static constexpr int hw = 4, bits = 4; };
 
 struct MmArgs {
     const uint8_t *xc, *xs, *wc, *ws;   // codes and scales of X (rows m) and W (rows n)
@@ -172,13 +163,6 @@ k_mxmm(const MmArgs a)
 }
 
 // ---- host side ----
-inline bool mm_fmt_known(int f)
-{
-    return f == FP8Q_MX_E4M3FN || f == FP8Q_MX_E5M2 || f == FP8Q_MX_E2M1 || f == FP8Q_MX_E2M3 || f == FP8Q_MX_E3M2;
-}
-
-inline int mm_block_bytes(int f) { return f == FP8Q_MX_E2M1 ? 16 : ((f == FP8Q_MX_E2M3 || f == FP8Q_MX_E3M2) ? 24 : 32); }
-
 int mm_launch(const uint8_t *xc, const uint8_t *xs, const uint8_t *wc, const uint8_t *ws, void *y, int64_t M, int64_t N,
               int64_t K, int x_fmt, int w_fmt, int y_type, hipStream_t st)
 {

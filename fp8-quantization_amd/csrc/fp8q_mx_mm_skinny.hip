@@ -1,0 +1,282 @@
+// fp8q_mx_mm_skinny.hip -- the small-M kernel of the MX product: y[M, N] = A[M, K] . B[N, K]^T for 1 <= M <= 64, the shape of a
+// decode step (a handful of tokens against an FP4 / FP6 / FP8 weight matrix).  Operands, formats, K % 32 == 0 and the
+// instruction are those of fp8q_mx_mm.hip, whose header states the lane and result layouts; X is the function's A, W its B,
+// W the instruction's "A".  include/fp8q.h states the contract and the summation order.  The product is bound by streaming W
+// from HBM once, so the work is split for loads in flight, not for reuse:
+//
+// Split.  A workgroup of 256 lanes owns 64 rows of W (four instruction groups of 16) and one slice of T K steps (a step is 128
+// elements, four MX blocks); grid ceil(N / 64) x S.  Its four waves own consecutive sub-slices of tw = ceil(T / 4) steps,
+// clipped to the slice -- a wave may own none.  sk_plan (host, the only place that decides S, T, tw) chooses S from the shape
+// alone, so the summation order does not depend on the device.
+//
+// Main loop: no LDS, no barrier.  A lane's fragment is a straight copy of bytes the encoders wrote, so it goes from global
+// memory into the registers the instruction reads.  Lane (r = l % 16, g = l / 16), step s, of a codes row:
+//   FP4  the 16 bytes at 64 s + 16 g                          (block 4 s + g)
+//   FP6  the 24 bytes at 96 s + 24 g, a 16- and an 8-byte chunk (block 4 s + g); 24 g is only 8-aligned, so FP6 loads are
+//        at most 8 bytes wide
+//   FP8  the 16-byte runs at 128 s + 16 g and 128 s + 64 + 16 g (halves of the blocks 4 s + g / 2 and 4 s + 2 + g / 2)
+// and the scale byte of block 4 s + g.  Per step a wave loads 4 W fragments, MG X fragments (MG = 1, 2 or 4 groups of 16 rows
+// of M, a template constant) and their 4 + MG scale bytes, and issues 4 x MG instructions into acc[4][MG]: every X fragment
+// serves four W groups from registers.  X is at most 64 rows and stays in L2; a wave reads only the K slice it owns, so the
+// waves have nothing to share.  The loads of the next two steps are issued before a step's instructions: a ring of three
+// register stages, the loop unrolled by three so that every stage index is a constant.  Consecutive steps of one wave read
+// consecutive bytes of a row, so both halves of an FP4 row's 128-byte line are in flight together.
+// Edges are masked per lane; nothing is read past a row's end: a run is read iff its row exists (n < N, m < M) and its block
+// exists (< K / 32).  Everything else is zero codes under the scale byte 127, as in k_mxmm.
+//
+// After the loop the four waves' partial sums meet in LDS once: wave v keeps row group v in registers and writes the other
+// three (4 x 3 x MG x 64 lanes x 16 bytes: 48 KiB at MG = 4), one barrier, and wave w adds row group w over the waves 0, 1, 2, 3
+// in that order.  It stores with mm_store4: to y in its final type when S == 1, else float32 to workspace[s][m][n].
+// k_mxsk_reduce then adds the S partial results in ascending s and rounds once: two launches when S > 1, one otherwise.  No
+// float atomics: the same plan gives the same bits on every run.
+#include "fp8q_mmq.h"
+
+namespace {
+
+constexpr int kSkRows = 64;      // rows of W under one workgroup
+constexpr int kSkMaxM = 64;
+constexpr int kSkRing = 3;       // register stages: a step's loads are issued two steps ahead
+constexpr int kSkWant = 512;     // workgroups the plan aims for: about two per CU of a 256-CU part
+constexpr int kSkMinSteps = 8;   // steps a chosen split keeps at least: two per wave
+constexpr int kSkMaxSplits = 65535;
+
+struct SkPlan {
+    int64_t S, T, tw, ws_bytes;
+};
+
+struct SkArgs {
+    const uint8_t *xc, *xs, *wc, *ws;   // codes and scales of X (rows m) and W (rows n)
+    void *y;                            // [M, N] of y_type (S == 1) or float32 [S, M, N] (the workspace)
+    int64_t M, N, kblocks;              // kblocks = K / 32
+    int64_t xpitch, wpitch;             // bytes of a codes row
+    int nsteps, T, tw;                  // ceil(K / 128); steps per split; steps per wave
+    int xw, ww;                         // bytes per global load of either operand's codes: 16, 8, 4 or 1
+    int y_type;                         // FP8Q_DT_* of what this launch stores
+    int vec_store;                      // N % 4 == 0 and y aligned to four of its elements
+};
+
+// the lane's fragment of step ks of the codes row at `row`: the runs the header lists, zero where the row (ok) or the run's
+// block (< kb) does not exist; w: mm_load_width's, at most 8 for FP6
+template <int BITS>
+__device__ __forceinline__ i8v sk_load_frag(const uint8_t *row, bool ok, int ks, int g, int64_t kb, int w)
+{
+    i8v f = {0, 0, 0, 0, 0, 0, 0, 0};
+    if constexpr (BITS == 8) {
+        const int64_t blk = 4 * (int64_t)ks + (g >> 1);
+        const uint8_t *p = row + 128 * (int64_t)ks + 16 * g;
+        const u4v lo = mm_load_chunk(p, ok && blk < kb ? 16 : 0, w);
+        const u4v hi = mm_load_chunk(p + 64, ok && blk + 2 < kb ? 16 : 0, w);
+        f[0] = (int)lo.x, f[1] = (int)lo.y, f[2] = (int)lo.z, f[3] = (int)lo.w;
+        f[4] = (int)hi.x, f[5] = (int)hi.y, f[6] = (int)hi.z, f[7] = (int)hi.w;
+    } else if constexpr (BITS == 4) {
+        const u4v lo = mm_load_chunk(row + 64 * (int64_t)ks + 16 * g, ok && 4 * (int64_t)ks + g < kb ? 16 : 0, w);
+        f[0] = (int)lo.x, f[1] = (int)lo.y, f[2] = (int)lo.z, f[3] = (int)lo.w;
+    } else {
+        const bool in = ok && 4 * (int64_t)ks + g < kb;
+        const uint8_t *p = row + 96 * (int64_t)ks + 24 * g;
+        const u4v lo = mm_load_chunk(p, in ? 16 : 0, w);
+        const u4v hi = mm_load_chunk(p + 16, in ? 8 : 0, w);
+        f[0] = (int)lo.x, f[1] = (int)lo.y, f[2] = (int)lo.z, f[3] = (int)lo.w;
+        f[4] = (int)hi.x, f[5] = (int)hi.y;
+    }
+    return f;
+}
+
+// what one step's instructions read: W's four fragments, X's MG, the scale byte of the lane's block of each row
+template <int MG>
+struct SkStage {
+    i8v w[4], x[MG];
+    int sw[4], sx[MG];
+};
+
+template <int FX, int FW, int MG>
+__device__ __forceinline__ void sk_load_stage(SkStage<MG> &st, const SkArgs &a, int64_t n, int r, int g, int ks)
+{
+    const int64_t blk = 4 * (int64_t)ks + g;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int64_t row = n + 16 * i;
+        st.w[i] = sk_load_frag<MmFmt<FW>::bits>(a.wc + row * a.wpitch, row < a.N, ks, g, a.kblocks, a.ww);
+        st.sw[i] = (row < a.N && blk < a.kblocks) ? (int)a.ws[row * a.kblocks + blk] : kMmScaleOne;
+    }
+#pragma unroll
+    for (int j = 0; j < MG; ++j) {
+        const int64_t row = r + 16 * j;
+        st.x[j] = sk_load_frag<MmFmt<FX>::bits>(a.xc + row * a.xpitch, row < a.M, ks, g, a.kblocks, a.xw);
+        st.sx[j] = (row < a.M && blk < a.kblocks) ? (int)a.xs[row * a.kblocks + blk] : kMmScaleOne;
+    }
+}
+
+template <int FX, int FW, int MG>
+__global__ void __launch_bounds__(kMmBlock)
+k_mxsk(const SkArgs a)
+{
+    __shared__ f4v s_part[4][3][MG][64];    // [the wave that wrote][a row group that is not its own][j][lane]
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lr = lane & 15, lg = lane >> 4;
+    const int64_t n0 = (int64_t)blockIdx.x * kSkRows;
+    const int split = blockIdx.y;
+    // the wave's steps [k0, k1): its sub-slice, clipped to the split's slice and to K
+    const int send = min(a.nsteps, (split + 1) * a.T);
+    const int k0 = min(send, split * a.T + wave * a.tw), k1 = min(send, k0 + a.tw);
+
+    f4v acc[4][MG];     // [i: W's 16 rows][j: X's 16 rows]
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < MG; ++j) acc[i][j] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
+
+    SkStage<MG> st[kSkRing];
+#pragma unroll
+    for (int p = 0; p < kSkRing - 1; ++p)
+        if (k0 + p < k1) sk_load_stage<FX, FW, MG>(st[p], a, n0 + lr, lr, lg, k0 + p);
+    for (int k = k0; k < k1; k += kSkRing) {
+#pragma unroll
+        for (int p = 0; p < kSkRing; ++p) {
+            if (k + p >= k1) break;
+            if (k + p + kSkRing - 1 < k1)    // two steps ahead, into the stage that the step before this one left
+                sk_load_stage<FX, FW, MG>(st[(p + kSkRing - 1) % kSkRing], a, n0 + lr, lr, lg, k + p + kSkRing - 1);
+#pragma unroll
+            for (int j = 0; j < MG; ++j)
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(st[p].w[i], st[p].x[j], acc[i][j], MmFmt<FW>::hw,
+                                                                                 MmFmt<FX>::hw, 0, st[p].sw[i], 0, st[p].sx[j]);
+        }
+    }
+
+    // wave v hands the row groups i != v to their owners
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (i == wave) continue;
+#pragma unroll
+        for (int j = 0; j < MG; ++j) s_part[wave][i < wave ? i : i - 1][j][lane] = acc[i][j];
+    }
+    __syncthreads();
+
+    // lane l, register r of acc[i][j]: y[16 j + l % 16][n0 + 16 i + 4 (l / 16) + r]; this wave finishes i == wave
+    const int64_t n = n0 + 16 * wave + 4 * lg;
+    if (n >= a.N) return;
+    const int left = a.N - n < 4 ? (int)(a.N - n) : 4;
+#pragma unroll
+    for (int j = 0; j < MG; ++j) {
+        const int64_t m = lr + 16 * j;
+        if (m >= a.M) continue;
+        const f4v own = wave == 0 ? acc[0][j] : (wave == 1 ? acc[1][j] : (wave == 2 ? acc[2][j] : acc[3][j]));
+        f4v sum;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            f4v t;
+            if (v == wave) t = own;
+            else t = s_part[v][wave < v ? wave : wave - 1][j][lane];
+            sum = v == 0 ? t : sum + t;
+        }
+        mm_store4(a.y, a.y_type, ((int64_t)split * a.M + m) * a.N + n, sum, left, a.vec_store != 0);
+    }
+}
+
+// y[e] = part[0][e] + part[1][e] + ... + part[S - 1][e] in that order, rounded once to y's type; four outputs per lane
+__global__ void __launch_bounds__(kMmBlock)
+k_mxsk_reduce(const float *part, void *y, int64_t total, int S, int y_type, int vec)
+{
+    const int64_t e = 4 * ((int64_t)blockIdx.x * kMmBlock + threadIdx.x);
+    if (e >= total) return;
+    const int n = total - e < 4 ? (int)(total - e) : 4;
+    f4v sum = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int s = 0; s < S; ++s) {
+        const float *p = part + (int64_t)s * total + e;
+        f4v t = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (vec) {
+            t = *reinterpret_cast<const f4v *>(p);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (r < n) t[r] = p[r];
+        }
+        sum = s == 0 ? t : sum + t;
+    }
+    mm_store4(y, y_type, e, sum, n, vec != 0);
+}
+
+// ---- host side ----
+// The one place that decides the split (include/fp8q.h states the rule).  splits_req <= 0: the plan chooses.
+int sk_plan(int64_t M, int64_t N, int64_t K, int64_t splits_req, SkPlan &p)
+{
+    if (K <= 0 || K % 32 || M < 0 || N < 0) return FP8Q_EINVAL;
+    if (M > kSkMaxM) return FP8Q_EUNSUPPORTED;
+    const int64_t nsteps = cdiv(K, 128);
+    if (K / 32 > (int64_t)INT32_MAX || cdiv(N, kSkRows) > (int64_t)INT32_MAX) return FP8Q_EINVAL;
+    const int64_t gn = std::max<int64_t>(1, cdiv(N, kSkRows));
+    const int64_t want = splits_req > 0 ? splits_req : cdiv(kSkWant, gn);
+    const int64_t cap = std::min<int64_t>(kSkMaxSplits, splits_req > 0 ? nsteps : std::max<int64_t>(1, nsteps / kSkMinSteps));
+    p.S = std::min(std::max<int64_t>(want, 1), cap);
+    p.T = cdiv(nsteps, p.S);
+    p.S = cdiv(nsteps, p.T);        // no split is empty
+    p.tw = cdiv(p.T, 4);
+    p.ws_bytes = p.S == 1 ? 0 : p.S * M * N * 4;   // S < 2^16, M < 2^7, N < 2^37: below 2^62
+    return FP8Q_OK;
+}
+
+int sk_launch(const uint8_t *xc, const uint8_t *xs, const uint8_t *wc, const uint8_t *ws, void *y, int64_t M, int64_t N,
+              int64_t K, int x_fmt, int w_fmt, int y_type, int64_t splits_req, void *workspace, int64_t workspace_bytes,
+              hipStream_t st)
+{
+    if (!mm_fmt_known(x_fmt) || !mm_fmt_known(w_fmt)) return FP8Q_EUNSUPPORTED;
+    SkPlan p;
+    if (const int rc = sk_plan(M, N, K, splits_req, p)) return rc;
+    if (y_type != FP8Q_DT_F32 && !half_type(y_type)) return FP8Q_EINVAL;
+    if (M == 0 || N == 0) return FP8Q_OK;
+    if (!xc || !xs || !wc || !ws || !y) return FP8Q_EINVAL;
+    const int ybytes = y_type == FP8Q_DT_F32 ? 4 : 2;
+    if ((uintptr_t)y % (uintptr_t)ybytes) return FP8Q_EINVAL;
+    if (p.S > 1 && (!workspace || workspace_bytes < p.ws_bytes || (uintptr_t)workspace % 16)) return FP8Q_EINVAL;
+    const bool yvec = (uintptr_t)y % (uintptr_t)(4 * ybytes) == 0;
+    SkArgs a;
+    a.xc = xc, a.xs = xs, a.wc = wc, a.ws = ws;
+    a.M = M, a.N = N, a.kblocks = K / 32;
+    a.xpitch = a.kblocks * mm_block_bytes(x_fmt);
+    a.wpitch = a.kblocks * mm_block_bytes(w_fmt);
+    a.nsteps = (int)cdiv(a.kblocks, 4), a.T = (int)p.T, a.tw = (int)p.tw;
+    // an FP6 fragment starts at a multiple of 24 bytes: 8-byte loads at the most
+    a.xw = std::min(mm_load_width(xc, a.xpitch), mm_block_bytes(x_fmt) == 24 ? 8 : 16);
+    a.ww = std::min(mm_load_width(wc, a.wpitch), mm_block_bytes(w_fmt) == 24 ? 8 : 16);
+    if (p.S == 1) a.y = y, a.y_type = y_type, a.vec_store = N % 4 == 0 && yvec;
+    else a.y = workspace, a.y_type = FP8Q_DT_F32, a.vec_store = N % 4 == 0;
+    const dim3 grid((unsigned)cdiv(N, kSkRows), (unsigned)p.S), block(kMmBlock);
+    dispatch<FP8Q_MX_E4M3FN, FP8Q_MX_E5M2, FP8Q_MX_E2M1, FP8Q_MX_E2M3, FP8Q_MX_E3M2>(x_fmt, [&](auto FX) {
+        dispatch<FP8Q_MX_E4M3FN, FP8Q_MX_E5M2, FP8Q_MX_E2M1, FP8Q_MX_E2M3, FP8Q_MX_E3M2>(w_fmt, [&](auto FW) {
+            dispatch<1, 2, 4>(M <= 16 ? 1 : (M <= 32 ? 2 : 4), [&](auto MG) {
+                hipLaunchKernelGGL((k_mxsk<FX(), FW(), MG()>), grid, block, 0, st, a);
+            });
+        });
+    });
+    if (const int rc = launch_rc()) return rc;
+    if (p.S == 1) return FP8Q_OK;
+    const int64_t total = M * N;
+    hipLaunchKernelGGL(k_mxsk_reduce, dim3((unsigned)cdiv(cdiv(total, 4), kMmBlock)), block, 0, st,
+                       static_cast<const float *>(workspace), y, total, (int)p.S, y_type, (int)(total % 4 == 0 && yvec));
+    return launch_rc();
+}
+
+}  // namespace
+
+extern "C" {
+
+int fp8q_mxsk_plan(int64_t M, int64_t N, int64_t K, int64_t splits_req, int64_t *plan4)
+{
+    SkPlan p;
+    if (!plan4) return FP8Q_EINVAL;
+    if (const int rc = sk_plan(M, N, K, splits_req, p)) return rc;
+    plan4[0] = p.S, plan4[1] = p.T, plan4[2] = p.tw, plan4[3] = p.ws_bytes;
+    return FP8Q_OK;
+}
+
+int fp8q_mxsk_nt(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *b_codes, const uint8_t *b_scales, void *y,
+                 int64_t M, int64_t N, int64_t K, int a_fmt, int b_fmt, int y_type, int64_t splits_req, void *workspace,
+                 int64_t workspace_bytes, fp8q_stream_t stream)
+{
+    return sk_launch(a_codes, a_scales, b_codes, b_scales, y, M, N, K, a_fmt, b_fmt, y_type, splits_req, workspace,
+                     workspace_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"

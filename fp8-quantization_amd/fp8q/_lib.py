@@ -244,6 +244,10 @@ SIGNATURES = {
     "fp8q_mxh_quantize_t_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _i, _i, _u32, _i, _u64, _u64, _vp]),
     # the product of two MX operands: (a_codes, a_scales, b_codes, b_scales, y, M, N, K, a_fmt, b_fmt, y_type, stream)
     "fp8q_mxmm_nt": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp]),
+    # its small-M split-K kernel: the host plan (M, N, K, splits_req, plan4) and the product (..., y_type, splits_req,
+    # workspace, workspace_bytes, stream)
+    "fp8q_mxsk_plan": (_i, [_i64, _i64, _i64, _i64, _vp]),
+    "fp8q_mxsk_nt": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i64, _vp, _i64, _vp]),
     "fp8q_ocpbmm_nt": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "fp8q_ocpsr_encode_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _f, _vp, _u64, _u64, _vp]),
     "fp8q_ocpsr_encode_h16": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _i64, _i, _f, _vp, _u64, _u64, _vp]),

@@ -1977,6 +1977,7 @@ _MX_FP6 = (MX_E2M3, MX_E3M2)
 _MX_FMT = {torch.float8_e4m3fn: 0, torch.float8_e5m2: 1, torch.float4_e2m1fn_x2: 2, MX_E2M3: 4, MX_E3M2: 5}   # FP8Q_MX_* (include/fp8q.h; 3 is unassigned)
 _MX_ROUNDING = {"floor": 0, "ceil": 1}
 MX_BLOCK = 32
+MX_SKINNY_MAX_M = 64       # rows of A that mx_matmul(skinny=True) serves
 MX_SCALE_DTYPE = torch.float8_e8m0fnu
 
 
@@ -2350,7 +2351,23 @@ def _mx_mm_operand(codes, fmt, name):
     return fmt, (kb * 4 // 3 if fmt in _MX_FP6 else kb * (2 if fmt == torch.float4_e2m1fn_x2 else 1))
 
 
-def mx_matmul(a_codes, a_scales, b_codes, b_scales, a_fmt=None, b_fmt=None, out_dtype=torch.float32, out=None):
+def mx_skinny_plan(M, N, K, splits=None):
+    """(splits, steps_per_split, steps_per_wave, workspace_bytes) of mx_matmul(..., skinny=True) for a [M, K] x [N, K] product:
+    fp8q_mxsk_plan, the one place that decides the split (include/fp8q.h states the rule).  A step is 128 elements of K.  It
+    depends on the shape and `splits` alone, never on the device; host code, no GPU needed.  splits=None lets the plan choose; an
+    int >= 1 is clipped to the number of steps."""
+    if splits is not None and (isinstance(splits, bool) or not isinstance(splits, int) or splits < 1):
+        raise Fp8qError(f"splits must be None or an int >= 1, got {splits!r}")
+    if M > MX_SKINNY_MAX_M:
+        raise Fp8qError(f"the skinny kernel serves M <= {MX_SKINNY_MAX_M} rows after flattening, got {M}")
+    import ctypes
+    plan = (ctypes.c_int64 * 4)()
+    check(lib().fp8q_mxsk_plan(int(M), int(N), int(K), 0 if splits is None else splits, plan), "fp8q_mxsk_plan")
+    return tuple(int(v) for v in plan)
+
+
+def mx_matmul(a_codes, a_scales, b_codes, b_scales, a_fmt=None, b_fmt=None, out_dtype=torch.float32, out=None, *, skinny=False,
+              splits=None, workspace=None):
     """y[M, N] = A[M, K] . B[N, K]^T of two MX operands on gfx950's scaled matrix instruction (csrc/fp8q_mx_mm.hip; include/fp8q.h
     states the contract): the product of the operands' mx_decode values, accumulated in float32 by the instruction in an order
     that is not specified -- defined up to the summation bound stated there (the instruction's own sum of 8 neighbouring
@@ -2365,7 +2382,17 @@ def mx_matmul(a_codes, a_scales, b_codes, b_scales, a_fmt=None, b_fmt=None, out_
     for both operands and a multiple of 32: short last blocks are out of scope.  M, N >= 1 are arbitrary; an empty M or N gives
     an empty result with no launch.  The result is float32, or float16 / bfloat16 where `out` / out_dtype ask (the float32
     accumulator rounded once).  Operands are expected finite with products in float32's normal range.  One launch; no
-    autograd, no split-K or small-M kernel, no batched B."""
+    autograd, no batched B.
+    skinny=True takes the small-M split-K kernel instead (csrc/fp8q_mx_mm_skinny.hip, the entry fp8q_mxsk_nt): the same operands,
+    pairs and output types for 1 <= M <= 64 after flattening -- a decode step's few tokens against a weight matrix that is
+    streamed once.  K is cut into `splits` slices (None: mx_skinny_plan chooses from the shape; an int >= 1 is clipped to what
+    the plan can honour), each slice into four waves' sub-slices; the partial sums are added in float32 in ascending wave, then
+    ascending split order, never by atomics: equal bits on every call with the same plan, the summation bound plus
+    (splits + 2) * 2^-24 * (|A| . |B|^T), not the bits of skinny=False.  More than one split needs mx_skinny_plan(...)[3] bytes
+    of workspace: a uint8 tensor is allocated per call unless the caller passes its own (`workspace`, 16-byte aligned); two
+    launches then, one otherwise.  splits= and workspace= without skinny=True raise."""
+    if not skinny and (splits is not None or workspace is not None):
+        raise Fp8qError("splits= and workspace= belong to skinny=True")
     dt = _decode_out_dtype(out, out_dtype)
     a_fmt, K = _mx_mm_operand(a_codes, a_fmt, "a")
     b_fmt, Kb = _mx_mm_operand(b_codes, b_fmt, "b")
@@ -2379,13 +2406,16 @@ def mx_matmul(a_codes, a_scales, b_codes, b_scales, a_fmt=None, b_fmt=None, out_
     for name, s, shape in (("a_scales", a_scales, lead + (K // MX_BLOCK,)), ("b_scales", b_scales, (N, K // MX_BLOCK))):
         if isinstance(s, torch.Tensor) and tuple(s.shape) != shape:
             raise Fp8qError(f"{name} are {tuple(s.shape)}, the codes have {shape}")
+    M = 1
+    for d in lead:
+        M *= int(d)
+    plan = mx_skinny_plan(M, N, K, splits) if skinny else None      # refuses M > 64 and a bad splits= before the device check
     _require(a_codes, "a_codes", (torch.uint8, _mx_code_dtype(a_fmt)))
     _require(b_codes, "b_codes", (torch.uint8, _mx_code_dtype(b_fmt)), a_codes)
     _require(a_scales, "a_scales", (MX_SCALE_DTYPE, torch.uint8), a_codes)
     _require(b_scales, "b_scales", (MX_SCALE_DTYPE, torch.uint8), a_codes)
     a, b = a_codes.contiguous().view(torch.uint8), b_codes.contiguous().view(torch.uint8)
     sa, sb = a_scales.contiguous().view(torch.uint8), b_scales.contiguous().view(torch.uint8)
-    M = a.numel() // a.shape[-1] if a.shape[-1] else 0
     if out is None:
         y = torch.empty(lead + (N,), dtype=dt, device=a.device)
     else:
@@ -2395,6 +2425,19 @@ def mx_matmul(a_codes, a_scales, b_codes, b_scales, a_fmt=None, b_fmt=None, out_
                             f"contiguous={out.is_contiguous()})")
         y = out
     if M * N == 0:
+        return y
+    if skinny:
+        ws = workspace
+        if ws is not None:
+            _require(ws, "workspace", torch.uint8, a)
+            if not ws.is_contiguous() or ws.numel() < plan[3] or (plan[3] and ws.data_ptr() % 16):
+                raise Fp8qError(f"workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {plan[3]} bytes "
+                                f"(mx_skinny_plan), got {ws.numel()}")
+        elif plan[3]:
+            ws = torch.empty(plan[3], dtype=torch.uint8, device=a.device)
+        _run("fp8q_mxsk_nt", a, a.data_ptr(), sa.data_ptr(), b.data_ptr(), sb.data_ptr(), y.data_ptr(), M, N, K, _mx_fmt(a_fmt),
+             _mx_fmt(b_fmt), _DT[dt], 0 if splits is None else splits, ws.data_ptr() if ws is not None else None,
+             ws.numel() if ws is not None else 0)
         return y
     _run("fp8q_mxmm_nt", a, a.data_ptr(), sa.data_ptr(), b.data_ptr(), sb.data_ptr(), y.data_ptr(), M, N, K, _mx_fmt(a_fmt),
          _mx_fmt(b_fmt), _DT[dt])

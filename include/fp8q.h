@@ -1443,12 +1443,43 @@ int fp8q_mxh_quantize_t_h16(const void *x, void *y, int x_type, int y_type, int6
  * scales may start at any byte (the loads narrow from 16 bytes to 8, 4 or 1 as the pointer and the row pitch require); y must
  * be aligned to its element.  Errors, all reported before the launch: FP8Q_EUNSUPPORTED for a format id that is not one of the
  * five, 3 included; FP8Q_EINVAL for K <= 0 or K % 32 != 0, negative M or N, an unknown y_type, null pointers, a misaligned y,
- * a size whose grid overflows.  One launch, enqueue-only, no workspace.  Split-K, a small-M kernel, batched B and
- * pre-swizzled scale layouts are out of scope.
+ * a size whose grid overflows.  One launch, enqueue-only, no workspace.  Batched B and pre-swizzled scale
+ * layouts are out of scope; the split-K kernel for M <= 64 is fp8q_mxsk_nt below, an entry of its own.
  * Names: fp8q_mxmm_*; the sets of fp8q_mx_*, fp8q_mxt_*, fp8q_mxsr_* and fp8q_mxh_* entries are unchanged.  FP8Q_VERSION is
  * unchanged: the entry is additive. */
 int fp8q_mxmm_nt(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *b_codes, const uint8_t *b_scales, void *y,
                  int64_t M, int64_t N, int64_t K, int a_fmt, int b_fmt, int y_type, fp8q_stream_t stream);
+
+/* ---- the MX product for 1 <= M <= 64: a split-K kernel that streams B --------------------------------------------------------------
+ * (csrc/fp8q_mx_mm_skinny.hip)  The same product from the same operands as fp8q_mxmm_nt above (all 25 format pairs, the three
+ * y types, codes at any byte, K % 32 == 0), for the shape of a decode step: a few rows of A against a weight matrix B that is
+ * read once.  A workgroup owns 64 rows of B and one slice of K; its four waves own consecutive sub-slices; no LDS in the loop.
+ * The plan.  With nsteps = ceil(K / 128): the grid is ceil(N / 64) x S workgroups, split s owns the steps [s T, s T + T), wave
+ * w of it the steps [s T + w tw, s T + w tw + tw), both clipped to the split and to nsteps (a wave may own none).
+ *   S_want = splits_req if splits_req > 0, else ceil(512 / ceil(N / 64))   (about two workgroups per CU of a 256-CU part)
+ *   S_max  = nsteps if splits_req > 0, else max(1, nsteps / 8)             (a chosen split keeps two steps per wave)
+ *   S = clamp(S_want, 1, min(S_max, 65535)),  T = ceil(nsteps / S),  S = ceil(nsteps / T),  tw = ceil(T / 4)
+ *   workspace_bytes = 0 if S == 1, else S * M * N * 4
+ * S depends on the shape and splits_req alone, never on the device.  fp8q_mxsk_plan is host code: it fills plan4 with
+ * {S, T, tw, workspace_bytes} and returns FP8Q_EINVAL for K <= 0, K % 32 != 0, negative M or N, a null plan4 or a size whose
+ * grid overflows, FP8Q_EUNSUPPORTED for M > 64.
+ * Contract.  The result is the product of the operands' decoded values.  Each wave's sub-slice is accumulated by the
+ * instruction in ascending step order from a zero accumulator; the sub-slices are then added in float32 in ascending wave
+ * order, then ascending split order (S > 1: the splits' float32 partial results go through the workspace, a second launch adds
+ * them and rounds once to y_type).  No float atomics.  So the result is defined up to fp8q_mxmm_nt's summation bound plus
+ * (S + 2) * 2^-24 * (|A| . |B|^T) for those additions: not bit for bit against fp8q_mxmm_nt, bit for bit against itself for the
+ * same plan, on every run and every device.  Sums that need no rounding are exact under any split.
+ * fp8q_mxsk_nt: splits_req <= 0 lets the plan choose.  When the plan has S > 1, workspace must be non-null, 16-byte aligned and
+ * of at least the planned bytes; it is ignored when S == 1.  Errors, all reported before any launch: FP8Q_EUNSUPPORTED for
+ * M > 64 or a format id that is not one of the five; FP8Q_EINVAL for what fp8q_mxmm_nt refuses and for such a workspace.
+ * M == 0 or N == 0 is a no-op that returns FP8Q_OK.  Enqueue-only; it allocates nothing; one launch when S == 1, two otherwise.
+ * M > 64, batched B and pre-swizzled scale layouts are out of scope.
+ * Names: fp8q_mxsk_*; the sets of fp8q_mxmm_*, fp8q_mx_*, fp8q_mxt_*, fp8q_mxsr_* and fp8q_mxh_* entries are unchanged.
+ * FP8Q_VERSION is unchanged: the entries are additive. */
+int fp8q_mxsk_plan(int64_t M, int64_t N, int64_t K, int64_t splits_req, int64_t *plan4);
+int fp8q_mxsk_nt(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *b_codes, const uint8_t *b_scales, void *y,
+                 int64_t M, int64_t N, int64_t K, int a_fmt, int b_fmt, int y_type, int64_t splits_req, void *workspace,
+                 int64_t workspace_bytes, fp8q_stream_t stream);
 
 /* ---- the product of two block-scaled hardware FP8 operands on the matrix cores ---------------------------------------------------
  * (csrc/fp8q_ocp_block_mm.hip)  y[M, N] = A[M, K] . B[N, K]^T from what the fp8q_ocpb_* / fp8q_ocpbt_* encoders write: codes
