@@ -1,6 +1,6 @@
 // fp8q_mmq.h -- what the matrix-core products share (fp8q_mx_mm.hip: MX operands under E8M0 block scales, and its small-M
-// kernel fp8q_mx_mm_skinny.hip, which takes the chunk loads, the stores, the load width and the MX format table;
-// fp8q_ocp_block_mm.hip: hardware FP8 under float32 tile scales): the 128-row tile and its 256 lanes, an operand's panel of one
+// kernel fp8q_mx_mm_skinny.hip, which takes the chunk loads, the stores, the load width and the MX format table, and its
+// grouped form fp8q_mx_mm_grouped.hip, which takes everything and a 32-row panel besides; fp8q_ocp_block_mm.hip: hardware FP8 under float32 tile scales): the 128-row tile and its 256 lanes, an operand's panel of one
 // K step in LDS with its bank-conflict-free layout, the chunk loads that narrow with the operand's alignment, the fragment a
 // lane hands to v_mfma_*_16x16x128_f8f6f4, the masked stores of a lane's four results, and the one host rule for the load
 // width.  fp8q_mx_mm.hip's header has the instruction's operand and result layouts and the bank arithmetic.  Which bytes of a
@@ -27,16 +27,20 @@ template <> struct MmFmt<FP8Q_MX_E2M3> { static constexpr int hw = 2, bits = 6; 
 template <> struct MmFmt<FP8Q_MX_E3M2> { static constexpr int hw = 3, bits = 6; };
 template <> struct MmFmt<FP8Q_MX_E2M1> { static constexpr int hw = 4, bits = 4; };
 
-// one operand's panel of a K step in LDS (fp8q_mx_mm.hip's header has the bank arithmetic)
-template <int BITS>
+// one operand's panel of a K step in LDS (fp8q_mx_mm.hip's header has the bank arithmetic).  ROWS is 128 everywhere but in
+// fp8q_mx_mm_grouped.hip's 32-row X panel, whose 256 / 192 / 128 chunks leave lanes idle (kWhole false): chunk_at depends on
+// the row alone, so the layout and its bank arithmetic hold for any multiple of 16 rows.
+template <int BITS, int ROWS = kMmTile>
 struct MmPanel {
     static constexpr int kBlockBytes = 4 * BITS;            // one MX block: 32 / 24 / 16
     static constexpr int kStepBytes = 4 * kBlockBytes;      // a row's four blocks: 128 / 96 / 64
     static constexpr int kChunks = kStepBytes / 16;         // 8 / 6 / 4
     static constexpr bool kSwizzle = BITS != 6;
     static constexpr int kPitch = kSwizzle ? kStepBytes : kStepBytes + 16;
-    static constexpr int kBytes = kMmTile * kPitch;
-    static constexpr int kPerLane = kMmTile * kChunks / kMmBlock;   // 4 / 3 / 2 chunks per lane
+    static constexpr int kBytes = ROWS * kPitch;
+    static constexpr int kCount = ROWS * kChunks;                           // the panel's chunks
+    static constexpr int kPerLane = (kCount + kMmBlock - 1) / kMmBlock;     // 128 rows: 4 / 3 / 2 chunks per lane
+    static constexpr bool kWhole = kCount % kMmBlock == 0;                  // every lane has kPerLane chunks
     static __device__ __forceinline__ int chunk_at(int row, int c)
     {
         if constexpr (kSwizzle) return row * kPitch + 16 * (c ^ ((row / (256 / kStepBytes)) % kChunks));
@@ -85,6 +89,7 @@ __device__ __forceinline__ void mm_store_panel(uint8_t *s, const u4v (&g)[P::kPe
 #pragma unroll
     for (int j = 0; j < P::kPerLane; ++j) {
         const int q = tid + j * kMmBlock;
+        if (!P::kWhole && q >= P::kCount) continue;
         *reinterpret_cast<u4v *>(s + P::chunk_at(q / P::kChunks, q % P::kChunks)) = g[j];
     }
 }

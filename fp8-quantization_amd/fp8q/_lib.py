@@ -248,6 +248,10 @@ SIGNATURES = {
     # workspace, workspace_bytes, stream)
     "fp8q_mxsk_plan": (_i, [_i64, _i64, _i64, _i64, _vp]),
     "fp8q_mxsk_nt": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i64, _vp, _i64, _vp]),
+    # the grouped MX product: the host plan (T, N, K, G, tile_m_req, plan3) and the product (a_codes, a_scales, b_codes, b_scales,
+    # offsets, offsets_64, y, T, N, K, G, a_fmt, b_fmt, y_type, tile_m_req, workspace, workspace_bytes, stream)
+    "fp8q_mxgmm_plan": (_i, [_i64, _i64, _i64, _i64, _i64, _vp]),
+    "fp8q_mxgmm_nt": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i64, _vp, _i64, _vp]),
     "fp8q_ocpbmm_nt": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "fp8q_ocpsr_encode_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _f, _vp, _u64, _u64, _vp]),
     "fp8q_ocpsr_encode_h16": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _i64, _i, _f, _vp, _u64, _u64, _vp]),

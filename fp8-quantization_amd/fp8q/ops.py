@@ -2444,6 +2444,89 @@ def mx_matmul(a_codes, a_scales, b_codes, b_scales, a_fmt=None, b_fmt=None, out_
     return y
 
 
+# ---- the grouped MX product: one weight matrix per group of rows (csrc/fp8q_mx_mm_grouped.hip) ----
+MX_GROUPED_MAX_G = 4096
+MX_GROUPED_TILES = (32, 128)
+
+
+def mx_grouped_plan(T, N, K, G, tile_m=None):
+    """(tile_m, m_tiles_max, workspace_bytes) of mx_grouped_matmul for T rows in G groups against [G, N, K] weights:
+    fp8q_mxgmm_plan, the one place that decides the tile height (include/fp8q.h states the rule).  It depends on the shape
+    alone, never on the offsets or the device; host code, no GPU needed.  tile_m=None lets the plan choose; 32 or 128 forces it."""
+    if tile_m is not None and (isinstance(tile_m, bool) or tile_m not in MX_GROUPED_TILES):
+        raise Fp8qError(f"tile_m must be None, 32 or 128, got {tile_m!r}")
+    if G > MX_GROUPED_MAX_G:
+        raise Fp8qError(f"the grouped product serves G <= {MX_GROUPED_MAX_G} groups, got {G}")
+    import ctypes
+    plan = (ctypes.c_int64 * 3)()
+    check(lib().fp8q_mxgmm_plan(int(T), int(N), int(K), int(G), tile_m or 0, plan), "fp8q_mxgmm_plan")
+    return tuple(int(v) for v in plan)
+
+
+def mx_grouped_matmul(a_codes, a_scales, b_codes, b_scales, offsets, a_fmt=None, b_fmt=None, out_dtype=torch.float32, out=None,
+                      *, tile_m=None, workspace=None):
+    """y[o_g : o_{g+1}, :] = A[o_g : o_{g+1}, :] . B[g]^T for every group g in [0, G): the expert products of a mixture-of-experts
+    layer in two launches with no host sync (csrc/fp8q_mx_mm_grouped.hip, the entry fp8q_mxgmm_nt; include/fp8q.h states the
+    contract).  a_codes [T, K'] / a_scales [T, K / 32] are what mx_encode writes, rows sorted by group; b_codes [G, N, K'] /
+    b_scales [G, N, K / 32] are mx_encode of the [G * N, K] weights viewed 3-D.  Formats are told as mx_matmul tells them; all 25
+    pairs, float32 / float16 / bfloat16 results, K a positive multiple of 32, any N >= 1.
+    offsets [G + 1] is an int32 or int64 tensor ON THE DEVICE with 0 = o_0 <= o_1 <= ... <= o_G <= T.  Only the kernels read it:
+    nothing here copies it to the host or decides by its contents.  Rows [o_G, T) of y are not written (capacity padding: pass
+    `out` to choose what they hold).  Offsets outside the contract give unspecified values in y and never an access outside the
+    operands or y.
+    The result is [T, N]; each element is formed exactly as mx_matmul forms it, so it has mx_matmul's bound and the bits of
+    mx_matmul on the group's slices.  tile_m: None lets mx_grouped_plan choose from the shape (32 rows per workgroup when the
+    average group has at most 32, else 128); 32 or 128 forces it.  The call needs mx_grouped_plan(...)[2] bytes of workspace
+    for the tile table: a uint8 tensor is allocated per call unless the caller passes its own (`workspace`, 16-byte aligned).
+    An empty T, N or G launches nothing.  No autograd."""
+    dt = _decode_out_dtype(out, out_dtype)
+    a_fmt, K = _mx_mm_operand(a_codes, a_fmt, "a")
+    b_fmt, Kb = _mx_mm_operand(b_codes, b_fmt, "b")
+    if a_codes.dim() != 2 or b_codes.dim() != 3:
+        raise Fp8qError(f"a_codes must be 2-D [T, K'] and b_codes 3-D [G, N, K'], got {tuple(a_codes.shape)} and "
+                        f"{tuple(b_codes.shape)}")
+    if K != Kb:
+        raise Fp8qError(f"the operands disagree on K: a has {K} elements along its last dimension, b has {Kb}")
+    if K == 0 or K % MX_BLOCK:
+        raise Fp8qError(f"K must be a positive multiple of {MX_BLOCK} (short last blocks are out of scope), got {K}")
+    T, (G, N) = int(a_codes.shape[0]), (int(d) for d in b_codes.shape[:2])
+    for name, s, shape in (("a_scales", a_scales, (T, K // MX_BLOCK)), ("b_scales", b_scales, (G, N, K // MX_BLOCK)),
+                           ("offsets", offsets, (G + 1,))):
+        if isinstance(s, torch.Tensor) and tuple(s.shape) != shape:
+            raise Fp8qError(f"{name} are {tuple(s.shape)}, the codes have {shape}")
+    plan = mx_grouped_plan(T, N, K, G, tile_m)      # refuses a bad tile_m=, G > 4096 and a table too long for one grid
+    _require(a_codes, "a_codes", (torch.uint8, _mx_code_dtype(a_fmt)))
+    _require(b_codes, "b_codes", (torch.uint8, _mx_code_dtype(b_fmt)), a_codes)
+    _require(a_scales, "a_scales", (MX_SCALE_DTYPE, torch.uint8), a_codes)
+    _require(b_scales, "b_scales", (MX_SCALE_DTYPE, torch.uint8), a_codes)
+    _require(offsets, "offsets", (torch.int32, torch.int64), a_codes)
+    a, b = a_codes.contiguous().view(torch.uint8), b_codes.contiguous().view(torch.uint8)
+    sa, sb = a_scales.contiguous().view(torch.uint8), b_scales.contiguous().view(torch.uint8)
+    off = offsets.contiguous()
+    if out is None:
+        y = torch.empty((T, N), dtype=dt, device=a.device)
+    else:
+        _require(out, "out", dt, a)
+        if out.numel() != T * N or not out.is_contiguous():
+            raise Fp8qError(f"out must be a contiguous tensor of {T * N} elements (got {tuple(out.shape)}, "
+                            f"contiguous={out.is_contiguous()})")
+        y = out
+    ws = workspace
+    if ws is not None:
+        _require(ws, "workspace", torch.uint8, a)
+        if not ws.is_contiguous() or ws.numel() < plan[2] or (plan[2] and ws.data_ptr() % 16):
+            raise Fp8qError(f"workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {plan[2]} bytes "
+                            f"(mx_grouped_plan), got {ws.numel()}")
+    if T * N * G == 0:
+        return y
+    if ws is None:
+        ws = torch.empty(plan[2], dtype=torch.uint8, device=a.device)
+    _run("fp8q_mxgmm_nt", a, a.data_ptr(), sa.data_ptr(), b.data_ptr(), sb.data_ptr(), off.data_ptr(),
+         int(off.dtype == torch.int64), y.data_ptr(), T, N, K, G, _mx_fmt(a_fmt), _mx_fmt(b_fmt), _DT[dt], tile_m or 0,
+         ws.data_ptr(), ws.numel())
+    return y
+
+
 # ---- the product of two block-scaled hardware FP8 operands on the matrix cores (csrc/fp8q_ocp_block_mm.hip) ----
 OCP_BLOCK_MM_TILES = ((1, 128), (128, 128))
 

@@ -1481,6 +1481,43 @@ int fp8q_mxsk_nt(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t 
                  int64_t M, int64_t N, int64_t K, int a_fmt, int b_fmt, int y_type, int64_t splits_req, void *workspace,
                  int64_t workspace_bytes, fp8q_stream_t stream);
 
+/* ---- the grouped MX product: one weight matrix per group of rows, no host sync ---------------------------------------------------
+ * (csrc/fp8q_mx_mm_grouped.hip)  For every group g in [0, G): y[o_g : o_{g+1}, :] = A[o_g : o_{g+1}, :] . B[g]^T, the expert
+ * products of a mixture-of-experts layer.  a_codes / a_scales are fp8q_mxmm_nt's A with T rows, sorted by group; b_codes /
+ * b_scales are the operands of the [G * N, K] weights, group g the rows [g N, g N + N); all 25 format pairs, the three y
+ * types, codes at any byte, K % 32 == 0, any N >= 1.  y is [T, N] row-major.  offsets is a DEVICE array of G + 1 int32
+ * (offsets_64 == 0) or int64 values, aligned to its element; only the kernels read it: the call is enqueue-only, never waits
+ * for the device and takes no host decision that depends on the offsets' contents.
+ * Offsets.  The contract is 0 = o_0 <= o_1 <= ... <= o_G <= T; rows [o_G, T) of y are not written (capacity padding).  Both
+ * kernels use, for group g, start = min(max(o_g, 0), T) and end = min(max(o_{g+1}, start), T), from those two values alone.
+ * Offsets outside the contract therefore give unspecified values in y, but every row read or written lies in [0, T): never
+ * an access outside the operands, y or the workspace.
+ * The plan.  fp8q_mxgmm_plan is host code, a function of the shape alone; it fills plan3 with {tile_m, m_tiles_max,
+ * workspace_bytes}.  With n = min(G, T):
+ *   tile_m          = tile_m_req if it is 32 or 128; for 0: 32 when T <= 32 n (an average group of at most 32 rows), else 128
+ *   m_tiles_max     = (T - n) / tile_m + n   (integer division: the largest sum over g of ceil(c_g / tile_m) over all counts c_g
+ *                     with sum c_g <= T, reached by n - 1 groups of one row and one group of the rest); 0 when n == 0
+ *   workspace_bytes = 8 * m_tiles_max
+ * Two launches: k_mxg_map (one workgroup) writes workspace[m_tiles_max] of (int32 group, int32 first row), group -1 past the
+ * last tile, by a block scan of the groups' tile counts and a binary search; k_mxgmm, grid ceil(N / 128) x m_tiles_max, runs
+ * fp8q_mxmm_nt's step loop on each listed tile.  tile_m 128 is that kernel's 2 x 2 waves of 64 x 64; tile_m 32 has the four
+ * waves side by side along N, each 32 rows of A by 32 rows of B.
+ * Contract.  Each element of y is formed as in fp8q_mxmm_nt: the same instruction chain in ascending K from a zero accumulator,
+ * so its summation bound holds, exact sums are exact, and the bits equal those of fp8q_mxmm_nt on the group's slices, for
+ * either tile_m.
+ * Errors, all reported before any launch: FP8Q_EUNSUPPORTED for a format id that is not one of the five, G > 4096, a
+ * tile_m_req other than 0, 32, 128; FP8Q_EINVAL for K <= 0 or K % 32 != 0, negative T, N or G, T > INT32_MAX,
+ * m_tiles_max > 65535, an unknown y_type, null pointers, a misaligned y or offsets, a workspace that is null, smaller than
+ * planned or off its 16-byte alignment, a null plan3, a size that overflows.  T == 0, N == 0 or G == 0 is a no-op that returns
+ * FP8Q_OK.  It allocates nothing.  K-grouped products (dW per expert), gather / scatter by token, split-K inside a group
+ * and pre-swizzled scale layouts are out of scope.
+ * Names: fp8q_mxgmm_*; the sets of fp8q_mxmm_*, fp8q_mxsk_*, fp8q_mx_*, fp8q_mxt_*, fp8q_mxsr_* and fp8q_mxh_* entries are
+ * unchanged.  FP8Q_VERSION is unchanged: the entries are additive. */
+int fp8q_mxgmm_plan(int64_t T, int64_t N, int64_t K, int64_t G, int64_t tile_m_req, int64_t *plan3);
+int fp8q_mxgmm_nt(const uint8_t *a_codes, const uint8_t *a_scales, const uint8_t *b_codes, const uint8_t *b_scales,
+                  const void *offsets, int offsets_64, void *y, int64_t T, int64_t N, int64_t K, int64_t G, int a_fmt, int b_fmt,
+                  int y_type, int64_t tile_m_req, void *workspace, int64_t workspace_bytes, fp8q_stream_t stream);
+
 /* ---- the product of two block-scaled hardware FP8 operands on the matrix cores ---------------------------------------------------
  * (csrc/fp8q_ocp_block_mm.hip)  y[M, N] = A[M, K] . B[N, K]^T from what the fp8q_ocpb_* / fp8q_ocpbt_* encoders write: codes
  * [rows, K] bytes, K contiguous, a_fmt / b_fmt FP8Q_OCP_E4M3FN or FP8Q_OCP_E5M2 independently; scales float32
