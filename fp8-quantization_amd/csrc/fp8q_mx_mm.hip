@@ -41,125 +41,21 @@
 //   Writes are one 16-byte chunk per lane, consecutive lanes consecutive chunks of a row: 8 (FP8) or 4 (FP4) lanes fill one
 //   row's banks under a permutation, the next row the other half (FP8) or the next quarter (FP4): conflict-free per 16 lanes.
 // There is no float arithmetic outside the instruction and the final conversion to a half type.
-// The tile, the panel, the chunk load, the fragment read, the stores and mm_load_width are in fp8q_mmq.h, which
-// fp8q_ocp_block_mm.hip shares; the MX format table (MmFmt, mm_fmt_known, mm_block_bytes) is there too, shared with the
-// small-M kernel of fp8q_mx_mm_skinny.hip.
+// fp8q_mmq.h has all of it: the tile, the panel and its loaders, the fragment read, the stores, and the tile body mm_mx_tile
+// that this kernel and the grouped product's (fp8q_mx_mm_grouped.hip) both are; this unit is the kernel's shell and its launcher.
 #include "fp8q_mmq.h"
 
 namespace {
 
-struct MmArgs {
-    const uint8_t *xc, *xs, *wc, *ws;   // codes and scales of X (rows m) and W (rows n)
-    void *y;
-    int64_t M, N, kblocks;              // kblocks = K / 32
-    int64_t xpitch, wpitch;             // bytes of a codes row
-    int nsteps;                         // ceil(K / 128)
-    int xw, ww;                         // bytes per global load of either operand's codes: 16, 8, 4 or 1
-    int y_type;                         // FP8Q_DT_*
-    int vec_store;                      // N % 4 == 0 and y aligned to four of its elements
+struct MmArgs : MxOperands {
+    int64_t M;
 };
-
-// step ks of the panel rows [row0, row0 + 128): lane tid takes the chunks tid, tid + 256, ...  Chunk (r, c) is the bytes
-// [o, o + 16) of row row0 + r, o = ks * kStepBytes + 16 c.  It is read only for row0 + r < rows, and then its first
-// min(pitch - o, 16) bytes where that is positive: pitch % 8 == 0 and o % 16 == 0, so this is 16, 8 or nothing, and every
-// byte read lies in [row * pitch, row * pitch + pitch) of a buffer of rows * pitch bytes.
-template <class P>
-__device__ __forceinline__ void mm_load_panel(u4v (&g)[P::kPerLane], const uint8_t *codes, int64_t pitch, int64_t rows,
-                                              int64_t row0, int ks, int w, int tid)
-{
-#pragma unroll
-    for (int j = 0; j < P::kPerLane; ++j) {
-        const int q = tid + j * kMmBlock, r = q / P::kChunks, c = q % P::kChunks;
-        const int64_t row = row0 + r, o = (int64_t)ks * P::kStepBytes + 16 * c, left = pitch - o;
-        const int nvalid = row < rows ? (left >= 16 ? 16 : (left >= 8 ? 8 : 0)) : 0;
-        g[j] = mm_load_chunk(codes + row * pitch + o, nvalid, w);
-    }
-}
-
-// the scale bytes of block `blk` of the rows row, row + 16, row + 32, row + 48; 127 where the row or the block does not exist
-__device__ __forceinline__ void mm_load_scales(int (&s)[4], const uint8_t *scales, int64_t rows, int64_t row, int64_t blk,
-                                               int64_t kblocks)
-{
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int64_t r = row + 16 * t;
-        s[t] = (r < rows && blk < kblocks) ? (int)scales[r * kblocks + blk] : kMmScaleOne;
-    }
-}
 
 template <int FX, int FW>
 __global__ void __launch_bounds__(kMmBlock)
 k_mxmm(const MmArgs a)
 {
-    using PX = MmPanel<MmFmt<FX>::bits>;
-    using PW = MmPanel<MmFmt<FW>::bits>;
-    __shared__ __attribute__((aligned(16))) uint8_t s_x[2][PX::kBytes];
-    __shared__ __attribute__((aligned(16))) uint8_t s_w[2][PW::kBytes];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;        // the wave's 64 x 64 quarter
-    const int lr = lane & 15, lg = lane >> 4;       // the lane's row of an instruction; the MX block of the step it scales
-    const int64_t m0 = (int64_t)blockIdx.y * kMmTile, n0 = (int64_t)blockIdx.x * kMmTile;
-    const int64_t xrow = m0 + wm * 64 + lr, wrow = n0 + wn * 64 + lr;   // (+ 16 j / 16 i: the rows whose scales the lane feeds)
-
-    u4v gx[PX::kPerLane], gw[PW::kPerLane];
-    int sx[4], sw[4], sx_next[4], sw_next[4];
-    f4v acc[4][4];      // [i: W's 16 rows][j: X's 16 rows]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
-
-    mm_load_panel<PX>(gx, a.xc, a.xpitch, a.M, m0, 0, a.xw, tid);
-    mm_load_panel<PW>(gw, a.wc, a.wpitch, a.N, n0, 0, a.ww, tid);
-    mm_load_scales(sx, a.xs, a.M, xrow, lg, a.kblocks);
-    mm_load_scales(sw, a.ws, a.N, wrow, lg, a.kblocks);
-    mm_store_panel<PX>(s_x[0], gx, tid);
-    mm_store_panel<PW>(s_w[0], gw, tid);
-    __syncthreads();
-
-    for (int ks = 0; ks < a.nsteps; ++ks) {
-        const int buf = ks & 1;
-        const bool more = ks + 1 < a.nsteps;
-        if (more) {         // the next step's loads fly over this step's instructions
-            mm_load_panel<PX>(gx, a.xc, a.xpitch, a.M, m0, ks + 1, a.xw, tid);
-            mm_load_panel<PW>(gw, a.wc, a.wpitch, a.N, n0, ks + 1, a.ww, tid);
-            mm_load_scales(sx_next, a.xs, a.M, xrow, 4 * (int64_t)(ks + 1) + lg, a.kblocks);
-            mm_load_scales(sw_next, a.ws, a.N, wrow, 4 * (int64_t)(ks + 1) + lg, a.kblocks);
-        }
-        i8v fw[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) fw[i] = mm_read_frag<PW>(s_w[buf], wn * 64 + 16 * i + lr, lg);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const i8v fx = mm_read_frag<PX>(s_x[buf], wm * 64 + 16 * j + lr, lg);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw[i], fx, acc[i][j], MmFmt<FW>::hw, MmFmt<FX>::hw,
-                                                                             0, sw[i], 0, sx[j]);
-        }
-        if (more) {
-            // the other buffer: every wave left it at the barrier that ended the step before
-            mm_store_panel<PX>(s_x[buf ^ 1], gx, tid);
-            mm_store_panel<PW>(s_w[buf ^ 1], gw, tid);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) sx[t] = sx_next[t], sw[t] = sw_next[t];
-        }
-        __syncthreads();
-    }
-
-    // lane l, register r of acc[i][j]: y[m0 + 64 wm + 16 j + l % 16][n0 + 64 wn + 16 i + 4 (l / 16) + r]
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t m = xrow + 16 * j;
-        if (m >= a.M) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int64_t n = n0 + wn * 64 + 16 * i + 4 * lg;
-            if (n >= a.N) continue;
-            const int64_t left = a.N - n;
-            mm_store4(a.y, a.y_type, m * a.N + n, acc[i][j], left < 4 ? (int)left : 4, a.vec_store != 0);
-        }
-    }
+    mm_mx_tile<FX, FW, kMmTile, 2, 2>(a, (int64_t)blockIdx.y * kMmTile, (int64_t)blockIdx.x * kMmTile, a.M, a.wc, a.ws);
 }
 
 // ---- host side ----
@@ -168,29 +64,20 @@ int mm_launch(const uint8_t *xc, const uint8_t *xs, const uint8_t *wc, const uin
 {
     if (!mm_fmt_known(x_fmt) || !mm_fmt_known(w_fmt)) return FP8Q_EUNSUPPORTED;
     if (K <= 0 || K % 32 || M < 0 || N < 0) return FP8Q_EINVAL;
-    if (y_type != FP8Q_DT_F32 && !half_type(y_type)) return FP8Q_EINVAL;
+    const int ybytes = mm_y_bytes(y_type);
+    if (!ybytes) return FP8Q_EINVAL;
     if (M == 0 || N == 0) return FP8Q_OK;
     if (!xc || !xs || !wc || !ws || !y) return FP8Q_EINVAL;
-    const int ybytes = y_type == FP8Q_DT_F32 ? 4 : 2;
     if ((uintptr_t)y % (uintptr_t)ybytes) return FP8Q_EINVAL;
-    const int64_t kblocks = K / 32, gm = cdiv(M, kMmTile), gn = cdiv(N, kMmTile);
-    if (kblocks > (int64_t)INT32_MAX || gm > 65535 || gn > (int64_t)INT32_MAX || M > INT64_MAX / N) return FP8Q_EINVAL;
+    const int64_t gm = cdiv(M, kMmTile), gn = cdiv(N, kMmTile);
+    if (K / 32 > (int64_t)INT32_MAX || gm > 65535 || gn > (int64_t)INT32_MAX || M > INT64_MAX / N) return FP8Q_EINVAL;
     MmArgs a;
-    a.xc = xc, a.xs = xs, a.wc = wc, a.ws = ws, a.y = y;
-    a.M = M, a.N = N, a.kblocks = kblocks;
-    a.xpitch = kblocks * mm_block_bytes(x_fmt);
-    a.wpitch = kblocks * mm_block_bytes(w_fmt);
-    a.nsteps = (int)cdiv(kblocks, 4);
-    a.xw = mm_load_width(xc, a.xpitch);
-    a.ww = mm_load_width(wc, a.wpitch);
+    mm_mx_operands(a, xc, xs, wc, ws, K, x_fmt, w_fmt);
+    a.y = y, a.M = M, a.N = N;
     a.y_type = y_type;
-    a.vec_store = N % 4 == 0 && (uintptr_t)y % (uintptr_t)(4 * ybytes) == 0;
+    a.vec_store = mm_vec_store(N, y, ybytes);
     const dim3 grid((unsigned)gn, (unsigned)gm), block(kMmBlock);
-    dispatch<FP8Q_MX_E4M3FN, FP8Q_MX_E5M2, FP8Q_MX_E2M1, FP8Q_MX_E2M3, FP8Q_MX_E3M2>(x_fmt, [&](auto FX) {
-        dispatch<FP8Q_MX_E4M3FN, FP8Q_MX_E5M2, FP8Q_MX_E2M1, FP8Q_MX_E2M3, FP8Q_MX_E3M2>(w_fmt, [&](auto FW) {
-            hipLaunchKernelGGL((k_mxmm<FX(), FW()>), grid, block, 0, st, a);
-        });
-    });
+    mm_dispatch_mx_pair(x_fmt, w_fmt, [&](auto FX, auto FW) { hipLaunchKernelGGL((k_mxmm<FX(), FW()>), grid, block, 0, st, a); });
     return launch_rc();
 }
 

@@ -21,13 +21,12 @@
 //
 // k_mxgmm<FX, FW, TM, WM, WN>: grid ceil(N / 128) x m_tiles_max, N fastest as in k_mxmm, so the workgroups that share an X
 // tile and the ones that share a group's W panel run together.  A workgroup loads its table entry (8 bytes), returns if the
-// group is -1 (or, defensively, not in [0, G), or row0 not in [start, end)), recomputes end, and runs k_mxmm's step loop --
-// two LDS buffers, the next step's global loads issued before this step's instructions, one barrier per step -- on X rows
-// [row0, min(row0 + TM, end)) and the group's W: codes at wc + g * N * wpitch, scales at ws + g * N * kblocks.  (g * N * wpitch
-// is a multiple of the pitch, so mm_load_width of the base pointer holds for every group.)  X rows past `end` are zero codes
-// under scale byte 127, never the next group's rows; stores are masked by m < end, n < N.
-// One body over (TM, WM waves along M, WN waves along N), WM * WN = 4; a wave owns TM / WM rows of X (JX fragments of 16) and
-// 128 / WN rows of W (IW fragments), IW x JX instructions per step into acc[IW][JX]:
+// group is -1 (or, defensively, not in [0, G), or row0 not in [start, end)), recomputes end, and runs the tile body that
+// k_mxmm runs (fp8q_mmq.h's mm_mx_tile: prologue, step loop, store) on X rows [row0, min(row0 + TM, end)) and the group's W:
+// codes at wc + g * N * wpitch, scales at ws + g * N * kblocks.  (g * N * wpitch is a multiple of the pitch, so mm_load_width
+// of the base pointer holds for every group.)  X rows past `end` are zero codes under scale byte 127, never the next group's
+// rows; stores are masked by m < end, n < N.
+// The body's geometry (TM, WM waves along M, WN waves along N):
 //   TM = 128, 2 x 2: k_mxmm's geometry, 64 x 64 per wave, acc[4][4].
 //   TM = 32,  1 x 4: the four waves split N.  Wave w takes all 32 rows of X and W rows [32 w, 32 w + 32): 2 x 2 instructions
 //        per step into acc[2][2], 16 accumulator registers.  The W panel is unchanged; the X panel is MmPanel<bits, 32>: 256 /
@@ -36,7 +35,7 @@
 //        alone, a read pass is still one lane group over 16 consecutive rows from a multiple of 16, and a write pass still
 //        consecutive lanes over consecutive chunks of a row, so fp8q_mx_mm.hip's header holds line for line for 32 rows.
 // Each output element is the same ascending chain of instructions over the same two rows as in k_mxmm, from a zero
-// accumulator: the same bits as fp8q_mxmm_nt on the group's slices, whichever TM.
+// accumulator: the same bits as fp8q_mxmm_nt on the group's slices, whichever TM (at TM = 128 it is the same code).
 #include "fp8q_mmq.h"
 
 namespace {
@@ -48,18 +47,11 @@ struct GmPlan {
     int64_t tile_m, m_tiles_max, ws_bytes;
 };
 
-struct GmArgs {
-    const uint8_t *xc, *xs, *wc, *ws;   // codes and scales of X (rows m, all groups) and W (rows g * N + n)
-    void *y;
+struct GmArgs : MxOperands {            // X: the rows of all groups; W: rows g * N + n
     const void *offsets;                // [G + 1], int64 (off64) or int32
     const int2 *table;                  // [m_tiles_max] of (group, row0), k_mxg_map's
-    int64_t T, N, kblocks;              // kblocks = K / 32
-    int64_t xpitch, wpitch;             // bytes of a codes row
+    int64_t T;
     int G, off64;
-    int nsteps;                         // ceil(K / 128)
-    int xw, ww;                         // bytes per global load of either operand's codes: 16, 8, 4 or 1
-    int y_type;                         // FP8Q_DT_*
-    int vec_store;                      // N % 4 == 0 and y aligned to four of its elements
 };
 
 // rows [start, end) of group g, 0 <= start <= end <= T whatever offsets[g], offsets[g + 1] hold (the header's clamp)
@@ -124,47 +116,10 @@ k_mxg_map(const void *offsets, int off64, int G, int64_t T, int TM, int2 *table,
     }
 }
 
-// step ks of the panel rows [row0, row0 + P's rows) of an operand whose rows end at `rows`: fp8q_mx_mm.hip's mm_load_panel (a
-// chunk is read only for a row < rows and only where it lies in its row: 16, 8 or no bytes), with the lanes past a 32-row
-// panel's chunk count idle
-template <class P>
-__device__ __forceinline__ void gm_load_panel(u4v (&g)[P::kPerLane], const uint8_t *codes, int64_t pitch, int64_t rows,
-                                              int64_t row0, int ks, int w, int tid)
-{
-#pragma unroll
-    for (int j = 0; j < P::kPerLane; ++j) {
-        const int q = tid + j * kMmBlock, r = q / P::kChunks, c = q % P::kChunks;
-        const int64_t row = row0 + r, o = (int64_t)ks * P::kStepBytes + 16 * c, left = pitch - o;
-        const bool in = (P::kWhole || q < P::kCount) && row < rows;
-        const int nvalid = in ? (left >= 16 ? 16 : (left >= 8 ? 8 : 0)) : 0;
-        g[j] = mm_load_chunk(codes + row * pitch + o, nvalid, w);
-    }
-}
-
-// the scale bytes of block `blk` of the rows row, row + 16, ...; 127 where the row or the block does not exist
-template <int NF>
-__device__ __forceinline__ void gm_load_scales(int (&s)[NF], const uint8_t *scales, int64_t rows, int64_t row, int64_t blk,
-                                               int64_t kblocks)
-{
-#pragma unroll
-    for (int t = 0; t < NF; ++t) {
-        const int64_t r = row + 16 * t;
-        s[t] = (r < rows && blk < kblocks) ? (int)scales[r * kblocks + blk] : kMmScaleOne;
-    }
-}
-
 template <int FX, int FW, int TM, int WM, int WN>
 __global__ void __launch_bounds__(kMmBlock)
 k_mxgmm(const GmArgs a)
 {
-    static_assert(WM * WN == 4 && TM % (16 * WM) == 0 && kMmTile % (16 * WN) == 0, "four waves tile TM x 128");
-    using PX = MmPanel<MmFmt<FX>::bits, TM>;
-    using PW = MmPanel<MmFmt<FW>::bits>;
-    constexpr int XR = TM / WM, WR = kMmTile / WN;      // the wave's rows of X and of W
-    constexpr int JX = XR / 16, IW = WR / 16;
-    __shared__ __attribute__((aligned(16))) uint8_t s_x[2][PX::kBytes];
-    __shared__ __attribute__((aligned(16))) uint8_t s_w[2][PW::kBytes];
-
     const int2 entry = a.table[blockIdx.y];
     const int grp = entry.x;
     if (grp < 0 || grp >= a.G) return;
@@ -172,75 +127,8 @@ k_mxgmm(const GmArgs a)
     gm_group_rows(a.offsets, a.off64, grp, a.T, start, end);
     const int64_t m0 = entry.y;
     if (m0 < start || m0 >= end) return;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WN, wn = wave % WN;
-    const int lr = lane & 15, lg = lane >> 4;       // the lane's row of an instruction; the MX block of the step it scales
-    const int64_t n0 = (int64_t)blockIdx.x * kMmTile;
-    const int64_t xrow = m0 + wm * XR + lr, wrow = n0 + wn * WR + lr;   // (+ 16 j / 16 i: the rows whose scales the lane feeds)
-    const uint8_t *wc = a.wc + (int64_t)grp * a.N * a.wpitch, *ws = a.ws + (int64_t)grp * a.N * a.kblocks;
-
-    u4v gx[PX::kPerLane], gw[PW::kPerLane];
-    int sx[JX], sw[IW], sx_next[JX], sw_next[IW];
-    f4v acc[IW][JX];    // [i: W's 16 rows][j: X's 16 rows]
-#pragma unroll
-    for (int i = 0; i < IW; ++i)
-#pragma unroll
-        for (int j = 0; j < JX; ++j) acc[i][j] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
-
-    gm_load_panel<PX>(gx, a.xc, a.xpitch, end, m0, 0, a.xw, tid);
-    gm_load_panel<PW>(gw, wc, a.wpitch, a.N, n0, 0, a.ww, tid);
-    gm_load_scales<JX>(sx, a.xs, end, xrow, lg, a.kblocks);
-    gm_load_scales<IW>(sw, ws, a.N, wrow, lg, a.kblocks);
-    mm_store_panel<PX>(s_x[0], gx, tid);
-    mm_store_panel<PW>(s_w[0], gw, tid);
-    __syncthreads();
-
-    for (int ks = 0; ks < a.nsteps; ++ks) {
-        const int buf = ks & 1;
-        const bool more = ks + 1 < a.nsteps;
-        if (more) {         // the next step's loads fly over this step's instructions
-            gm_load_panel<PX>(gx, a.xc, a.xpitch, end, m0, ks + 1, a.xw, tid);
-            gm_load_panel<PW>(gw, wc, a.wpitch, a.N, n0, ks + 1, a.ww, tid);
-            gm_load_scales<JX>(sx_next, a.xs, end, xrow, 4 * (int64_t)(ks + 1) + lg, a.kblocks);
-            gm_load_scales<IW>(sw_next, ws, a.N, wrow, 4 * (int64_t)(ks + 1) + lg, a.kblocks);
-        }
-        i8v fw[IW];
-#pragma unroll
-        for (int i = 0; i < IW; ++i) fw[i] = mm_read_frag<PW>(s_w[buf], wn * WR + 16 * i + lr, lg);
-#pragma unroll
-        for (int j = 0; j < JX; ++j) {
-            const i8v fx = mm_read_frag<PX>(s_x[buf], wm * XR + 16 * j + lr, lg);
-#pragma unroll
-            for (int i = 0; i < IW; ++i)
-                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw[i], fx, acc[i][j], MmFmt<FW>::hw, MmFmt<FX>::hw,
-                                                                             0, sw[i], 0, sx[j]);
-        }
-        if (more) {
-            // the other buffer: every wave left it at the barrier that ended the step before
-            mm_store_panel<PX>(s_x[buf ^ 1], gx, tid);
-            mm_store_panel<PW>(s_w[buf ^ 1], gw, tid);
-#pragma unroll
-            for (int t = 0; t < JX; ++t) sx[t] = sx_next[t];
-#pragma unroll
-            for (int t = 0; t < IW; ++t) sw[t] = sw_next[t];
-        }
-        __syncthreads();
-    }
-
-    // lane l, register r of acc[i][j]: y[m0 + XR wm + 16 j + l % 16][n0 + WR wn + 16 i + 4 (l / 16) + r]
-#pragma unroll
-    for (int j = 0; j < JX; ++j) {
-        const int64_t m = xrow + 16 * j;
-        if (m >= end) continue;
-#pragma unroll
-        for (int i = 0; i < IW; ++i) {
-            const int64_t n = n0 + wn * WR + 16 * i + 4 * lg;
-            if (n >= a.N) continue;
-            const int64_t left = a.N - n;
-            mm_store4(a.y, a.y_type, m * a.N + n, acc[i][j], left < 4 ? (int)left : 4, a.vec_store != 0);
-        }
-    }
+    mm_mx_tile<FX, FW, TM, WM, WN>(a, m0, (int64_t)blockIdx.x * kMmTile, end, a.wc + (int64_t)grp * a.N * a.wpitch,
+                                   a.ws + (int64_t)grp * a.N * a.kblocks);
 }
 
 // ---- host side ----
@@ -265,10 +153,10 @@ int gm_launch(const uint8_t *xc, const uint8_t *xs, const uint8_t *wc, const uin
     if (!mm_fmt_known(x_fmt) || !mm_fmt_known(w_fmt)) return FP8Q_EUNSUPPORTED;
     GmPlan p;
     if (const int rc = gm_plan(T, N, K, G, tile_m_req, p)) return rc;
-    if (y_type != FP8Q_DT_F32 && !half_type(y_type)) return FP8Q_EINVAL;
+    const int ybytes = mm_y_bytes(y_type);
+    if (!ybytes) return FP8Q_EINVAL;
     if (T == 0 || N == 0 || G == 0) return FP8Q_OK;
     if (!xc || !xs || !wc || !ws || !offsets || !y) return FP8Q_EINVAL;
-    const int ybytes = y_type == FP8Q_DT_F32 ? 4 : 2;
     if ((uintptr_t)y % (uintptr_t)ybytes || (uintptr_t)offsets % (uintptr_t)(off64 ? 8 : 4)) return FP8Q_EINVAL;
     if (!workspace || workspace_bytes < p.ws_bytes || (uintptr_t)workspace % 16) return FP8Q_EINVAL;
     const int64_t kblocks = K / 32, gn = cdiv(N, kMmTile);
@@ -276,26 +164,19 @@ int gm_launch(const uint8_t *xc, const uint8_t *xs, const uint8_t *wc, const uin
     if (kblocks > (int64_t)INT32_MAX || gn > (int64_t)INT32_MAX || N > (INT64_MAX >> 13) / (32 * kblocks) || T > INT64_MAX / N)
         return FP8Q_EINVAL;
     GmArgs a;
-    a.xc = xc, a.xs = xs, a.wc = wc, a.ws = ws, a.y = y;
-    a.offsets = offsets, a.table = static_cast<const int2 *>(workspace);
-    a.T = T, a.N = N, a.kblocks = kblocks;
-    a.xpitch = kblocks * mm_block_bytes(x_fmt);
-    a.wpitch = kblocks * mm_block_bytes(w_fmt);
-    a.G = (int)G, a.off64 = off64;
-    a.nsteps = (int)cdiv(kblocks, 4);
-    a.xw = mm_load_width(xc, a.xpitch);
-    a.ww = mm_load_width(wc, a.wpitch);
+    mm_mx_operands(a, xc, xs, wc, ws, K, x_fmt, w_fmt);
+    a.y = y, a.N = N;
     a.y_type = y_type;
-    a.vec_store = N % 4 == 0 && (uintptr_t)y % (uintptr_t)(4 * ybytes) == 0;
+    a.vec_store = mm_vec_store(N, y, ybytes);
+    a.offsets = offsets, a.table = static_cast<const int2 *>(workspace);
+    a.T = T, a.G = (int)G, a.off64 = off64;
     hipLaunchKernelGGL(k_mxg_map, dim3(1), dim3(kMmBlock), 0, st, offsets, off64, (int)G, T, (int)p.tile_m,
                        static_cast<int2 *>(workspace), (int)p.m_tiles_max);
     if (const int rc = launch_rc()) return rc;
     const dim3 grid((unsigned)gn, (unsigned)p.m_tiles_max), block(kMmBlock);
-    dispatch<FP8Q_MX_E4M3FN, FP8Q_MX_E5M2, FP8Q_MX_E2M1, FP8Q_MX_E2M3, FP8Q_MX_E3M2>(x_fmt, [&](auto FX) {
-        dispatch<FP8Q_MX_E4M3FN, FP8Q_MX_E5M2, FP8Q_MX_E2M1, FP8Q_MX_E2M3, FP8Q_MX_E3M2>(w_fmt, [&](auto FW) {
-            if (p.tile_m == 32) hipLaunchKernelGGL((k_mxgmm<FX(), FW(), 32, 1, 4>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((k_mxgmm<FX(), FW(), 128, 2, 2>), grid, block, 0, st, a);
-        });
+    mm_dispatch_mx_pair(x_fmt, w_fmt, [&](auto FX, auto FW) {
+        if (p.tile_m == 32) hipLaunchKernelGGL((k_mxgmm<FX(), FW(), 32, 1, 4>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((k_mxgmm<FX(), FW(), 128, 2, 2>), grid, block, 0, st, a);
     });
     return launch_rc();
 }

@@ -44,15 +44,9 @@ struct SkPlan {
     int64_t S, T, tw, ws_bytes;
 };
 
-struct SkArgs {
-    const uint8_t *xc, *xs, *wc, *ws;   // codes and scales of X (rows m) and W (rows n)
-    void *y;                            // [M, N] of y_type (S == 1) or float32 [S, M, N] (the workspace)
-    int64_t M, N, kblocks;              // kblocks = K / 32
-    int64_t xpitch, wpitch;             // bytes of a codes row
-    int nsteps, T, tw;                  // ceil(K / 128); steps per split; steps per wave
-    int xw, ww;                         // bytes per global load of either operand's codes: 16, 8, 4 or 1
-    int y_type;                         // FP8Q_DT_* of what this launch stores
-    int vec_store;                      // N % 4 == 0 and y aligned to four of its elements
+struct SkArgs : MxOperands {            // y: [M, N] of y_type (S == 1) or float32 [S, M, N] (the workspace)
+    int64_t M;
+    int T, tw;                          // steps per split; steps per wave
 };
 
 // the lane's fragment of step ks of the codes row at `row`: the runs the header lists, zero where the row (ok) or the run's
@@ -224,37 +218,28 @@ int sk_launch(const uint8_t *xc, const uint8_t *xs, const uint8_t *wc, const uin
     if (!mm_fmt_known(x_fmt) || !mm_fmt_known(w_fmt)) return FP8Q_EUNSUPPORTED;
     SkPlan p;
     if (const int rc = sk_plan(M, N, K, splits_req, p)) return rc;
-    if (y_type != FP8Q_DT_F32 && !half_type(y_type)) return FP8Q_EINVAL;
+    const int ybytes = mm_y_bytes(y_type);
+    if (!ybytes) return FP8Q_EINVAL;
     if (M == 0 || N == 0) return FP8Q_OK;
     if (!xc || !xs || !wc || !ws || !y) return FP8Q_EINVAL;
-    const int ybytes = y_type == FP8Q_DT_F32 ? 4 : 2;
     if ((uintptr_t)y % (uintptr_t)ybytes) return FP8Q_EINVAL;
     if (p.S > 1 && (!workspace || workspace_bytes < p.ws_bytes || (uintptr_t)workspace % 16)) return FP8Q_EINVAL;
-    const bool yvec = (uintptr_t)y % (uintptr_t)(4 * ybytes) == 0;
     SkArgs a;
-    a.xc = xc, a.xs = xs, a.wc = wc, a.ws = ws;
-    a.M = M, a.N = N, a.kblocks = K / 32;
-    a.xpitch = a.kblocks * mm_block_bytes(x_fmt);
-    a.wpitch = a.kblocks * mm_block_bytes(w_fmt);
-    a.nsteps = (int)cdiv(a.kblocks, 4), a.T = (int)p.T, a.tw = (int)p.tw;
-    // an FP6 fragment starts at a multiple of 24 bytes: 8-byte loads at the most
-    a.xw = std::min(mm_load_width(xc, a.xpitch), mm_block_bytes(x_fmt) == 24 ? 8 : 16);
-    a.ww = std::min(mm_load_width(wc, a.wpitch), mm_block_bytes(w_fmt) == 24 ? 8 : 16);
-    if (p.S == 1) a.y = y, a.y_type = y_type, a.vec_store = N % 4 == 0 && yvec;
+    mm_mx_operands(a, xc, xs, wc, ws, K, x_fmt, w_fmt, 8);     // an FP6 fragment starts at a multiple of 24 bytes
+    a.M = M, a.N = N, a.T = (int)p.T, a.tw = (int)p.tw;
+    if (p.S == 1) a.y = y, a.y_type = y_type, a.vec_store = mm_vec_store(N, y, ybytes);
     else a.y = workspace, a.y_type = FP8Q_DT_F32, a.vec_store = N % 4 == 0;
     const dim3 grid((unsigned)cdiv(N, kSkRows), (unsigned)p.S), block(kMmBlock);
-    dispatch<FP8Q_MX_E4M3FN, FP8Q_MX_E5M2, FP8Q_MX_E2M1, FP8Q_MX_E2M3, FP8Q_MX_E3M2>(x_fmt, [&](auto FX) {
-        dispatch<FP8Q_MX_E4M3FN, FP8Q_MX_E5M2, FP8Q_MX_E2M1, FP8Q_MX_E2M3, FP8Q_MX_E3M2>(w_fmt, [&](auto FW) {
-            dispatch<1, 2, 4>(M <= 16 ? 1 : (M <= 32 ? 2 : 4), [&](auto MG) {
-                hipLaunchKernelGGL((k_mxsk<FX(), FW(), MG()>), grid, block, 0, st, a);
-            });
+    mm_dispatch_mx_pair(x_fmt, w_fmt, [&](auto FX, auto FW) {
+        dispatch<1, 2, 4>(M <= 16 ? 1 : (M <= 32 ? 2 : 4), [&](auto MG) {
+            hipLaunchKernelGGL((k_mxsk<FX(), FW(), MG()>), grid, block, 0, st, a);
         });
     });
     if (const int rc = launch_rc()) return rc;
     if (p.S == 1) return FP8Q_OK;
     const int64_t total = M * N;
     hipLaunchKernelGGL(k_mxsk_reduce, dim3((unsigned)cdiv(cdiv(total, 4), kMmBlock)), block, 0, st,
-                       static_cast<const float *>(workspace), y, total, (int)p.S, y_type, (int)(total % 4 == 0 && yvec));
+                       static_cast<const float *>(workspace), y, total, (int)p.S, y_type, mm_vec_store(total, y, ybytes));
     return launch_rc();
 }
 

@@ -57,21 +57,6 @@ struct ObArgs {
     int vec_store;              // N % 4 == 0 and y aligned to four of its elements
 };
 
-// step ks of the panel rows [row0, row0 + 128): lane tid takes the chunks tid, tid + 256, ...  Chunk (r, c) is the bytes
-// [o, o + 16) of row row0 + r, o = 128 ks + 16 c, of which the first clamp(K - o, 0, 16) exist.  w divides K and o, so that
-// count is a multiple of w, and every byte read lies in [row * K, row * K + K) of a buffer of rows * K bytes.
-__device__ __forceinline__ void ob_load_panel(u4v (&g)[ObPanel::kPerLane], const uint8_t *codes, int64_t K, int64_t rows,
-                                              int64_t row0, int ks, int w, int tid)
-{
-#pragma unroll
-    for (int j = 0; j < ObPanel::kPerLane; ++j) {
-        const int q = tid + j * kMmBlock, r = q / ObPanel::kChunks, c = q % ObPanel::kChunks;
-        const int64_t row = row0 + r, o = (int64_t)ks * ObPanel::kStepBytes + 16 * c, left = K - o;
-        const int nvalid = row < rows ? (left >= 16 ? 16 : (left > 0 ? (int)left : 0)) : 0;
-        g[j] = mm_load_chunk(codes + row * K + o, nvalid, w);
-    }
-}
-
 // What a lane fetches of step ks's scales, one step ahead.  TILED: the one scale of the workgroup's 128x128 tile (row0 / 128 is
 // its scale row; row0 < rows, so it exists).  Otherwise the scale of row row0 + slot, lanes 0-127 (slot = tid) for X and
 // 128-255 (slot = tid - 128) for W, 0.0f past the operand's rows; the other lanes fetch nothing.
@@ -104,8 +89,8 @@ k_ocpbmm(const ObArgs a)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
 
-    ob_load_panel(gx, a.xc, a.K, a.M, m0, 0, a.xw, tid);
-    ob_load_panel(gw, a.wc, a.K, a.N, n0, 0, a.ww, tid);
+    mm_load_panel<ObPanel, true>(gx, a.xc, a.K, a.M, m0, 0, a.xw, tid);
+    mm_load_panel<ObPanel, true>(gw, a.wc, a.K, a.N, n0, 0, a.ww, tid);
     float ux = ob_fetch_scale<XT>(a.xs, a.M, m0, xslot, a.nsteps, 0);      // TILED: the step's scale; else in flight to LDS
     float uw = ob_fetch_scale<WT>(a.ws, a.N, n0, wslot, a.nsteps, 0);
     mm_store_panel<ObPanel>(s_x[0], gx, tid);
@@ -119,8 +104,8 @@ k_ocpbmm(const ObArgs a)
         const bool more = ks + 1 < a.nsteps;
         float ux_next = 0.0f, uw_next = 0.0f;
         if (more) {         // the next step's loads fly over this step's instructions
-            ob_load_panel(gx, a.xc, a.K, a.M, m0, ks + 1, a.xw, tid);
-            ob_load_panel(gw, a.wc, a.K, a.N, n0, ks + 1, a.ww, tid);
+            mm_load_panel<ObPanel, true>(gx, a.xc, a.K, a.M, m0, ks + 1, a.xw, tid);
+            mm_load_panel<ObPanel, true>(gw, a.wc, a.K, a.N, n0, ks + 1, a.ww, tid);
             ux_next = ob_fetch_scale<XT>(a.xs, a.M, m0, xslot, a.nsteps, ks + 1);
             uw_next = ob_fetch_scale<WT>(a.ws, a.N, n0, wslot, a.nsteps, ks + 1);
         }
@@ -169,18 +154,7 @@ k_ocpbmm(const ObArgs a)
         __syncthreads();
     }
 
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t m = m0 + wm * 64 + 16 * j + lr;
-        if (m >= a.M) continue;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int64_t n = n0 + wn * 64 + 16 * i + 4 * lg;
-            if (n >= a.N) continue;
-            const int64_t left = a.N - n;
-            mm_store4(a.y, a.y_type, m * a.N + n, acc[i][j], left < 4 ? (int)left : 4, a.vec_store != 0);
-        }
-    }
+    mm_store_tile<4, 4>(acc, a.y, a.y_type, a.N, m0 + wm * 64 + lr, a.M, n0 + wn * 64 + 4 * lg, a.vec_store != 0);
 }
 
 // ---- host side ----
@@ -196,10 +170,10 @@ int ob_launch(const uint8_t *xc, const float *xs, const uint8_t *wc, const float
     const int xr = ob_tile_rows(x_tr, x_tk), wr = ob_tile_rows(w_tr, w_tk);
     if (!xr || !wr) return FP8Q_EUNSUPPORTED;
     if (K <= 0 || M < 0 || N < 0) return FP8Q_EINVAL;
-    if (y_type != FP8Q_DT_F32 && !half_type(y_type)) return FP8Q_EINVAL;
+    const int ybytes = mm_y_bytes(y_type);
+    if (!ybytes) return FP8Q_EINVAL;
     if (M == 0 || N == 0) return FP8Q_OK;
     if (!xc || !xs || !wc || !ws || !y) return FP8Q_EINVAL;
-    const int ybytes = y_type == FP8Q_DT_F32 ? 4 : 2;
     if ((uintptr_t)y % (uintptr_t)ybytes || (uintptr_t)xs % 4 || (uintptr_t)ws % 4) return FP8Q_EINVAL;
     const int64_t nsteps = cdiv(K, kMmTile), gm = cdiv(M, kMmTile), gn = cdiv(N, kMmTile);
     if (nsteps > (int64_t)INT32_MAX || gm > 65535 || gn > (int64_t)INT32_MAX || M > INT64_MAX / N || M > INT64_MAX / K ||
@@ -212,7 +186,7 @@ int ob_launch(const uint8_t *xc, const float *xs, const uint8_t *wc, const float
     a.xw = mm_load_width(xc, K);
     a.ww = mm_load_width(wc, K);
     a.y_type = y_type;
-    a.vec_store = N % 4 == 0 && (uintptr_t)y % (uintptr_t)(4 * ybytes) == 0;
+    a.vec_store = mm_vec_store(N, y, ybytes);
     const dim3 grid((unsigned)gn, (unsigned)gm), block(kMmBlock);
     dispatch<FP8Q_OCP_E4M3FN, FP8Q_OCP_E5M2>(x_fmt, [&](auto FX) {
         dispatch<FP8Q_OCP_E4M3FN, FP8Q_OCP_E5M2>(w_fmt, [&](auto FW) {

@@ -6,7 +6,7 @@ uniform INT quantization, the fp16 / bf16 lane, the FP quantizer's backward, the
 uniform INT quantization on fp16 / bf16, percentile selection, the storage codes of fp16 / bf16 tensors, the fused epilogue of the INT quantizers, the OCP E4M3FN / E5M2 lane, the block-scaled MX lane, the same lane with the blocks along dim 0, the OCP lane under a float32 scale per 1x128 / 128x1 / 128x128 tile, that lane's transposed operands, the MX lane under a block Hadamard rotation in both orientations, the product of two MX operands on the matrix cores, the product of two tile-scaled OCP operands there, the small-M split-K kernel of the MX product, the grouped MX product of a mixture-of-experts layer) compiled in parallel and
 linked into one library.  HEADERS are what they share; the code lanes' pieces are in fp8q_io.h (launch modes, element policies, the
 FP8 conversion layer, the one I/O dispatcher), fp8q_half.h (the dword vectors, the half lane's helpers) and fp8q_intq.h (the INT
-argument block, code packing); the MX units share their device arithmetic through fp8q_mxq.h (the dim-0 ones their tile through fp8q_mxtq.h, the rotating ones the butterflies through fp8q_hadq.h), the two OCP units theirs through fp8q_ocpq.h, the four product units their panels, chunk loads, stores and the MX format table through fp8q_mmq.h.  In-tree build: the .so is git-ignored but travels to the GPU box with the repo snapshot.
+argument block, code packing); the MX units share their device arithmetic through fp8q_mxq.h (the dim-0 ones their tile through fp8q_mxtq.h, the rotating ones the butterflies through fp8q_hadq.h), the two OCP units theirs through fp8q_ocpq.h, the four product units everything but their own loops through fp8q_mmq.h (panels, loaders, the tile store, the MX operand block, format table and host prologue, and the one MX tile body that the plain and the grouped MX product both run).  In-tree build: the .so is git-ignored but travels to the GPU box with the repo snapshot.
 """
 import concurrent.futures
 import os

@@ -2351,6 +2351,47 @@ def _mx_mm_operand(codes, fmt, name):
     return fmt, (kb * 4 // 3 if fmt in _MX_FP6 else kb * (2 if fmt == torch.float4_e2m1fn_x2 else 1))
 
 
+def _mx_mm_operands(a_codes, a_fmt, b_codes, b_fmt, dims, dims_msg):
+    """(a_fmt, b_fmt, K) of an MX product's operands: each told by _mx_mm_operand, then their .dim() against `dims` (None: any;
+    dims_msg() is the refusal), then K: equal for both and a positive multiple of 32.  Raised before the device check."""
+    a_fmt, K = _mx_mm_operand(a_codes, a_fmt, "a")
+    b_fmt, Kb = _mx_mm_operand(b_codes, b_fmt, "b")
+    if any(d is not None and t.dim() != d for t, d in zip((a_codes, b_codes), dims)):
+        raise Fp8qError(dims_msg())
+    if K != Kb:
+        raise Fp8qError(f"the operands disagree on K: a has {K} elements along its last dimension, b has {Kb}")
+    if K == 0 or K % MX_BLOCK:
+        raise Fp8qError(f"K must be a positive multiple of {MX_BLOCK} (short last blocks are out of scope), got {K}")
+    return a_fmt, b_fmt, K
+
+
+def _mm_shapes(*named):
+    """(name, tensor, shape), ...: what the codes' shape asks of the tensors beside them"""
+    for name, s, shape in named:
+        if isinstance(s, torch.Tensor) and tuple(s.shape) != shape:
+            raise Fp8qError(f"{name} are {tuple(s.shape)}, the codes have {shape}")
+
+
+def _mm_out(out, shape, dt, like):
+    """A product's result: a new tensor of `shape`, or `out` if it has the dtype, the device, the element count and is contiguous"""
+    if out is None:
+        return torch.empty(shape, dtype=dt, device=like.device)
+    n = torch.Size(shape).numel()
+    _require(out, "out", dt, like)
+    if out.numel() != n or not out.is_contiguous():
+        raise Fp8qError(f"out must be a contiguous tensor of {n} elements (got {tuple(out.shape)}, "
+                        f"contiguous={out.is_contiguous()})")
+    return out
+
+
+def _mm_workspace(ws, nbytes, plan, like):
+    """refuse a caller's workspace that the plan's `nbytes` (`plan`: the function that states them) cannot use"""
+    _require(ws, "workspace", torch.uint8, like)
+    if not ws.is_contiguous() or ws.numel() < nbytes or (nbytes and ws.data_ptr() % 16):
+        raise Fp8qError(f"workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {nbytes} bytes "
+                        f"({plan}), got {ws.numel()}")
+
+
 def mx_skinny_plan(M, N, K, splits=None):
     """(splits, steps_per_split, steps_per_wave, workspace_bytes) of mx_matmul(..., skinny=True) for a [M, K] x [N, K] product:
     fp8q_mxsk_plan, the one place that decides the split (include/fp8q.h states the rule).  A step is 128 elements of K.  It
@@ -2394,21 +2435,11 @@ def mx_matmul(a_codes, a_scales, b_codes, b_scales, a_fmt=None, b_fmt=None, out_
     if not skinny and (splits is not None or workspace is not None):
         raise Fp8qError("splits= and workspace= belong to skinny=True")
     dt = _decode_out_dtype(out, out_dtype)
-    a_fmt, K = _mx_mm_operand(a_codes, a_fmt, "a")
-    b_fmt, Kb = _mx_mm_operand(b_codes, b_fmt, "b")
-    if b_codes.dim() != 2:
-        raise Fp8qError(f"b_codes must be 2-D [N, K'], got {tuple(b_codes.shape)}")
-    if K != Kb:
-        raise Fp8qError(f"the operands disagree on K: a has {K} elements along its last dimension, b has {Kb}")
-    if K == 0 or K % MX_BLOCK:
-        raise Fp8qError(f"K must be a positive multiple of {MX_BLOCK} (short last blocks are out of scope), got {K}")
+    a_fmt, b_fmt, K = _mx_mm_operands(a_codes, a_fmt, b_codes, b_fmt, (None, 2),
+                                      lambda: f"b_codes must be 2-D [N, K'], got {tuple(b_codes.shape)}")
     lead, N = tuple(a_codes.shape[:-1]), int(b_codes.shape[0])
-    for name, s, shape in (("a_scales", a_scales, lead + (K // MX_BLOCK,)), ("b_scales", b_scales, (N, K // MX_BLOCK))):
-        if isinstance(s, torch.Tensor) and tuple(s.shape) != shape:
-            raise Fp8qError(f"{name} are {tuple(s.shape)}, the codes have {shape}")
-    M = 1
-    for d in lead:
-        M *= int(d)
+    _mm_shapes(("a_scales", a_scales, lead + (K // MX_BLOCK,)), ("b_scales", b_scales, (N, K // MX_BLOCK)))
+    M = torch.Size(lead).numel()
     plan = mx_skinny_plan(M, N, K, splits) if skinny else None      # refuses M > 64 and a bad splits= before the device check
     _require(a_codes, "a_codes", (torch.uint8, _mx_code_dtype(a_fmt)))
     _require(b_codes, "b_codes", (torch.uint8, _mx_code_dtype(b_fmt)), a_codes)
@@ -2416,23 +2447,13 @@ def mx_matmul(a_codes, a_scales, b_codes, b_scales, a_fmt=None, b_fmt=None, out_
     _require(b_scales, "b_scales", (MX_SCALE_DTYPE, torch.uint8), a_codes)
     a, b = a_codes.contiguous().view(torch.uint8), b_codes.contiguous().view(torch.uint8)
     sa, sb = a_scales.contiguous().view(torch.uint8), b_scales.contiguous().view(torch.uint8)
-    if out is None:
-        y = torch.empty(lead + (N,), dtype=dt, device=a.device)
-    else:
-        _require(out, "out", dt, a)
-        if out.numel() != M * N or not out.is_contiguous():
-            raise Fp8qError(f"out must be a contiguous tensor of {M * N} elements (got {tuple(out.shape)}, "
-                            f"contiguous={out.is_contiguous()})")
-        y = out
+    y = _mm_out(out, lead + (N,), dt, a)
     if M * N == 0:
         return y
     if skinny:
         ws = workspace
         if ws is not None:
-            _require(ws, "workspace", torch.uint8, a)
-            if not ws.is_contiguous() or ws.numel() < plan[3] or (plan[3] and ws.data_ptr() % 16):
-                raise Fp8qError(f"workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {plan[3]} bytes "
-                                f"(mx_skinny_plan), got {ws.numel()}")
+            _mm_workspace(ws, plan[3], "mx_skinny_plan", a)
         elif plan[3]:
             ws = torch.empty(plan[3], dtype=torch.uint8, device=a.device)
         _run("fp8q_mxsk_nt", a, a.data_ptr(), sa.data_ptr(), b.data_ptr(), sb.data_ptr(), y.data_ptr(), M, N, K, _mx_fmt(a_fmt),
@@ -2480,20 +2501,12 @@ def mx_grouped_matmul(a_codes, a_scales, b_codes, b_scales, offsets, a_fmt=None,
     for the tile table: a uint8 tensor is allocated per call unless the caller passes its own (`workspace`, 16-byte aligned).
     An empty T, N or G launches nothing.  No autograd."""
     dt = _decode_out_dtype(out, out_dtype)
-    a_fmt, K = _mx_mm_operand(a_codes, a_fmt, "a")
-    b_fmt, Kb = _mx_mm_operand(b_codes, b_fmt, "b")
-    if a_codes.dim() != 2 or b_codes.dim() != 3:
-        raise Fp8qError(f"a_codes must be 2-D [T, K'] and b_codes 3-D [G, N, K'], got {tuple(a_codes.shape)} and "
-                        f"{tuple(b_codes.shape)}")
-    if K != Kb:
-        raise Fp8qError(f"the operands disagree on K: a has {K} elements along its last dimension, b has {Kb}")
-    if K == 0 or K % MX_BLOCK:
-        raise Fp8qError(f"K must be a positive multiple of {MX_BLOCK} (short last blocks are out of scope), got {K}")
+    a_fmt, b_fmt, K = _mx_mm_operands(a_codes, a_fmt, b_codes, b_fmt, (2, 3),
+                                      lambda: f"a_codes must be 2-D [T, K'] and b_codes 3-D [G, N, K'], got "
+                                              f"{tuple(a_codes.shape)} and {tuple(b_codes.shape)}")
     T, (G, N) = int(a_codes.shape[0]), (int(d) for d in b_codes.shape[:2])
-    for name, s, shape in (("a_scales", a_scales, (T, K // MX_BLOCK)), ("b_scales", b_scales, (G, N, K // MX_BLOCK)),
-                           ("offsets", offsets, (G + 1,))):
-        if isinstance(s, torch.Tensor) and tuple(s.shape) != shape:
-            raise Fp8qError(f"{name} are {tuple(s.shape)}, the codes have {shape}")
+    _mm_shapes(("a_scales", a_scales, (T, K // MX_BLOCK)), ("b_scales", b_scales, (G, N, K // MX_BLOCK)),
+               ("offsets", offsets, (G + 1,)))
     plan = mx_grouped_plan(T, N, K, G, tile_m)      # refuses a bad tile_m=, G > 4096 and a table too long for one grid
     _require(a_codes, "a_codes", (torch.uint8, _mx_code_dtype(a_fmt)))
     _require(b_codes, "b_codes", (torch.uint8, _mx_code_dtype(b_fmt)), a_codes)
@@ -2503,20 +2516,10 @@ def mx_grouped_matmul(a_codes, a_scales, b_codes, b_scales, offsets, a_fmt=None,
     a, b = a_codes.contiguous().view(torch.uint8), b_codes.contiguous().view(torch.uint8)
     sa, sb = a_scales.contiguous().view(torch.uint8), b_scales.contiguous().view(torch.uint8)
     off = offsets.contiguous()
-    if out is None:
-        y = torch.empty((T, N), dtype=dt, device=a.device)
-    else:
-        _require(out, "out", dt, a)
-        if out.numel() != T * N or not out.is_contiguous():
-            raise Fp8qError(f"out must be a contiguous tensor of {T * N} elements (got {tuple(out.shape)}, "
-                            f"contiguous={out.is_contiguous()})")
-        y = out
+    y = _mm_out(out, (T, N), dt, a)
     ws = workspace
     if ws is not None:
-        _require(ws, "workspace", torch.uint8, a)
-        if not ws.is_contiguous() or ws.numel() < plan[2] or (plan[2] and ws.data_ptr() % 16):
-            raise Fp8qError(f"workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {plan[2]} bytes "
-                            f"(mx_grouped_plan), got {ws.numel()}")
+        _mm_workspace(ws, plan[2], "mx_grouped_plan", a)
     if T * N * G == 0:
         return y
     if ws is None:
@@ -2592,14 +2595,7 @@ def ocp_block_matmul(a_codes, a_scales, b_codes, b_scales, a_tile=(1, 128), b_ti
     sa, sb = a_scales.detach().contiguous(), b_scales.detach().contiguous()
     lead, N = tuple(a.shape[:-1]), int(b.shape[0])
     M = a.numel() // K
-    if out is None:
-        y = torch.empty(lead + (N,), dtype=dt, device=a.device)
-    else:
-        _require(out, "out", dt, a)
-        if out.numel() != M * N or not out.is_contiguous():
-            raise Fp8qError(f"out must be a contiguous tensor of {M * N} elements (got {tuple(out.shape)}, "
-                            f"contiguous={out.is_contiguous()})")
-        y = out
+    y = _mm_out(out, lead + (N,), dt, a)
     if M * N == 0:
         return y
     _run("fp8q_ocpbmm_nt", a, a.data_ptr(), sa.data_ptr(), b.data_ptr(), sb.data_ptr(), y.data_ptr(), M, N, K, *a_tile, *b_tile,
