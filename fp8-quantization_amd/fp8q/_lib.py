@@ -253,7 +253,10 @@ SIGNATURES = {
     "fp8q_mxgmm_plan": (_i, [_i64, _i64, _i64, _i64, _i64, _vp]),
     "fp8q_mxgmm_nt": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i64, _vp, _i64, _vp]),
     "fp8q_ocpbmm_nt": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "fp8q_ocpsr_encode_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _f, _vp, _u64, _u64, _vp]),
+    # the product of two operands of INT codes: per operand (codes, delta, zero_float, signed_flag, n_delta, n_bits, symmetric),
+    # then (y, M, N, K, eps, y_type, stream)
+    "fp8q_i8mm_nt": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i] * 2 + [_vp, _i64, _i64, _i64, _f, _i, _vp]),
+    "fp8q_ocpsr_encode_f32":(_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _f, _vp, _u64, _u64, _vp]),
     "fp8q_ocpsr_encode_h16": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _i64, _i, _f, _vp, _u64, _u64, _vp]),
     "fp8q_ocpsr_quantize_f32": (_i, [_vp, _vp, _i64, _i64, _vp, _i64, _i, _f, _u64, _u64, _vp]),
     "fp8q_ocpsr_quantize_h16": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _i64, _i, _f, _u64, _u64, _vp]),

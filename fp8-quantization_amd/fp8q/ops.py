@@ -2603,6 +2603,68 @@ def ocp_block_matmul(a_codes, a_scales, b_codes, b_scales, a_tile=(1, 128), b_ti
     return y
 
 
+# ---- the product of two operands of the INT lane's one-byte codes on the matrix cores (csrc/fp8q_int_mm.hip) ----
+INT_MM_MAX_K = 32768        # 255^2 K < 2^31 up to here: the integer part fits int32
+
+
+def _int_mm_operand(codes, delta, n_bits, name):
+    """(delta flattened, its count, K) of one operand of int_matmul, told from dtypes and shapes alone: raised before the
+    device check"""
+    if not isinstance(codes, torch.Tensor) or not isinstance(delta, torch.Tensor):
+        raise Fp8qError(f"{name}_codes and {name}_delta must be CUDA(HIP) tensors: the FP8 engine has no CPU path")
+    if codes.dtype != torch.uint8:
+        raise Fp8qError(f"{name}_codes must be uint8, int_encode's one-byte codes, got {codes.dtype}")
+    if isinstance(n_bits, bool) or not isinstance(n_bits, int) or not 2 <= n_bits <= 8:
+        raise Fp8qError(f"{name}_n_bits must be an int in 2..8 (two-byte codes are out of scope), got {n_bits!r}")
+    if codes.dim() < 1 or (name == "b" and codes.dim() != 2):
+        raise Fp8qError(f"{name}_codes must be {'2-D [N, K]' if name == 'b' else '[..., K]'}, got {tuple(codes.shape)}")
+    delta = delta.detach().reshape(-1)
+    n = delta.numel()
+    if n != 1 and codes.dim() != 2:
+        raise Fp8qError(f"a per-channel {name}_delta ({n} elements) needs 2-D {name}_codes, got {tuple(codes.shape)}")
+    _mm_shapes((f"{name}_delta", delta, (1,) if n == 1 else (int(codes.shape[0]),)))
+    return delta, n, int(codes.shape[-1])
+
+
+def int_matmul(a_codes, a_delta, b_codes, b_delta, *, a_zero_float=None, a_signed_flag=None, a_symmetric=False, a_n_bits=8,
+               b_zero_float=None, b_signed_flag=None, b_symmetric=False, b_n_bits=8, eps=1e-8, out_dtype=torch.float32,
+               out=None):
+    """y[M, N] = A[M, K] . B[N, K]^T of two operands of int_encode's one-byte codes (n_bits <= 8) on gfx950's matrix cores
+    (csrc/fp8q_int_mm.hip, the entry fp8q_i8mm_nt; include/fp8q.h states the contract), defined bit for bit:
+        T[m, n] = sum_k (qa[m, k] - za[m]) * (qb[n, k] - zb[n])        an exact integer (v_mfma_i32_16x16x64_i8)
+        y[m, n] = float32(T) * (sa[m] * sb[n])                         one conversion, two float32 multiplications
+    with scale = max(delta, eps) and zp = clamp(rint(zero_float), 0, 2^n_bits - 1) (asymmetric) or 0 (symmetric), as int_decode
+    has them.  Each operand takes int_decode's four quantizer arguments under its prefix and is independently asymmetric
+    (delta, zero_float) or symmetric (delta and the quantizer's 1-byte device sign, read by the kernel: two's-complement codes
+    when set, unsigned otherwise), per tensor (1 element) or per channel (one per row: a_codes [M, K], b_codes [N, K]).
+    a_codes [..., K] uint8 (per tensor: leading dimensions are flattened to M), b_codes [N, K] uint8.  K is 1..32768 (beyond,
+    T does not fit int32); M, N >= 1 are arbitrary, and an empty M or N gives an empty result with no launch.  The result is
+    float32, or float16 / bfloat16 where `out` / out_dtype ask (the float32 rounded once).  One launch, no workspace, no host
+    synchronisation; no autograd, no split-K or small-M kernel."""
+    dt = _decode_out_dtype(out, out_dtype)
+    a_delta, na, K = _int_mm_operand(a_codes, a_delta, a_n_bits, "a")
+    b_delta, nb, Kb = _int_mm_operand(b_codes, b_delta, b_n_bits, "b")
+    if K != Kb:
+        raise Fp8qError(f"the operands disagree on K: a has {K} elements along its last dimension, b has {Kb}")
+    if not 1 <= K <= INT_MM_MAX_K:
+        raise Fp8qError(f"K must be in 1..{INT_MM_MAX_K} (beyond, the integer part does not fit int32), got {K}")
+    _require(a_codes, "a_codes", torch.uint8)
+    _require(b_codes, "b_codes", torch.uint8, a_codes)
+    a_zero_float, a_signed_flag, b_zero_float, b_signed_flag = (
+        t.detach().reshape(-1) if t is not None else None for t in (a_zero_float, a_signed_flag, b_zero_float, b_signed_flag))
+    pa = _int_ptrs(a_codes, a_delta, a_zero_float, a_signed_flag, a_symmetric, na)
+    pb = _int_ptrs(a_codes, b_delta, b_zero_float, b_signed_flag, b_symmetric, nb)
+    a, b = a_codes.contiguous(), b_codes.contiguous()
+    lead, N = tuple(a.shape[:-1]), int(b.shape[0])
+    M = a.numel() // K
+    y = _mm_out(out, lead + (N,), dt, a)
+    if M * N == 0:
+        return y
+    _run("fp8q_i8mm_nt", a, a.data_ptr(), *pa, na, a_n_bits, int(bool(a_symmetric)), b.data_ptr(), *pb, nb, b_n_bits,
+         int(bool(b_symmetric)), y.data_ptr(), M, N, K, float(eps), _DT[dt])
+    return y
+
+
 def _nchw(x):
     """[N, C, *spatial] -> (N, C, HW)."""
     if x.dim() < 2:

@@ -1553,6 +1553,41 @@ int fp8q_ocpbmm_nt(const uint8_t *a_codes, const float *a_scales, const uint8_t 
                    int64_t M, int64_t N, int64_t K, int a_tile_r, int a_tile_k, int b_tile_r, int b_tile_k, int a_fmt, int b_fmt,
                    int y_type, fp8q_stream_t stream);
 
+/* ---- the product of two operands of the uniform (INT) lane's one-byte codes on the matrix cores -------------------------------
+ * (csrc/fp8q_int_mm.hip)  y[M, N] = A[M, K] . B[N, K]^T from what fp8q_int_encode writes for n_bits <= 8: codes [rows, K]
+ * bytes, K contiguous.  Each operand independently is asymmetric or symmetric, with n_delta 1 (per tensor) or its rows (per
+ * channel, dim 0: [M] for A, [N] for B), n_bits in 2..8, one eps for both, all as fp8q_int_decode takes them:
+ *   asymmetric   unsigned codes, delta, zero_float [n_delta]; signed_flag unused (may be NULL)
+ *   symmetric    delta [n_delta] and the device byte signed_flag[0]: two's-complement codes when it is non-zero, unsigned codes
+ *                with zp = 0 otherwise; zero_float unused (may be NULL)
+ * The kernel reads signed_flag, delta and zero_float; the host never does.  With the lane's own definitions ("Uniform (INT)
+ * fake-quantization" above)  scale = max(delta, eps),  zp = clamp(rint(zero_float), 0, 2^n_bits - 1) (asymmetric) or 0:
+ * Contract.
+ *   T[m, n] = sum over k of (qa[m, k] - za[m]) * (qb[n, k] - zb[n])          an exact integer, |T| <= 255^2 K < 2^31
+ *   y[m, n] = fl32(fl32(T) * fl32(sa[m] * sb[n]))
+ * three roundings: int32 to float32 to nearest even, one float32 product of the two scales, one float32 product.  y_type
+ * FP8Q_DT_F16 / FP8Q_DT_BF16 rounds that float32 once more, to nearest even.  The result is defined bit for bit; the integer
+ * part is formed by v_mfma_i32_16x16x64_i8 on q ^ 0x80 for unsigned codes, the zero points and the flip taken out from row
+ * sums gathered in the same pass (the unit's header has the algebra).  Every byte of a code counts, whatever n_bits: n_bits
+ * only places the clamp of an asymmetric zero point.  fp8q_int_decode gives scale * (code - zp) per element, so for operands
+ * whose every product and partial sum is exact in float32 y equals the float32 product of the two decoded tensors.
+ * A NaN delta gives a NaN scale (max(delta, eps) keeps a NaN delta, as torch's does) and a NaN row or column of y, an
+ * infinite delta an infinite or (where T is 0) NaN one; a NaN zero_float passes the clamp and its conversion to an integer
+ * is whatever the hardware gives, +-inf clamps to an end of the grid.  Recorded here, not promised.
+ * K in 1..32768 is arbitrary (codes beyond K do not count; nothing past a row's end is read); K > 32768, where T no longer
+ * fits int32, is FP8Q_EUNSUPPORTED.  M, N >= 1 are arbitrary; M == 0 or N == 0 is a no-op that returns FP8Q_OK.  Codes may
+ * start at any byte (loads narrow from 16 bytes to 8, 4 or 1 as the pointer and K require); delta and zero_float must be
+ * 4-byte aligned, y aligned to its element.  Errors, all reported before the launch: FP8Q_EUNSUPPORTED for an n_bits outside
+ * 2..8 (two-byte codes are out of scope) and K > 32768; FP8Q_EINVAL for K <= 0, negative M or N, an unknown y_type, null
+ * pointers, an n_delta that is neither 1 nor the operand's rows, a misaligned delta, zero_float or y, a grid beyond 65535
+ * rows of tiles.  One launch, enqueue-only, no workspace, no host synchronisation.  Split-K, a small-M kernel, a grouped
+ * form, packed 4-bit storage and re-quantizing the result are out of scope.
+ * Names: fp8q_i8mm_*; the set of fp8q_int_* entries is unchanged.  FP8Q_VERSION is unchanged: the entry is additive. */
+int fp8q_i8mm_nt(const uint8_t *a_codes, const float *a_delta, const float *a_zero_float, const unsigned char *a_signed_flag,
+                 int64_t a_n_delta, int a_n_bits, int a_symmetric, const uint8_t *b_codes, const float *b_delta,
+                 const float *b_zero_float, const unsigned char *b_signed_flag, int64_t b_n_delta, int b_n_bits, int b_symmetric,
+                 void *y, int64_t M, int64_t N, int64_t K, float eps, int y_type, fp8q_stream_t stream);
+
 /* ---- hardware FP8 with seeded stochastic rounding: per tensor / channel, per tile, and the transposed operands ----------------
  * (csrc/fp8q_ocpq.h, used by csrc/fp8q_ocp.hip, csrc/fp8q_ocp_block.hip and csrc/fp8q_ocp_block_t.hip)  The operands these lanes
  * make for the backward products are gradients, and the reason the block above gives for the MX lane holds for them.  These
