@@ -259,8 +259,8 @@ int fp8q_i8mm_nt(const uint8_t *a_codes, const float *a_delta, const float *a_ze
     if (int rc = i8_side(a.x, a_codes, a_delta, a_zero_float, a_signed_flag, a_n_delta, a_n_bits, a_symmetric, M, K)) return rc;
     if (int rc = i8_side(a.w, b_codes, b_delta, b_zero_float, b_signed_flag, b_n_delta, b_n_bits, b_symmetric, N, K)) return rc;
     if (!y || (uintptr_t)y % (uintptr_t)ybytes) return FP8Q_EINVAL;
-    const int64_t gm = cdiv(M, kMmTile), gn = cdiv(N, kMmTile);
-    if (gm > 65535 || gn > (int64_t)INT32_MAX || M > INT64_MAX / N) return FP8Q_EINVAL;
+    int64_t gm, gn;
+    if (!mm_tile_grid(M, N, gm, gn)) return FP8Q_EINVAL;
     a.y = y;
     a.K = K;
     a.nsteps = (int)cdiv(K, kMmTile);

@@ -1,15 +1,22 @@
-// fp8q_mmq.h -- what the four matrix-core products share.  fp8q_mx_mm.hip's header has the instruction's operand and result
+// fp8q_mmq.h -- what the five matrix-core products share.  fp8q_mx_mm.hip's header has the instruction's operand and result
 // layouts and the LDS bank arithmetic.  Internal linkage, as fp8q_common.h.
 //   The tile: 128 rows of either operand under 256 lanes, MmPanel (one K step of an operand in LDS), mm_load_chunk (a 16-byte
 //     chunk by loads that narrow with the operand's alignment), mm_load_panel / mm_store_panel, mm_read_frag (what a lane hands
-//     to v_mfma_*_16x16x128_f8f6f4), mm_store4 and mm_store_tile (the masked stores of a wave's results).
-//     Users: k_mxmm, k_mxgmm, k_ocpbmm; k_mxsk takes mm_load_chunk and mm_store4 alone, k_mxsk_reduce mm_store4.
+//     to the matrix instruction), mm_store4 and mm_store_tile (the masked stores of a wave's results).
+//     Users: k_mxmm, k_mxgmm, k_ocpbmm, k_i8mm (which walks its tile itself, around its per-element correction); k_mxsk takes
+//     mm_load_chunk and mm_store4 alone, k_mxsk_reduce mm_store4.
 //   The MX products (fp8q_mx_mm.hip, its small-M kernel fp8q_mx_mm_skinny.hip, its grouped form fp8q_mx_mm_grouped.hip): the
 //     format table MmFmt, the operand block MxOperands that their kernels' arguments start with, mm_load_scales, and
 //     mm_mx_tile, the one tile body -- prologue, step loop, store -- that k_mxmm and k_mxgmm are.  k_mxsk has its own loop.
-//   Host side: mm_y_bytes and mm_vec_store (all four launchers), mm_load_width (the one rule for the load width), and for
-//     the MX launchers mm_fmt_known, mm_block_bytes, mm_mx_operands (fills the block) and mm_dispatch_mx_pair.
-// fp8q_ocp_block_mm.hip (hardware FP8 under float32 tile scales) keeps its own step loop and scales.
+//   Host side: mm_y_bytes and mm_vec_store (all five launchers), mm_load_width (the one rule for the load width),
+//     mm_tile_grid (the grid of 128 x 128 tiles and what it refuses), and for the MX launchers mm_fmt_known, mm_block_bytes,
+//     mm_mx_operands (fills the block) and mm_dispatch_mx_pair.
+// The double-buffered K-step loop stands three times: in mm_mx_tile, in k_ocpbmm (fp8q_ocp_block_mm.hip, with its float32
+// scales) and in k_i8mm (fp8q_int_mm.hip).  One skeleton with a policy per product gave the same bits and was measured:
+// the grouped product's 32-row kernels ran 5 to 7 % slower and the OCP product 1 to 7 %, with equal registers, LDS and
+// occupancy -- the compiler lays the loop out anew at every touch (profiles/mm_pipeline_ab.txt; k_i8mm's store through
+// mm_store_tile with an element map cost it about 1.5 % in the same way).  Whoever changes the loop changes it three times
+// until that is solved.
 #pragma once
 #include "fp8q_half.h"
 
@@ -310,6 +317,14 @@ inline int mm_y_bytes(int y_type) { return y_type == FP8Q_DT_F32 ? 4 : (half_typ
 
 // one store of a lane's four results: N % 4 == 0 and y aligned to four of its elements
 inline int mm_vec_store(int64_t N, const void *y, int ybytes) { return N % 4 == 0 && (uintptr_t)y % (uintptr_t)(4 * ybytes) == 0; }
+
+// the grid of 128 x 128 tiles over y[M, N] (M, N >= 1), gn x gm with N fastest; false where grid.y, grid.x or an element index
+// of y in int64 cannot hold it
+inline bool mm_tile_grid(int64_t M, int64_t N, int64_t &gm, int64_t &gn)
+{
+    gm = cdiv(M, kMmTile), gn = cdiv(N, kMmTile);
+    return gm <= 65535 && gn <= (int64_t)INT32_MAX && M <= INT64_MAX / N;
+}
 
 // the operands' part of an MX launch (K % 32 == 0 and K / 32 <= INT32_MAX checked by the caller); y, N, y_type and vec_store
 // are the launcher's.  w6: the widest load of an FP6 operand, 16 where chunks start 16-aligned (the panels), 8 where a lane's

@@ -69,8 +69,8 @@ int mm_launch(const uint8_t *xc, const uint8_t *xs, const uint8_t *wc, const uin
     if (M == 0 || N == 0) return FP8Q_OK;
     if (!xc || !xs || !wc || !ws || !y) return FP8Q_EINVAL;
     if ((uintptr_t)y % (uintptr_t)ybytes) return FP8Q_EINVAL;
-    const int64_t gm = cdiv(M, kMmTile), gn = cdiv(N, kMmTile);
-    if (K / 32 > (int64_t)INT32_MAX || gm > 65535 || gn > (int64_t)INT32_MAX || M > INT64_MAX / N) return FP8Q_EINVAL;
+    int64_t gm, gn;
+    if (K / 32 > (int64_t)INT32_MAX || !mm_tile_grid(M, N, gm, gn)) return FP8Q_EINVAL;
     MmArgs a;
     mm_mx_operands(a, xc, xs, wc, ws, K, x_fmt, w_fmt);
     a.y = y, a.M = M, a.N = N;

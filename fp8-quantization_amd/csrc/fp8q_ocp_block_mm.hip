@@ -175,10 +175,9 @@ int ob_launch(const uint8_t *xc, const float *xs, const uint8_t *wc, const float
     if (M == 0 || N == 0) return FP8Q_OK;
     if (!xc || !xs || !wc || !ws || !y) return FP8Q_EINVAL;
     if ((uintptr_t)y % (uintptr_t)ybytes || (uintptr_t)xs % 4 || (uintptr_t)ws % 4) return FP8Q_EINVAL;
-    const int64_t nsteps = cdiv(K, kMmTile), gm = cdiv(M, kMmTile), gn = cdiv(N, kMmTile);
-    if (nsteps > (int64_t)INT32_MAX || gm > 65535 || gn > (int64_t)INT32_MAX || M > INT64_MAX / N || M > INT64_MAX / K ||
-        N > INT64_MAX / K)
-        return FP8Q_EINVAL;
+    const int64_t nsteps = cdiv(K, kMmTile);
+    int64_t gm, gn;
+    if (nsteps > (int64_t)INT32_MAX || !mm_tile_grid(M, N, gm, gn) || M > INT64_MAX / K || N > INT64_MAX / K) return FP8Q_EINVAL;
     ObArgs a;
     a.xc = xc, a.wc = wc, a.xs = xs, a.ws = ws, a.y = y;
     a.M = M, a.N = N, a.K = K;

@@ -2358,11 +2358,16 @@ def _mx_mm_operands(a_codes, a_fmt, b_codes, b_fmt, dims, dims_msg):
     b_fmt, Kb = _mx_mm_operand(b_codes, b_fmt, "b")
     if any(d is not None and t.dim() != d for t, d in zip((a_codes, b_codes), dims)):
         raise Fp8qError(dims_msg())
-    if K != Kb:
-        raise Fp8qError(f"the operands disagree on K: a has {K} elements along its last dimension, b has {Kb}")
+    _mm_same_k(K, Kb)
     if K == 0 or K % MX_BLOCK:
         raise Fp8qError(f"K must be a positive multiple of {MX_BLOCK} (short last blocks are out of scope), got {K}")
     return a_fmt, b_fmt, K
+
+
+def _mm_same_k(K, Kb):
+    """a product's operands have one K"""
+    if K != Kb:
+        raise Fp8qError(f"the operands disagree on K: a has {K} elements along its last dimension, b has {Kb}")
 
 
 def _mm_shapes(*named):
@@ -2382,6 +2387,13 @@ def _mm_out(out, shape, dt, like):
         raise Fp8qError(f"out must be a contiguous tensor of {n} elements (got {tuple(out.shape)}, "
                         f"contiguous={out.is_contiguous()})")
     return out
+
+
+def _mm_result(a, b, out, dt):
+    """(M, N, y) of a [..., K'] x [N, K'] product: a's leading dimensions flattened to M, y [..., N] as _mm_out gives it.  With
+    M * N == 0 y is the whole result and nothing is launched."""
+    lead, N = tuple(a.shape[:-1]), int(b.shape[0])
+    return torch.Size(lead).numel(), N, _mm_out(out, lead + (N,), dt, a)
 
 
 def _mm_workspace(ws, nbytes, plan, like):
@@ -2447,7 +2459,7 @@ def mx_matmul(a_codes, a_scales, b_codes, b_scales, a_fmt=None, b_fmt=None, out_
     _require(b_scales, "b_scales", (MX_SCALE_DTYPE, torch.uint8), a_codes)
     a, b = a_codes.contiguous().view(torch.uint8), b_codes.contiguous().view(torch.uint8)
     sa, sb = a_scales.contiguous().view(torch.uint8), b_scales.contiguous().view(torch.uint8)
-    y = _mm_out(out, lead + (N,), dt, a)
+    M, N, y = _mm_result(a, b, out, dt)
     if M * N == 0:
         return y
     if skinny:
@@ -2583,8 +2595,7 @@ def ocp_block_matmul(a_codes, a_scales, b_codes, b_scales, a_tile=(1, 128), b_ti
     dt = _decode_out_dtype(out, out_dtype)
     fa, a_tile, K = _ocpb_mm_operand(a_codes, a_scales, a_tile, a_fmt, "a")
     fb, b_tile, Kb = _ocpb_mm_operand(b_codes, b_scales, b_tile, b_fmt, "b")
-    if K != Kb:
-        raise Fp8qError(f"the operands disagree on K: a has {K} elements along its last dimension, b has {Kb}")
+    _mm_same_k(K, Kb)
     if K == 0:
         raise Fp8qError("K must be at least 1")
     _require(a_codes, "a_codes", (torch.uint8,) + tuple(_OCP_FMT))
@@ -2593,9 +2604,7 @@ def ocp_block_matmul(a_codes, a_scales, b_codes, b_scales, a_tile=(1, 128), b_ti
     _require(b_scales, "b_scales", like=a_codes)
     a, b = a_codes.contiguous().view(torch.uint8), b_codes.contiguous().view(torch.uint8)
     sa, sb = a_scales.detach().contiguous(), b_scales.detach().contiguous()
-    lead, N = tuple(a.shape[:-1]), int(b.shape[0])
-    M = a.numel() // K
-    y = _mm_out(out, lead + (N,), dt, a)
+    M, N, y = _mm_result(a, b, out, dt)
     if M * N == 0:
         return y
     _run("fp8q_ocpbmm_nt", a, a.data_ptr(), sa.data_ptr(), b.data_ptr(), sb.data_ptr(), y.data_ptr(), M, N, K, *a_tile, *b_tile,
@@ -2644,8 +2653,7 @@ def int_matmul(a_codes, a_delta, b_codes, b_delta, *, a_zero_float=None, a_signe
     dt = _decode_out_dtype(out, out_dtype)
     a_delta, na, K = _int_mm_operand(a_codes, a_delta, a_n_bits, "a")
     b_delta, nb, Kb = _int_mm_operand(b_codes, b_delta, b_n_bits, "b")
-    if K != Kb:
-        raise Fp8qError(f"the operands disagree on K: a has {K} elements along its last dimension, b has {Kb}")
+    _mm_same_k(K, Kb)
     if not 1 <= K <= INT_MM_MAX_K:
         raise Fp8qError(f"K must be in 1..{INT_MM_MAX_K} (beyond, the integer part does not fit int32), got {K}")
     _require(a_codes, "a_codes", torch.uint8)
@@ -2655,9 +2663,7 @@ def int_matmul(a_codes, a_delta, b_codes, b_delta, *, a_zero_float=None, a_signe
     pa = _int_ptrs(a_codes, a_delta, a_zero_float, a_signed_flag, a_symmetric, na)
     pb = _int_ptrs(a_codes, b_delta, b_zero_float, b_signed_flag, b_symmetric, nb)
     a, b = a_codes.contiguous(), b_codes.contiguous()
-    lead, N = tuple(a.shape[:-1]), int(b.shape[0])
-    M = a.numel() // K
-    y = _mm_out(out, lead + (N,), dt, a)
+    M, N, y = _mm_result(a, b, out, dt)
     if M * N == 0:
         return y
     _run("fp8q_i8mm_nt", a, a.data_ptr(), *pa, na, a_n_bits, int(bool(a_symmetric)), b.data_ptr(), *pb, nb, b_n_bits,

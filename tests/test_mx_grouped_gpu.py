@@ -3,7 +3,8 @@
 Operands, PAIRS and FACTOR are tests/test_mx_mm_gpu.py's; its docstring has the argument why the exact operands' sums are the
 same bits in every summation order (K <= 384).  Group counts [0, 1, 33, 128, 0, 130, 0]: an empty first, middle and last group,
 one row, one row past a 32-tile, exactly one 128-tile, a 128-tile plus two rows, and three padding rows (o_G = 292, T = 295).
-N = 129: the tile edge and N % 4 != 0.  K = 160: a full step and a one-block tail; K = 384: three steps, both buffers reused.
+N = 129: the tile edge and N % 4 != 0.  K = 160: a full step and a one-block tail; K = 384: three steps, both buffers reused;
+K = 96 (one mixed pair): a single short step, the loop body run once with nothing in flight.
 Bound cases: FACTOR is not measured on this kernel; it is the instruction's figure for the same chain of K steps.  The largest
 ratio of error to 2^-24 * (|A| . |B|^T) measured, equal for both tile_m (the bits are mx_matmul's, which is asserted):
 E4M3 x E4M3 5563.570, E2M1 x E2M1 0, E2M3 x E5M2 7286.073."""
@@ -37,8 +38,7 @@ def _case(K, fa, fb, exact=True):
     return (a, ac, asc), (b, bc.view(G, N, -1), bsc.view(G, N, -1)), ref
 
 
-@pytest.mark.parametrize("pair", PAIRS, ids=_id)
-@pytest.mark.parametrize("K", [160, 384])
+@pytest.mark.parametrize("K,pair", [(K, p) for K in (160, 384) for p in PAIRS] + [(96, (E4M3, E2M1))], ids=_id)
 @pytest.mark.parametrize("tile_m", [32, 128])
 def test_exact(tile_m, K, pair):
     (_, ac, asc), (_, bc, bsc), ref = _case(K, *pair)

@@ -3,7 +3,8 @@
 
     python tools/kernel_isa_diff.py PARENT_ROOT CHILD_ROOT [--jobs N] [--times]
 
-Every unit in each tree's fp8q/build.py SOURCES is compiled with build.py's flags plus `--cuda-device-only -S`.  A kernel
+Every unit in each tree's fp8q/build.py SOURCES is compiled with build.py's flags (CFLAGS and the unit's EXTRA_CFLAGS, so that
+the code compared is the code that ships) plus `--cuda-device-only -S`.  A kernel
 is its body (label to function end) and its .amdhsa_kernel descriptor block, keyed by unit and demangled name; a kernel
 that left a unit is looked up in the units only the child has (a file split).  Function-local label numbers, which count
 the functions in front of a kernel in its file, are the only thing normalised.  Prints one line per unit, every kernel
@@ -109,7 +110,8 @@ def main():
         for tag, root in (("parent", a.parent), ("child", a.child)):
             b = load_build(os.path.abspath(root))
             trees[tag] = b.SOURCES
-            jobs += [(b._hipcc(), b.CFLAGS, b.CSRC, u, os.path.join(tmp, tag + "_" + u + ".s")) for u in b.SOURCES]
+            jobs += [(b._hipcc(), b.CFLAGS + b.EXTRA_CFLAGS.get(u, []), b.CSRC, u, os.path.join(tmp, tag + "_" + u + ".s"))
+                     for u in b.SOURCES]
         with concurrent.futures.ThreadPoolExecutor(max_workers=a.jobs) as pool:
             done = list(pool.map(compile_unit, jobs))
         cxxfilt = os.path.join(os.path.dirname(jobs[0][0]), "..", "llvm", "bin", "llvm-cxxfilt")
